@@ -2,7 +2,7 @@
 """Headline benchmark: rays/s of the forward hybrid render (query -> gather/aggregate -> composite)
 on the scene0241_01-like synthetic config (BASELINE.json configs[2] / SURVEY.md section 8d C3).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one full 620x460 = 285 200-ray frame of the FIXED scene0241_01-like ray batch (north_star): with N ranks
@@ -19,7 +19,9 @@ rank render a whole frame of its own (value = N x 285 200 / time).
 `python bench.py --gpus N` with WORLD_SIZE unset spawns the N ranks itself (child processes, before anything touches the
 GPU);
 under torch.distributed.run the launcher's RANK / LOCAL_RANK / WORLD_SIZE are used and must agree with --gpus.
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints it; `--full` adds everything
+reported beside the headline (other shard order, training legs, rooflines, fp32 anchor, CPU baseline).
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (hnr_bench.frame.dump_outputs).
 """
 import os
 import sys

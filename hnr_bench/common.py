@@ -54,6 +54,13 @@ def parse():
                     help="strong: the N ranks share ONE fixed frame (north_star); weak: one whole frame per rank")
     ap.add_argument("--dump-colors", default="", help="rank 0 writes the assembled [R,3] colours of the last step to "
                                                       "this .npy file")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the last timed step returned to DIR/<name>.npy (frame.dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything reported beside the headline: the other shard order (N > 1), the training "
+                         "legs, the rooflines, the amortised / resident figures, the fp32-MFMA anchor frame and the CPU "
+                         "baseline (each still subject to its --no-* switch).  Without it a run sets up, warms up, times "
+                         "the steps and prints the line")
     return ap.parse_args()
 
 

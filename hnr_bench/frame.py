@@ -11,6 +11,47 @@ from .common import parse, spawn_ranks, build_world, render_frame
 from .cpu_leg import cpu_baseline
 from .train_legs import train_leg, train_leg_sharded
 
+DUMP_FRAME_BYTES = 12 << 20       # the whole colour frame up to this size (3.4 MB at 620 x 460), a sample of it beyond
+DUMP_SAMPLE_BYTES = 48 << 20      # the per-ray / per-sample outputs of at most DUMP_SAMPLE_RAYS seeded rays within this
+DUMP_SAMPLE_RAYS = 16384
+
+
+def dump_outputs(path, frame, out):
+    """--dump-outputs DIR: what the last timed step returned to its caller, one DIR/<name>.npy per array, float32
+    (float64: the int64 counters and the ray indices), at most DUMP_FRAME_BYTES + DUMP_SAMPLE_BYTES in all.
+    coarse_raycolor = the assembled frame [R, 3].  `out` (render_rays' dict, given when one rank rendered the frame in
+    one launch) adds its other outputs for the rays of sample_rays.npy (a fixed seeded sample) and the frame's counters;
+    the library leaves the slots past a ray's ray_nsamp kept samples unwritten, so they are written as zeros here
+    (sample_pidx: -1), and decoded as zeros where a kept slot found no neighbour (composite reads it only where it did)."""
+    os.makedirs(path, exist_ok=True)
+    save = lambda name, a: np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+    frame = frame.detach().float().cpu()
+    R = frame.shape[0]
+    SR, K = (out["sample_pidx"].shape[1], out["sample_pidx"].shape[2]) if out is not None else (0, 0)
+    per_ray = 12 + SR * (4 + 16 + 12 + 4 * K)          # what one sampled ray adds (float32 throughout)
+    n = min(R, DUMP_SAMPLE_RAYS, DUMP_SAMPLE_BYTES // per_ray)
+    idx = np.sort(np.random.default_rng(0).choice(R, size=n, replace=False))
+    save("sample_rays", idx.astype(np.float64))
+    sel = torch.from_numpy(idx)
+    save("coarse_raycolor", (frame if R * 12 <= DUMP_FRAME_BYTES else frame[sel]).numpy())
+    if out is None:
+        return
+    sel = sel.to(out["coarse_raycolor"].device)
+    g = lambda k: out[k].index_select(0, sel).cpu()
+    nsamp = g("ray_nsamp").long()
+    kept = torch.arange(SR)[None] < nsamp[:, None]                                   # [n, SR]
+    pidx = torch.where(kept[..., None], g("sample_pidx"), torch.tensor(-1, dtype=torch.int32))
+    zero = torch.tensor(0.0)
+    assert int(pidx.max()) < (1 << 24), "point ids past 2^24 are not exact in float32"
+    save("coarse_point_opacity", g("coarse_point_opacity").numpy())
+    save("coarse_is_background", g("coarse_is_background").numpy())
+    save("ray_mask", g("ray_mask").float().numpy())
+    save("ray_nsamp", nsamp.float().numpy())
+    save("sample_pidx", pidx.float().numpy())
+    save("sample_loc_w", torch.where(kept[..., None], g("sample_loc_w"), zero).numpy())
+    save("decoded", torch.where((kept & (pidx[..., 0] >= 0))[..., None], g("decoded"), zero).numpy())
+    save("counts", out["counts"].cpu().double().numpy())
+
 
 def main():
     args = parse()
@@ -153,7 +194,7 @@ def main():
     # SURVEY 8e) in the same run, same steps, so that one record settles the choice (round-4 verdict item 6).  Render
     # only (the gather moves the same bytes either way); max over ranks.
     shard_ab = None
-    if strong and world > 1:
+    if args.full and strong and world > 1:
         other = "blocks" if args.shard == "lines" else "lines"
         if other == "lines":
             mine_o = parallel.shard_lines(R_frame, line * max(1, args.band), world, rank)
@@ -190,8 +231,12 @@ def main():
                     "note": "same run, same frame, same steps; `%s` is what `value` is quoted on" % args.shard}
     if rank == 0 and args.dump_colors:
         np.save(args.dump_colors, frame.detach().cpu().numpy())
+    if rank == 0 and args.dump_outputs:
+        # the per-ray / per-sample outputs describe the whole frame only when one rank rendered it in one launch
+        dump_outputs(args.dump_outputs, frame, out if (world == 1 and not emulate and (args.chunk <= 0 or args.chunk >= R))
+                     else None)
     train_sharded = None
-    if not args.no_train_leg:
+    if args.full and not args.no_train_leg:
         train_sharded = train_leg_sharded(args, sc, opt, agg, cloud, rnd, cam, dev, world, rank, rehearsal, emulate)
         if world == 1 and not emulate and train_sharded and not train_sharded.get("error"):
             # what sharding this batch over 8 GPUs could buy (round-5 verdict): rank 0's 1/8 share alone on this GPU,
@@ -210,27 +255,25 @@ def main():
         counts = out["counts"].cpu().numpy() if args.chunk <= 0 or args.chunk >= R else None
         stage_ms = R_.stage_times(timers, args.steps)
         fused = getattr(rnd, "dense", "f32") == "f16x2" and opt.K == 8
-        roof = roof_q = None
-        if counts is not None:
+        roof = roof_q = amort = resident = f32_anchor = train = cpu = None
+        if args.full and counts is not None:
             roof = R_.chain_roofline(args, rnd, opt, counts, stage_ms, CNT)
             roof_q = R_.query_roofline(args, rnd, opt, cloud, sc, cam, dev, counts, stage_ms, CNT)
-        amort = R_.amortised(rnd, agg, cloud, opt)
-        resident = R_.resident_bytes(rnd, agg, cloud, cam, opt)
-        f32_anchor = None
-        if world == 1 and fused and not emulate and not getattr(args, "no_f32_anchor", False):
+        if args.full:
+            amort = R_.amortised(rnd, agg, cloud, opt)
+            resident = R_.resident_bytes(rnd, agg, cloud, cam, opt)
+        if args.full and world == 1 and fused and not emulate and not getattr(args, "no_f32_anchor", False):
             f32_anchor = R_.fp32_anchor(args, rnd, opt, agg, cloud, cam, sc, dev, col)
         # (the training leg runs BEFORE the CPU baseline: 128 host threads that have just been spinning would perturb a
         # leg whose launches are host-driven)
-        train = None
-        if world == 1 and not args.no_train_leg and not args.train_sharded_only:
+        if args.full and world == 1 and not args.no_train_leg and not args.train_sharded_only:
             try:                            # a leg reported beside the headline must not take the line down
                 train = train_leg(args, sc, opt, agg, cloud, rnd, cam, dev)
             except Exception as ex:         # noqa: BLE001
                 if os.environ.get("HNR_BENCH_STRICT", "0") == "1":
                     raise
                 train = dict(workload="C3 train step", error="%s: %s" % (type(ex).__name__, str(ex)[:300]))
-        cpu = None
-        if not args.no_cpu_baseline and world == 1:          # reported at N=1 only (rank 0)
+        if args.full and not args.no_cpu_baseline and world == 1:          # reported at N=1 only (rank 0)
             cpu = cpu_baseline(args, sc, opt, agg, cam, col.cpu().numpy())
         data = "synthetic"
         if emulate and world == 1:
@@ -242,7 +285,7 @@ def main():
             "value": R_job * args.steps / dt, "unit": "rays/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": args.scaling,
-            "vs_baseline": None,
+            "vs_baseline": None, "full": args.full,
             "dtype": "f32", "dense_arithmetic": R_.DENSE_NOTE[getattr(rnd, "dense", "f32")], "data": data,
             "config": R_.describe_config(args, sc, opt, rnd, R_frame, R_job, R, world, strong),
             "gather_ms": (round(sum(a.elapsed_time(b) for a, b in gather_ev) / max(len(gather_ev), 1),

@@ -734,6 +734,19 @@ def gen_param_keys(ref):
     print("aggregator_param_keys.json:", {k: len(v) for k, v in out.items()})
 
 
+def gen_install_signatures(ref):
+    """Parameter names of the reference callables that modules.install() replaces: the
+    replacements must accept the same names."""
+    import inspect
+    names = lambda f: list(inspect.signature(f).parameters)
+    out = {"NeuralPointsRayMarching.forward": names(ref.vol.NeuralPointsRayMarching.forward),
+           "NeuralPoints.__init__": names(ref.vol.NeuralPoints.__init__),
+           "lighting_fast_querier.query_points": names(ref.qw.lighting_fast_querier.query_points)}
+    with open(os.path.join(HERE, "install_signatures.json"), "w") as f:
+        json.dump(out, f, indent=0, sort_keys=True)
+    print("install_signatures.json:", {k: len(v) for k, v in out.items()})
+
+
 def gen_blur(ref):
     """BaseRenderingModel.blur_update_output (models/base_rendering_model.py:677-745) on a 7x7 grid of 8x8 patches with 12
     normalised 9x9 kernels: new colours, per-patch choice and the gradient of a random linear functional of the output."""
@@ -889,6 +902,7 @@ def main():
     gen_probe_hole(ref)
     gen_cloud_io(ref)
     gen_param_keys(ref)
+    gen_install_signatures(ref)
     gen_blur(ref)
     gen_blur_learn(ref)
     gen_voxel(ref)

@@ -389,31 +389,35 @@ def test_c_abi_rejects_bad_arguments_without_touching_the_gpu():
     assert L.hnr_image_features_scratch_elems(4, 480, 640) == 2 * 4 * (6 * 240 * 320 + 12 * 120 * 160 + 24 * 60 * 80)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/models"), reason="the reference checkout only exists in the build container")
-def test_install_rebinds_the_reference_globals():
-    """hnr.install() swaps the five names the reference's shell resolves by module global."""
-    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
-    from _ref_import import import_reference
-    ref = import_reference()
+def test_install_rebinds_the_reference_globals(monkeypatch):
+    """hnr.install() swaps the five names the reference's shell resolves by module global.  The reference's two
+    modules are stand-ins here; the parameter names of the callables they hold are recorded in tests/golden/install_signatures.json
+    (make_golden.py::gen_install_signatures)."""
+    import inspect
+    import json
+    import types
     import hybridneuralrendering_amd.modules as hnr
     from hybridneuralrendering_amd.aggregator import PointAggregator
     from hybridneuralrendering_amd import querier
-    saved = (ref.vol.NeuralPoints, ref.vol.PointAggregator, ref.vol.NeuralPointsRayMarching, ref.vol.ray_march, ref.npts.lighting_fast_querier_w)
-    try:
-        vol = hnr.install()
-        assert vol is ref.vol
-        assert ref.vol.NeuralPoints is hnr.NeuralPoints and ref.vol.PointAggregator is PointAggregator
-        assert ref.vol.NeuralPointsRayMarching is hnr.NeuralPointsRayMarching and ref.vol.ray_march is hnr.ray_march
-        assert ref.npts.lighting_fast_querier_w is querier.lighting_fast_querier
-        # same constructor / forward parameter names as the classes they replace
-        import inspect
-        for ours, theirs in ((hnr.NeuralPointsRayMarching.forward, saved[2].forward), (hnr.NeuralPoints.__init__, saved[0].__init__),
-                             (querier.lighting_fast_querier.query_points, ref.qw.lighting_fast_querier.query_points)):
-            po = [p for p in inspect.signature(ours).parameters]
-            pt = [p for p in inspect.signature(theirs).parameters]
-            assert po[:len(pt)] == pt or set(pt) <= set(po), (po, pt)
-    finally:
-        (ref.vol.NeuralPoints, ref.vol.PointAggregator, ref.vol.NeuralPointsRayMarching, ref.vol.ray_march, ref.npts.lighting_fast_querier_w) = saved
+    placeholder = object()
+    mods = {}
+    for name in ("models", "models.neural_points", "models.neural_points_volumetric_model", "models.neural_points.neural_points"):
+        mods[name] = types.ModuleType(name)
+        monkeypatch.setitem(sys.modules, name, mods[name])
+    vol, npm = mods["models.neural_points_volumetric_model"], mods["models.neural_points.neural_points"]
+    for n in ("NeuralPoints", "PointAggregator", "NeuralPointsRayMarching", "ray_march"):
+        setattr(vol, n, placeholder)
+    npm.lighting_fast_querier_w = placeholder
+    assert hnr.install() is vol
+    assert vol.NeuralPoints is hnr.NeuralPoints and vol.PointAggregator is PointAggregator
+    assert vol.NeuralPointsRayMarching is hnr.NeuralPointsRayMarching and vol.ray_march is hnr.ray_march
+    assert npm.lighting_fast_querier_w is querier.lighting_fast_querier
+    # same constructor / forward parameter names as the classes they replace
+    theirs = json.load(open(os.path.join(ROOT, "tests", "golden", "install_signatures.json")))
+    for ours, key in ((hnr.NeuralPointsRayMarching.forward, "NeuralPointsRayMarching.forward"), (hnr.NeuralPoints.__init__, "NeuralPoints.__init__"),
+                      (querier.lighting_fast_querier.query_points, "lighting_fast_querier.query_points")):
+        po, pt = list(inspect.signature(ours).parameters), theirs[key]
+        assert po[:len(pt)] == pt or set(pt) <= set(po), (po, pt)
 
 
 def test_ctypes_structs_have_the_layout_of_the_c_header(tmp_path):
@@ -504,7 +508,7 @@ def test_bench_refuses_a_stale_chain_pmc_file(tmp_path, monkeypatch):
     assert busy is None and "another build" in src
 
 
-def test_bench_parent_ends_all_ranks_when_one_fails():
+def test_bench_parent_ends_all_ranks_when_one_fails(tmp_path):
     """`python bench.py --gpus 2` without a launcher spawns the ranks itself.  A rank that dies must not leave the others waiting in a collective: the
     parent watches its children and ends the survivors (round-4 advice).  Here (no GPU) rank 1 is made to outlive rank 0 by far; the parent must come back
     promptly with the exit codes instead of waiting for it."""
@@ -513,20 +517,16 @@ def test_bench_parent_ends_all_ranks_when_one_fails():
     if torch.cuda.is_available():
         pytest.skip("needs a box without a GPU (both ranks fail at once on it: `bench.py needs a GPU`)")
     # rank 1 is put to sleep before it runs a line of bench.py: a sitecustomize on its PYTHONPATH
-    hook = os.path.join(ROOT, "tests", "_sleepy_rank")
-    os.makedirs(hook, exist_ok=True)
+    # (outside the repository tree, so that an interrupted run leaves nothing in it)
+    hook = str(tmp_path)
     with open(os.path.join(hook, "sitecustomize.py"), "w") as f:
         f.write("import os, time\nif os.environ.get('RANK') == '1' and os.environ.get('HNR_TEST_SLEEPY_RANK') == '1':\n    time.sleep(600)\n")
-    try:
-        t0 = time.time()
-        env = dict(os.environ, PYTHONPATH=hook + os.pathsep + os.environ.get("PYTHONPATH", ""), HNR_TEST_SLEEPY_RANK="1")
-        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"], cwd=ROOT, capture_output=True, text=True,
-                           timeout=300, env=env)
-        assert p.returncode != 0 and "rank exit codes" in (p.stderr + p.stdout), (p.returncode, p.stderr[-500:])
-        assert time.time() - t0 < 120, "the parent waited for the surviving rank"
-    finally:
-        import shutil
-        shutil.rmtree(hook, ignore_errors=True)
+    t0 = time.time()
+    env = dict(os.environ, PYTHONPATH=hook + os.pathsep + os.environ.get("PYTHONPATH", ""), HNR_TEST_SLEEPY_RANK="1")
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"], cwd=ROOT, capture_output=True, text=True,
+                       timeout=300, env=env)
+    assert p.returncode != 0 and "rank exit codes" in (p.stderr + p.stdout), (p.returncode, p.stderr[-500:])
+    assert time.time() - t0 < 120, "the parent waited for the surviving rank"
 
 
 def test_torch_library_ops_load_and_carry_schemas():

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_prints_one_json_line_with_the_contract_fields():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--points", "2e5",
-                        "--cpu-sample-rays", "256"], cwd=ROOT, capture_output=True, text=True, timeout=900)
+                        "--cpu-sample-rays", "256", "--full"], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1
@@ -45,7 +45,7 @@ def test_bench_two_rank_rehearsal_of_the_patch_sharded_train_step():
     all-gather of packed point records), not a measurement."""
     e = dict(os.environ, HNR_BENCH_REHEARSAL="1")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--points", "2e5", "--no-cpu-baseline",
-                        "--no-f32-anchor", "--train-sharded-only"], cwd=ROOT, capture_output=True, text=True, timeout=1500, env=e)
+                        "--no-f32-anchor", "--train-sharded-only", "--full"], cwd=ROOT, capture_output=True, text=True, timeout=1500, env=e)
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.strip().startswith("{")][0])
     t = d["train_step_sharded"]
@@ -59,7 +59,7 @@ def _run(extra, env=None, timeout=1500):
     e = dict(os.environ)
     e.update(env or {})
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--points", "2e5", "--no-cpu-baseline",
-                        "--no-train-leg"] + extra, cwd=ROOT, capture_output=True, text=True, timeout=timeout, env=e)
+                        "--no-train-leg", "--full"] + extra, cwd=ROOT, capture_output=True, text=True, timeout=timeout, env=e)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1
@@ -109,3 +109,37 @@ def test_feature_map_repeats_bit_for_bit_beside_another_process():
     assert p.returncode == 0, p.stderr[-2000:]
     last = [l for l in p.stdout.splitlines() if "launches: feature map differs" in l][-1]
     assert last.startswith("0 of 500 launches"), last
+
+
+def test_plain_run_times_only_the_frame_and_dumps_the_same_outputs_twice(tmp_path):
+    """Without --full a run sets up, warms up, times --steps frames and prints the line: the figures reported beside the headline stay None.
+    --dump-outputs writes what the last timed step returned (float32 / float64, at most 64 MB), the same arrays from run to run."""
+    import numpy as np
+    runs = []
+    for i in range(2):
+        out = tmp_path / ("run%d" % i)
+        extra = ["--dump-colors", str(tmp_path / "colors.npy")] if i == 0 else []
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--points", "2e5",
+                            "--dump-outputs", str(out)] + extra, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.strip().startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["full"] is False and d["ms_per_step"] > 0 and d["unit"] == "rays/s"
+        assert abs(d["value"] - d["config"]["rays_per_step"] * 1000.0 / d["ms_per_step"]) < 1e-3 * d["value"]
+        for k in ("roofline", "roofline_query", "amortised_ms", "resident_bytes", "fp32_mfma_anchor", "train_step", "train_step_sharded",
+                  "cpu_baseline", "shard_ab"):
+            assert d[k] is None, k
+        runs.append({f.name[:-len(".npy")]: np.load(f) for f in out.glob("*.npy")})
+    a, b = runs
+    R = d["config"]["rays_per_step"]
+    assert set(a) == {"sample_rays", "coarse_raycolor", "coarse_point_opacity", "coarse_is_background", "ray_mask", "ray_nsamp", "sample_pidx",
+                      "sample_loc_w", "decoded", "counts"}
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["coarse_raycolor"].shape == (R, 3) and a["decoded"].shape[0] == a["sample_rays"].shape[0] == 16384
+    np.testing.assert_array_equal(a["coarse_raycolor"], np.load(tmp_path / "colors.npy"))
+    np.testing.assert_array_equal(a["counts"], list(d["counts"].values()))
+    assert a["ray_mask"].sum() > 0
+    for k, v in a.items():
+        assert v.dtype in (np.float32, np.float64), k
+        np.testing.assert_array_equal(v, b[k], err_msg=k)

@@ -26,7 +26,7 @@ for k, cs in per.items():
         e["wait_inst_any_frac"] = round(c.get("SQ_WAIT_INST_ANY", 0.0) / c["SQ_WAVE_CYCLES"], 4)
     out["chain_ws_kernel" if "chain_ws_kernel" in k else k] = e
     print("%-50s cycles %.0f mfma_busy %s valu/mfma %s" % (k[:50], cyc, e.get("mfma_busy_fraction"), e.get("valu_per_mfma")))
-note = ("rocprofv3 --kernel-trace --pmc, separate passes of `bench.py --no-cpu-baseline --no-train-leg --no-f32-anchor --steps 2 --warmup 1` (tools/gpu_job.sh); "
+note = ("rocprofv3 --kernel-trace --pmc, separate passes of `bench.py --full --no-cpu-baseline --no-train-leg --no-f32-anchor --steps 2 --warmup 1` (tools/gpu_job.sh); "
         "per kernel the LARGEST launch of each counter (the frame launches). SQ_VALU_MFMA_BUSY_CYCLES is summed over the 1024 SIMDs (= 32 x SQ_INSTS_MFMA for "
         "v_mfma_f32_32x32x16_f16); GRBM_GUI_ACTIVE is summed over the 8 XCDs; mfma_busy_fraction = busy cycles per SIMD / kernel cycles.")
 import hashlib

@@ -3,7 +3,7 @@
 # Jobs (run in the order given):
 #   tests[:<pytest args>]  the -m gpu suite (or the given selection)
 #   smoke                  __graft_entry__.smoke()
-#   bench[:<args>]         bench.py, default arguments unless given; prints the line's headline fields
+#   bench[:<args>]         bench.py --full, default arguments unless given; prints the line's headline fields
 #   stats                  rocprofv3 --kernel-trace --stats of a 4-step frame-only bench  -> bench_kernel_stats.csv
 #   traffic                FETCH_SIZE / WRITE_SIZE passes (separate runs)                 -> tools/collect_traffic.py <tag>
 #   pmc                    SQ / GRBM counter groups (separate runs, no other tracing)     -> tools/collect_pmc.py <tag>
@@ -15,7 +15,7 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 TAG=$1; shift
 G=$GRAFT_REPO_ROOT; O=$G/gpurun_out/$TAG; mkdir -p "$O"
-FRAME="python3 $G/bench.py --no-cpu-baseline --no-train-leg --no-f32-anchor"
+FRAME="python3 $G/bench.py --full --no-cpu-baseline --no-train-leg --no-f32-anchor"
 export TMPDIR=/tmp
 for job in "$@"; do
   name=${job%%:*}; arg=""; [ "$job" != "$name" ] && arg=${job#*:}
@@ -25,7 +25,7 @@ for job in "$@"; do
     smoke)
       timeout 600 python3 -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.txt" 2>&1; echo "smoke rc=$?"; tail -2 "$O/smoke.txt";;
     bench)
-      timeout 1500 python3 bench.py $arg > "$O/bench.txt" 2> "$O/bench.err"; echo "bench rc=$?"; tail -2 "$O/bench.err"
+      timeout 1500 python3 bench.py --full $arg > "$O/bench.txt" 2> "$O/bench.err"; echo "bench rc=$?"; tail -2 "$O/bench.err"
       python3 tools/show_bench.py "$O/bench.txt";;
     stats)
       (cd /tmp && rm -rf /tmp/st && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/st -o s -- $FRAME --steps 4 --warmup 1 > "$O/stats.log" 2>&1)
