@@ -151,6 +151,7 @@ SIGNATURES = {
     "hnr_final_color": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P]),
     "hnr_mixup_stage": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _I, _F, _P, _I, _P, _P]),
     "hnr_composite": (_I, [_P] * 8 + [_I, _I, _I, _F, _I, _P, _P, _P, _P, _P]),
+    "hnr_ray_depth": (_I, [_P] * 6 + [_I, _I, _P, _P]),
     "hnr_probe_outputs": (_I, [_P] * 10 + [_I, _I, _I, _I] + [_P] * 7 + [_P]),
     "hnr_ray_march": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "hnr_blur_select": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
@@ -167,6 +168,7 @@ SIGNATURES = {
     "hnr_blur_apply_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     # backward
     "hnr_composite_bwd": (_I, [_P] * 8 + [_I, _I, _I, _F, _I, _P, _P, _P]),
+    "hnr_composite_bwd_depth": (_I, [_P] * 8 + [_I, _I, _I, _F, _I, _P, _P, _P, _P]),
     "hnr_final_color_bwd": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P]),
     "hnr_merge_bwd": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _F, _P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _P]),
     "hnr_proj_rows_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, ctypes.c_int64, _P]),
@@ -198,6 +200,9 @@ SIGNATURES = {
     "hnr_render_train_backward": (_I, [ctypes.POINTER(TrainParams), ctypes.POINTER(TrainCloud), ctypes.POINTER(TrainWeights), ctypes.POINTER(RenderCamera),
                                        ctypes.POINTER(TrainViews), _P, ctypes.c_int64, ctypes.POINTER(RenderOutputs), _P, _P, ctypes.POINTER(TrainCloudGrads),
                                        ctypes.POINTER(TrainWeights), _P]),
+    "hnr_render_train_backward_depth": (_I, [ctypes.POINTER(TrainParams), ctypes.POINTER(TrainCloud), ctypes.POINTER(TrainWeights), ctypes.POINTER(RenderCamera),
+                                             ctypes.POINTER(TrainViews), _P, ctypes.c_int64, ctypes.POINTER(RenderOutputs), _P, _P, _P,
+                                             ctypes.POINTER(TrainCloudGrads), ctypes.POINTER(TrainWeights), _P]),
 }
 
 _lib = None

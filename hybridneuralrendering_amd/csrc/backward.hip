@@ -39,10 +39,16 @@ struct CompositeBwdArgs {
     float vsize_z;
     int unit_mode;
     const float *g_raycolor;                             // [R,3] gradient of the (fill_invalid'ed) ray colour
+    const float *g_depth;                                // [R] gradient of the expected depth (DEPTH kernels only)
     float *g_decoded;                                    // [R,SR,4] out: (d sigma, d rgb); doubles as the per-ray scratch
 };
 
+// DEPTH: the gradient of the expected depth D = sum_s w_s z_s / (W + 1e-6), W = sum_s w_s (hnr_ray_depth, csrc/depth.hip) is added.  It is the
+// colour's backward with one more per-sample "colour" c_s = dD/dw_s g_D = g_D (z_s - D) / (W + 1e-6) and a background of 0: c_s joins gs.
+// A and W are summed in the front-to-back pass.  DEPTH = false is the colour-only kernel, unchanged.
+
 // one thread per ray: any SR (the wave-per-ray form below holds a ray's samples in the lanes of one wave: SR <= 64)
+template <bool DEPTH>
 __global__ __launch_bounds__(256) void composite_bwd_serial_kernel(CompositeBwdArgs a)
 {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -63,8 +69,8 @@ __global__ __launch_bounds__(256) void composite_bwd_serial_kernel(CompositeBwdA
         const float s0 = __fsub_rn(q0, cp[0]), s1 = __fsub_rn(q1, cp[1]), s2 = __fsub_rn(q2, cp[2]);
         return __fadd_rn(__fadd_rn(__fmul_rn(cr[2], s0), __fmul_rn(cr[5], s1)), __fmul_rn(cr[8], s2));
     };
-    // pass 1 (front to back, identical to composite_kernel): park (opacity, ray_dist * valid, T before the sample)
-    float T = 1.f;
+    // pass 1 (front to back, identical to composite_kernel): park (opacity, ray_dist * valid, T before the sample[, z])
+    float T = 1.f, A = 0.f, Wsum = 0.f;
     float zmax = zc(0);
     for (int s = 0; s < a.SR; ++s) {
         float dist;
@@ -81,18 +87,31 @@ __global__ __launch_bounds__(256) void composite_bwd_serial_kernel(CompositeBwdA
         const float sigma = valid ? d.x : 0.f;
         const float rd = valid ? dist : 0.f;
         const float o = 1.f - expf(-sigma * rd);
-        dd[s] = make_float4(o, rd, T, 0.f);
+        float zs = 0.f;
+        if (DEPTH) {
+            zs = zc(s);
+            const float w = o * T;
+            A += w * zs;
+            Wsum += w;
+        }
+        dd[s] = make_float4(o, rd, T, zs);
         T *= (1.f - o + 1e-10f);
     }
     // pass 2 (back to front).  colour = sum_s w_s rgb_s + bg T_end,  w_s = o_s T_s,  T_s = prod_{j<s} q_j,  q = 1 - o + 1e-10:
     //   d/d o_s = T_s (rgb_s . g) - (sum_{j>s} w_j (rgb_j . g) + (bg . g) T_end) / q_s
     const float g0 = a.g_raycolor[3 * (size_t)r], g1 = a.g_raycolor[3 * (size_t)r + 1], g2 = a.g_raycolor[3 * (size_t)r + 2];
     float S = (a.bg[0] * g0 + a.bg[1] * g1 + a.bg[2] * g2) * T;
+    float D = 0.f, kD = 0.f;
+    if (DEPTH) {
+        D = hnr_div(A, Wsum + 1e-6f);
+        kD = hnr_div(a.g_depth[r], Wsum + 1e-6f);
+    }
     for (int s = a.SR - 1; s >= 0; --s) {
         const float4 t = dd[s];
         const float o = t.x, rd = t.y, Ts = t.z;
         const float4 d = reinterpret_cast<const float4 *>(a.decoded)[(size_t)r * a.SR + s];
-        const float gs = d.y * g0 + d.z * g1 + d.w * g2;
+        float gs = d.y * g0 + d.z * g1 + d.w * g2;
+        if (DEPTH) gs += kD * (t.w - D);
         const float q = 1.f - o + 1e-10f;
         const float d_o = Ts * gs - hnr_div(S, q);
         const float w = o * Ts;
@@ -107,6 +126,7 @@ __global__ __launch_bounds__(256) void composite_bwd_serial_kernel(CompositeBwdA
 // to back: running depth maximum and transmittance; back to front: the suffix sum S) then run over wave-uniform values fetched with
 // v_readlane, each lane keeping the step that is its own.  The same operations in the same order as one thread per ray -- which took 56 us
 // for 3 136 rays: 2 x 24 dependent steps, each waiting for its own loads (thirteen workgroups on the whole chip).
+template <bool DEPTH>
 __global__ __launch_bounds__(256) void composite_bwd_kernel(CompositeBwdArgs a)
 {
     const int lane = threadIdx.x & 63;
@@ -136,6 +156,7 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(CompositeBwdArgs a)
     // pass 1 (front to back, identical to composite_kernel): (opacity, ray_dist * valid, T before the sample) of every sample
     float T = 1.f, zmax = bc(z_l, 0);
     float o_l = 0.f, rd_l = 0.f, T_l = 1.f;
+    float A = 0.f, Wsum = 0.f;                           // DEPTH: sum_s w_s z_s, sum_s w_s
     for (int s = 0; s < a.SR; ++s) {
         float dist;
         if (s + 1 < a.SR) {
@@ -151,13 +172,19 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(CompositeBwdArgs a)
         const float rd = valid ? dist : 0.f;
         const float o = 1.f - expf(-sigma * rd);
         if (lane == s) { o_l = o; rd_l = rd; T_l = T; }
+        if (DEPTH) {
+            const float w = o * T;
+            A += w * bc(z_l, s);
+            Wsum += w;
+        }
         T *= (1.f - o + 1e-10f);
     }
     // pass 2 (back to front).  colour = sum_s w_s rgb_s + bg T_end,  w_s = o_s T_s,  T_s = prod_{j<s} q_j,  q = 1 - o + 1e-10:
     //   d/d o_s = T_s (rgb_s . g) - (sum_{j>s} w_j (rgb_j . g) + (bg . g) T_end) / q_s
     const float g0 = a.g_raycolor[3 * (size_t)r], g1 = a.g_raycolor[3 * (size_t)r + 1], g2 = a.g_raycolor[3 * (size_t)r + 2];
     float S = (a.bg[0] * g0 + a.bg[1] * g1 + a.bg[2] * g2) * T;
-    const float gs_l = d_l.y * g0 + d_l.z * g1 + d_l.w * g2;
+    float gs_l = d_l.y * g0 + d_l.z * g1 + d_l.w * g2;
+    if (DEPTH) gs_l += hnr_div(a.g_depth[r], Wsum + 1e-6f) * (z_l - hnr_div(A, Wsum + 1e-6f));
     const float w_l = o_l * T_l;
     float S_l = 0.f;                                     // S as it stands when the loop reaches this lane's sample
     for (int s = a.SR - 1; s >= 0; --s) {
@@ -906,24 +933,48 @@ static int persistent_blocks(int64_t n_waves_wanted)
 }
 
 // ================================================================================== C ABI
+// d_g_depth == NULL: the colour-only kernels (the bits of hnr_composite_bwd)
+static int composite_bwd(const char *name, const float *d_decoded, const float *d_sample_loc_w, const int32_t *d_sample_pidx, const int8_t *d_ray_mask,
+                         const int32_t *d_ray_nsamp, const float *d_campos, const float *d_camrot, const float *d_bg_color, int R, int SR, int K,
+                         float vsize_z, int raydist_mode_unit, const float *d_g_raycolor, const float *d_g_depth, float *d_g_decoded, void *stream)
+{
+    if (R < 0 || SR <= 0 || K <= 0) { set_error("%s: bad sizes", name); return HNR_ERR_BADARG; }
+    if (R == 0) return HNR_OK;
+    if (!d_decoded || !d_sample_loc_w || !d_sample_pidx || !d_ray_mask || !d_campos || !d_camrot || !d_bg_color || !d_g_raycolor || !d_g_decoded) {
+        set_error("%s: NULL argument", name); return HNR_ERR_BADARG;
+    }
+    CompositeBwdArgs a;
+    a.decoded = d_decoded; a.loc_w = d_sample_loc_w; a.pidx = d_sample_pidx; a.ray_mask = d_ray_mask; a.nsamp = d_ray_nsamp;
+    a.campos = d_campos; a.camrot = d_camrot; a.bg = d_bg_color; a.R = R; a.SR = SR; a.K = K; a.vsize_z = vsize_z;
+    a.unit_mode = raydist_mode_unit; a.g_raycolor = d_g_raycolor; a.g_depth = d_g_depth; a.g_decoded = d_g_decoded;
+    const hipStream_t st = (hipStream_t)stream;
+    if (SR <= 64) {
+        if (d_g_depth) composite_bwd_kernel<true><<<cdiv((int64_t)R * 64, 256), 256, 0, st>>>(a);
+        else composite_bwd_kernel<false><<<cdiv((int64_t)R * 64, 256), 256, 0, st>>>(a);
+    } else {
+        if (d_g_depth) composite_bwd_serial_kernel<true><<<cdiv(R, 256), 256, 0, st>>>(a);
+        else composite_bwd_serial_kernel<false><<<cdiv(R, 256), 256, 0, st>>>(a);
+    }
+    HNR_LAUNCH_CHECK();
+    return HNR_OK;
+}
+
 extern "C" int hnr_composite_bwd(const float *d_decoded, const float *d_sample_loc_w, const int32_t *d_sample_pidx, const int8_t *d_ray_mask,
                                  const int32_t *d_ray_nsamp, const float *d_campos, const float *d_camrot, const float *d_bg_color,
                                  int R, int SR, int K, float vsize_z, int raydist_mode_unit, const float *d_g_raycolor,
                                  float *d_g_decoded, void *stream)
 {
-    if (R < 0 || SR <= 0 || K <= 0) { set_error("hnr_composite_bwd: bad sizes"); return HNR_ERR_BADARG; }
-    if (R == 0) return HNR_OK;
-    if (!d_decoded || !d_sample_loc_w || !d_sample_pidx || !d_ray_mask || !d_campos || !d_camrot || !d_bg_color || !d_g_raycolor || !d_g_decoded) {
-        set_error("hnr_composite_bwd: NULL argument"); return HNR_ERR_BADARG;
-    }
-    CompositeBwdArgs a;
-    a.decoded = d_decoded; a.loc_w = d_sample_loc_w; a.pidx = d_sample_pidx; a.ray_mask = d_ray_mask; a.nsamp = d_ray_nsamp;
-    a.campos = d_campos; a.camrot = d_camrot; a.bg = d_bg_color; a.R = R; a.SR = SR; a.K = K; a.vsize_z = vsize_z;
-    a.unit_mode = raydist_mode_unit; a.g_raycolor = d_g_raycolor; a.g_decoded = d_g_decoded;
-    if (SR <= 64) composite_bwd_kernel<<<cdiv((int64_t)R * 64, 256), 256, 0, (hipStream_t)stream>>>(a);
-    else composite_bwd_serial_kernel<<<cdiv(R, 256), 256, 0, (hipStream_t)stream>>>(a);
-    HNR_LAUNCH_CHECK();
-    return HNR_OK;
+    return composite_bwd("hnr_composite_bwd", d_decoded, d_sample_loc_w, d_sample_pidx, d_ray_mask, d_ray_nsamp, d_campos, d_camrot, d_bg_color, R, SR,
+                         K, vsize_z, raydist_mode_unit, d_g_raycolor, nullptr, d_g_decoded, stream);
+}
+
+extern "C" int hnr_composite_bwd_depth(const float *d_decoded, const float *d_sample_loc_w, const int32_t *d_sample_pidx, const int8_t *d_ray_mask,
+                                       const int32_t *d_ray_nsamp, const float *d_campos, const float *d_camrot, const float *d_bg_color,
+                                       int R, int SR, int K, float vsize_z, int raydist_mode_unit, const float *d_g_raycolor,
+                                       const float *d_g_depth, float *d_g_decoded, void *stream)
+{
+    return composite_bwd("hnr_composite_bwd_depth", d_decoded, d_sample_loc_w, d_sample_pidx, d_ray_mask, d_ray_nsamp, d_campos, d_camrot, d_bg_color,
+                         R, SR, K, vsize_z, raydist_mode_unit, d_g_raycolor, d_g_depth, d_g_decoded, stream);
 }
 
 extern "C" int hnr_final_color_bwd(const float *d_Y, int ldy, const float *d_CF, int ldcf, const float *d_w_fin, const float *d_b_fin,

@@ -673,17 +673,18 @@ extern "C" int hnr_render_train_forward(const hnr_grid *grid, const hnr_train_pa
     return HNR_OK;
 }
 
-extern "C" int hnr_render_train_backward(const hnr_train_params *p, const hnr_train_cloud *cl, const hnr_train_weights *w, const hnr_render_camera *cam,
-                                         const hnr_train_views *vw, void *d_workspace, int64_t workspace_bytes, const hnr_render_outputs *o,
-                                         const float *d_g_raycolor, const float *d_g_conf_coefficient, const hnr_train_cloud_grads *gc,
-                                         const hnr_train_weights *gw_, void *stream)
+// d_g_depth == NULL: hnr_render_train_backward (the colour-only composite transpose)
+static int train_backward(const char *name, const hnr_train_params *p, const hnr_train_cloud *cl, const hnr_train_weights *w, const hnr_render_camera *cam,
+                          const hnr_train_views *vw, void *d_workspace, int64_t workspace_bytes, const hnr_render_outputs *o,
+                          const float *d_g_raycolor, const float *d_g_conf_coefficient, const float *d_g_depth, const hnr_train_cloud_grads *gc,
+                          const hnr_train_weights *gw_, void *stream)
 {
-    TR(check_params(p, "hnr_render_train_backward"));
-    if (!cl || !w || !cam || !o || !gc || !gw_ || !d_g_raycolor || (p->V > 0 && !vw)) { set_error("hnr_render_train_backward: NULL argument"); return HNR_ERR_BADARG; }
-    if (!d_workspace || ((uintptr_t)d_workspace & 255)) { set_error("hnr_render_train_backward: workspace must be 256-byte aligned"); return HNR_ERR_BADARG; }
+    TR(check_params(p, name));
+    if (!cl || !w || !cam || !o || !gc || !gw_ || !d_g_raycolor || (p->V > 0 && !vw)) { set_error("%s: NULL argument", name); return HNR_ERR_BADARG; }
+    if (!d_workspace || ((uintptr_t)d_workspace & 255)) { set_error("%s: workspace must be 256-byte aligned", name); return HNR_ERR_BADARG; }
     bool ok = true;
     const Layout L = carve(d_workspace, (size_t)workspace_bytes, p, &ok);
-    if (!ok) { set_error("hnr_render_train_backward: workspace too small"); return HNR_ERR_BADARG; }
+    if (!ok) { set_error("%s: workspace too small", name); return HNR_ERR_BADARG; }
     // the gradient block has the parameter block's layout; its pointers are written through
     struct G { float *block1_0_w, *block1_0_b, *block1_2_w, *block1_2_b, *block3_0_w, *block3_0_b, *block3_2_w, *block3_2_b, *alpha_w, *alpha_b;
                float *cf_w[3], *cf_b[3], *mw_w[4], *mw_b[4], *mx_w[3], *mx_b[3], *fin_w, *fin_b, *conv_w[6], *conv_b[6]; };
@@ -761,9 +762,9 @@ extern "C" int hnr_render_train_backward(const hnr_train_params *p, const hnr_tr
         return hnr_h2lin(dZ, ldz, Mcap, dm, nseg, segs, L.img[im], Nn, Kk, side ? 1 : 0, 0, sl, side, lds_, out, ldo, amo >= 0 ? am + amo : nullptr, stream);
     };
     TR(mark());
-    // ---- 1. composite, 2. final colour
-    TR(hnr_composite_bwd(o->d_decoded, o->d_sample_loc_w, o->d_sample_pidx, o->d_ray_mask, nullptr, cam->d_campos, cam->d_camrot, cam->d_bg_color, R, SR, K, p->vsize_z,
-                         p->raydist_mode_unit, d_g_raycolor, L.g_dec, stream));
+    // ---- 1. composite (+ the expected depth's term when its gradient is given), 2. final colour
+    TR(hnr_composite_bwd_depth(o->d_decoded, o->d_sample_loc_w, o->d_sample_pidx, o->d_ray_mask, nullptr, cam->d_campos, cam->d_camrot, cam->d_bg_color, R, SR, K,
+                               p->vsize_z, p->raydist_mode_unit, d_g_raycolor, d_g_depth, L.g_dec, stream));
     TR(final_color_bwd_max(L.Y3, 48, L.CF, 128, w->fin_w, w->fin_b, L.vs_item, o->d_counts, cap, L.g_dec, L.gY3, 48, L.gCF, 128, L.g_sigma, g.fin_w, g.fin_b, am + AM_gY3,
                            stream));
     // ---- 3. mix-up block (its last layer has no activation: gY3 is the gradient of its pre-activation)
@@ -883,4 +884,22 @@ extern "C" int hnr_render_train_backward(const hnr_train_params *p, const hnr_tr
     HNR_LAUNCH_CHECK();
     guard.armed = false;
     return HNR_OK;
+}
+
+extern "C" int hnr_render_train_backward(const hnr_train_params *p, const hnr_train_cloud *cl, const hnr_train_weights *w, const hnr_render_camera *cam,
+                                         const hnr_train_views *vw, void *d_workspace, int64_t workspace_bytes, const hnr_render_outputs *o,
+                                         const float *d_g_raycolor, const float *d_g_conf_coefficient, const hnr_train_cloud_grads *gc,
+                                         const hnr_train_weights *gw_, void *stream)
+{
+    return train_backward("hnr_render_train_backward", p, cl, w, cam, vw, d_workspace, workspace_bytes, o, d_g_raycolor, d_g_conf_coefficient, nullptr, gc,
+                          gw_, stream);
+}
+
+extern "C" int hnr_render_train_backward_depth(const hnr_train_params *p, const hnr_train_cloud *cl, const hnr_train_weights *w,
+                                               const hnr_render_camera *cam, const hnr_train_views *vw, void *d_workspace, int64_t workspace_bytes,
+                                               const hnr_render_outputs *o, const float *d_g_raycolor, const float *d_g_conf_coefficient,
+                                               const float *d_g_depth, const hnr_train_cloud_grads *gc, const hnr_train_weights *gw_, void *stream)
+{
+    return train_backward("hnr_render_train_backward_depth", p, cl, w, cam, vw, d_workspace, workspace_bytes, o, d_g_raycolor, d_g_conf_coefficient, d_g_depth,
+                          gc, gw_, stream);
 }

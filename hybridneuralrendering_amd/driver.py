@@ -16,12 +16,13 @@ from ._lib import HnrError
 from . import parallel
 
 
-def render_image(renderer, cloud, frame, chunk_rays=0, sharded=None, group=None):
+def render_image(renderer, cloud, frame, chunk_rays=0, sharded=None, group=None, depth=False):
     """frame: dict with the dataset item of the reference (data/scannet_ft_dataset.py:855-976), batch dim optional:
     raydir [R,3], pixel_idx [R,2] (x, y), campos [3], camrotc2w [3,3], bg_color [3], near, far, h, w, c2w_nearest [V,4,4],
     campos_nearest [V,3], intrinsic_nearest [3,3], images_nearest [V,H,W,3] (+ optional frame_weight_nearest [V]).
     Returns dict(image [h,w,3] (zero where no ray was cast: run/test_ft.py:191 scatters into np.zeros), ray_mask [R] i8, coarse_raycolor [R,3]) --
-    on rank 0 when sharded, None on the other ranks."""
+    on rank 0 when sharded, None on the other ranks.  depth=True adds depth [h,w] (zero where no ray was cast) and coarse_depth [R], the expected
+    camera-space depth of every ray (render_rays(want_depth=True); 0 where ray_mask = 0); sharded, it travels as a fifth row column."""
     sq = lambda t, nd: t.reshape(t.shape[-nd:]) if isinstance(t, torch.Tensor) else t
     raydir = sq(frame["raydir"], 2)
     pix = sq(frame["pixel_idx"], 2)
@@ -43,9 +44,10 @@ def render_image(renderer, cloud, frame, chunk_rays=0, sharded=None, group=None)
             o = renderer.render_rays(cloud, rays[lo:lo + step].contiguous(), sq(frame["campos"], 1), sq(frame["camrotc2w"], 2),
                                      sq(frame["bg_color"], 1), near, far, sq(frame["c2w_nearest"], 3), sq(frame["campos_nearest"], 2),
                                      sq(frame["intrinsic_nearest"], 2), sq(frame["images_nearest"], 4),
-                                     frame_weight=None if fw is None else sq(fw, 1))
+                                     frame_weight=None if fw is None else sq(fw, 1), want_depth=depth)
             statuses.append(o)
-            outs.append(torch.cat([o["coarse_raycolor"], o["ray_mask"].to(torch.float32)[:, None]], dim=1))
+            cols = [o["coarse_raycolor"], o["ray_mask"].to(torch.float32)[:, None]] + ([o["coarse_depth"][:, None]] if depth else [])
+            outs.append(torch.cat(cols, dim=1))
         return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
 
     def render_auto(rays):
@@ -70,4 +72,10 @@ def render_image(renderer, cloud, frame, chunk_rays=0, sharded=None, group=None)
     img = torch.zeros((h, w, 3), dtype=torch.float32, device=col.device)        # test_ft.py:191 `np.zeros((height, width, 3))`: the margin stays zero
     px, py = pix[:, 0].to(col.device, torch.long), pix[:, 1].to(col.device, torch.long)
     img[py, px] = col                                            # test_ft.py:193 `visuals[key][y, x, :] = chunk`, on the device
-    return dict(image=img, ray_mask=mask, coarse_raycolor=col)
+    res = dict(image=img, ray_mask=mask, coarse_raycolor=col)
+    if depth:
+        d = rows[:, 4].contiguous()
+        dimg = torch.zeros((h, w), dtype=torch.float32, device=col.device)
+        dimg[py, px] = d
+        res.update(depth=dimg, coarse_depth=d)
+    return res

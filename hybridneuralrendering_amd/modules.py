@@ -245,7 +245,13 @@ class NeuralPoints(nn.Module):
 # ------------------------------------------------------------------------------------------------ ray marching
 class NeuralPointsRayMarching(nn.Module):
     """Same constructor and forward signature / output dict as the reference (:219-391); the forward runs the fused
-    HIP path (HybridRenderer) and then compacts to the reference's valid-ray row layout."""
+    HIP path (HybridRenderer) and then compacts to the reference's valid-ray row layout.
+
+    is_compute_depth (set by --compute_depth or any --depth_loss_items, :141): output["coarse_depth"] [1,R'] is the expected depth of every
+    valid ray, sum_s w_s z_s / (sum_s w_s + 1e-6) with w = the blend weight and z = the shading sample's camera-space depth (:381-385, whose
+    undefined `ray_ts` is read as sample_loc[..., 2], the quantity ray_dist is built from, :331).  In training it is attached to autograd
+    (HIP backward), so a depth loss item back-propagates.  Unlike the reference, which overwrites its local `weight` with the blend weight at
+    :383, output["weight"] stays the aggregator's [1,R',SR,K] weight with depth on or off."""
 
     def __init__(self, tonemap_func=None, render_func=None, blend_func=None, aggregator=None, is_compute_depth=False,
                  neural_points=None, opt=None, num_pos_freqs=0, num_viewdir_freqs=0, **kwargs):
@@ -256,8 +262,6 @@ class NeuralPointsRayMarching(nn.Module):
         self.return_depth, self.return_color = is_compute_depth, True
         self.opt = opt
         self.neural_points = neural_points
-        if is_compute_depth:
-            raise HnrError("compute_depth is unsupported (no shipped config sets it; the reference path itself references an undefined ray_ts)")
         self._renderer = None
         self._train_path = None
 
@@ -286,11 +290,13 @@ class NeuralPointsRayMarching(nn.Module):
             npnt = self.neural_points
             full = render_train(self._train_path, self.aggregator, npnt.xyz, npnt.points_embeding, npnt.points_conf, npnt.points_dir,
                                 npnt.points_color, raydir[0], campos[0], camrotc2w[0], bg_color[0], nearv, farv, c2w_nearest[0],
-                                campos_nearest[0], intrinsic_nearest[0], images_nearest[0], frame_weight=fw, tmid=kargs.get("tmid"))
+                                campos_nearest[0], intrinsic_nearest[0], images_nearest[0], frame_weight=fw, tmid=kargs.get("tmid"),
+                                want_depth=bool(self.return_depth))
         else:
             cloud = self.neural_points.cloud()
             full = rnd.render_rays(cloud, raydir[0], campos[0], camrotc2w[0], bg_color[0], nearv, farv, c2w_nearest[0], campos_nearest[0],
-                                   intrinsic_nearest[0], images_nearest[0], frame_weight=fw, want_weights=True, pad=True)
+                                   intrinsic_nearest[0], images_nearest[0], frame_weight=fw, want_weights=True, pad=True,
+                                   want_depth=bool(self.return_depth))
         mask = full["ray_mask"]
         rows = torch.nonzero(mask)[:, 0]                                  # valid rays, in ray order (:705-709)
         sel = lambda t: t.index_select(0, rows)[None]
@@ -307,6 +313,8 @@ class NeuralPointsRayMarching(nn.Module):
         out["weight"] = sel(full["weight"])
         out["blend_weight"] = sel(full["blend_weight"])[..., None]
         out["conf_coefficient"] = sel(full["conf_coefficient"])
+        if self.return_depth:
+            out["coarse_depth"] = sel(full["coarse_depth"])               # [1,R'] (:385; not among fill_invalid's keys)
         if getattr(self.opt, "prob", 0) == 1 and rows.numel() > 0:
             out.update(self._probe_outputs(full, rows))
         return out

@@ -25,6 +25,19 @@ def _f32(shape, dev):
     return torch.empty(shape, dtype=torch.float32, device=dev)
 
 
+def ray_depth(blend_weight, sample_loc_w, ray_nsamp, ray_mask, campos, camrot):
+    """Expected depth [R] of every ray (hnr_ray_depth): sum_s w_s z_s / (sum_s w_s + 1e-6) with w = blend_weight [R,SR] and z = the camera-space
+    depth of sample_loc_w [R,SR,3] -- the compute_depth branch of the reference (models/neural_points_volumetric_model.py:381-385) with its
+    undefined `ray_ts` read as sample_loc[..., 2] (:331).  ray_nsamp: None for padded query outputs.  0 where ray_mask = 0."""
+    R, SR = blend_weight.shape
+    depth = _f32((R,), blend_weight.device)
+    p = _lib.ptr
+    with torch.cuda.device(blend_weight.device):
+        _lib.check(_lib.lib().hnr_ray_depth(p(blend_weight), p(sample_loc_w), p(ray_nsamp), p(ray_mask), p(campos), p(camrot), R, SR, p(depth),
+                                            _lib.stream()), "hnr_ray_depth")
+    return depth
+
+
 class _Stage:
     """Optional HIP-event bracket around a stage (events are recorded on the launch stream)."""
 
@@ -348,24 +361,29 @@ class HybridRenderer:
         return out
 
     # -- stage 4 ------------------------------------------------------------------------------------
-    def composite(self, decoded, qres, campos, camrot, bg_color, want_blend=False):
+    def composite(self, decoded, qres, campos, camrot, bg_color, want_blend=False, want_depth=False):
+        """want_depth: also coarse_depth [R] (hnr_ray_depth over the blend weights, which are then computed too)."""
         L = _lib.lib()
         pidx, loc_w, mask = qres["sample_pidx"], qres["sample_loc_w"], qres["ray_mask"]
         R, SR, K = pidx.shape
         dev = pidx.device
         col, opa, isbg = _f32((R, 3), dev), _f32((R, SR), dev), _f32((R,), dev)
-        bw = _f32((R, SR), dev) if want_blend else None
+        bw = _f32((R, SR), dev) if (want_blend or want_depth) else None
+        nsamp = None if qres.get("padded", True) else qres["ray_nsamp"]
         p = _lib.ptr
         with torch.cuda.device(dev):
-            _lib.check(L.hnr_composite(p(decoded), p(loc_w), p(pidx), p(mask), None if qres.get("padded", True) else p(qres["ray_nsamp"]),
+            _lib.check(L.hnr_composite(p(decoded), p(loc_w), p(pidx), p(mask), p(nsamp),
                                        p(campos), p(camrot), p(bg_color), R, SR, K,
                                        float(np.float32(self.opt.vsize[2])), int(getattr(self.opt, "raydist_mode_unit", 0) > 0),
-                                       p(col), p(opa), p(isbg), p(bw) if want_blend else None, _lib.stream()), "hnr_composite")
-        return dict(coarse_raycolor=col, coarse_point_opacity=opa, coarse_is_background=isbg, blend_weight=bw)
+                                       p(col), p(opa), p(isbg), p(bw), _lib.stream()), "hnr_composite")
+        out = dict(coarse_raycolor=col, coarse_point_opacity=opa, coarse_is_background=isbg, blend_weight=bw if want_blend else None)
+        if want_depth:
+            out["coarse_depth"] = ray_depth(bw, loc_w, nsamp, mask, campos, camrot)
+        return out
 
     # -- the whole path as ONE library call (no host read between query and composite) ---------------
     def _single_call(self, cloud, raydir, campos, camrot, bg_color, tmid, grid, radius2, w2c_nearest, campos_nearest, intrinsic_nearest, fm,
-                     frame_weight, want_weights, timers, fm_ready=None):
+                     frame_weight, want_weights, timers, fm_ready=None, want_depth=False):
         """hnr_render_forward: every launch of the frame issued by the library on the current stream; workspaces sized for the worst
         case R*SR valid samples (or what fits: the status word reports an overflow), no `.cpu()` / `.item()` on the way."""
         L, p = _lib.lib(), _lib.ptr
@@ -402,7 +420,7 @@ class HybridRenderer:
             vw = _lib.RenderViews(p(w2c_nearest), p(intrinsic_nearest), p(campos_nearest), p(fm), int(fm.shape[1]), int(fm.shape[2]),
                                   p(fw) if fw is not None else None, ctypes.c_void_p(fm_ready.cuda_event) if fm_ready is not None else None)
         col, opa, isbg = _f32((R, 3), dev), _f32((R, SR), dev), _f32((R,), dev)
-        bw = _f32((R, SR), dev) if want_weights else None
+        bw = _f32((R, SR), dev) if (want_weights or want_depth) else None
         mask = torch.empty((R,), dtype=torch.int8, device=dev)
         decoded = _f32((R, SR, 4), dev)
         pidx = torch.empty((R, SR, K), dtype=torch.int32, device=dev)
@@ -426,10 +444,12 @@ class HybridRenderer:
                                             ctypes.byref(vw) if vw is not None else None, ctypes.c_void_p(ws.data_ptr() + off), nbytes,
                                             ctypes.byref(out), _lib.stream()), "hnr_render_forward")
         self._keepalive = (ws, fw)             # the launches are asynchronous: the workspace must outlive them (next call replaces it)
-        res = dict(coarse_raycolor=col, coarse_point_opacity=opa, coarse_is_background=isbg, blend_weight=bw, ray_mask=mask, decoded=decoded,
-                   sample_pidx=pidx, sample_loc_w=loc, ray_nsamp=nsamp, counts=counts, status=status)
+        res = dict(coarse_raycolor=col, coarse_point_opacity=opa, coarse_is_background=isbg, blend_weight=bw if want_weights else None, ray_mask=mask,
+                   decoded=decoded, sample_pidx=pidx, sample_loc_w=loc, ray_nsamp=nsamp, counts=counts, status=status)
         if want_weights:
             res.update(weight=w_out, conf_coefficient=c_out)
+        if want_depth:
+            res["coarse_depth"] = ray_depth(bw, loc, nsamp, mask, campos, camrot)      # (the query outputs are un-padded: nsamp bounds the slots read)
         return res
 
     @staticmethod
@@ -451,10 +471,12 @@ class HybridRenderer:
 
     # -- the whole path -------------------------------------------------------------------------------
     def render_rays(self, cloud, raydir, campos, camrot, bg_color, near, far, c2w_nearest, campos_nearest, intrinsic_nearest,
-                    images_nearest, frame_weight=None, want_weights=False, w2c_nearest=None, timers=None, pad=False):
+                    images_nearest, frame_weight=None, want_weights=False, w2c_nearest=None, timers=None, pad=False, want_depth=False):
         """raydir [R,3]; campos [3]; camrot [3,3]; c2w_nearest [V,4,4]; images_nearest [V,H,W,3] (or with a leading 1).
         Returns full-R outputs (fill_invalid applied): coarse_raycolor [R,3], coarse_point_opacity [R,SR],
-        coarse_is_background [R], ray_mask [R] i8, decoded [R,SR,4] + the query tensors."""
+        coarse_is_background [R], ray_mask [R] i8, decoded [R,SR,4] + the query tensors.
+        want_depth: also coarse_depth [R], the expected camera-space depth of every ray (ray_depth; 0 where ray_mask = 0) -- one more launch
+        after the composite; every other output is what the call without it returns."""
         g = _lib.require_gpu
         raydir = g(raydir, "raydir", torch.float32).reshape(-1, 3)
         campos = g(campos, "campos", torch.float32).reshape(3)
@@ -477,7 +499,7 @@ class HybridRenderer:
                 with _Stage(timers, "featmap"):
                     fm, fm_ready = self.feature_map_async(images_nearest)
             res = self._single_call(cloud, raydir, campos, camrot, bg_color, tmid, grid, np.float32(hp[0] ** 2), w2c_nearest, campos_nearest,
-                                    intrinsic_nearest, fm, frame_weight, want_weights, timers, fm_ready=fm_ready)
+                                    intrinsic_nearest, fm, frame_weight, want_weights, timers, fm_ready=fm_ready, want_depth=want_depth)
             if res is not None:
                 return res
             if fm_ready is not None:
@@ -492,7 +514,7 @@ class HybridRenderer:
         a = self.aggregate(cloud, qres, raydir, campos, camrot, w2c_nearest, intrinsic_nearest, campos_nearest, fm,
                            frame_weight=frame_weight, want_weights=want_weights, timers=timers)
         with _Stage(timers, "composite"):
-            out = self.composite(a["decoded"], qres, campos, camrot, bg_color, want_blend=want_weights)
+            out = self.composite(a["decoded"], qres, campos, camrot, bg_color, want_blend=want_weights, want_depth=want_depth)
         if "overflow" in a and int(a["overflow"].item()) != 0:
             raise HnrError("hnr_sample_plan: row buffers too small (internal sizing error)")
         out.update(ray_mask=qres["ray_mask"], decoded=a["decoded"], sample_pidx=qres["sample_pidx"],

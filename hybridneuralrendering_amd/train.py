@@ -7,7 +7,8 @@ models/aggregators/point_aggregators.py:1222-1237, straight-through conf clamp :
 (models/mvs_points_volumetric_model.py:111-131).  Gradients are produced for points_embeding / points_conf / points_dir / points_color
 and every aggregator parameter that takes part in the order-2 hybrid path (`color_branch` is constructed but unused, :542-553, and gets
 none).  Differentiable outputs: coarse_raycolor and conf_coefficient (the two the shipped loss terms read,
-dev_scripts/w_scannet_etf/scene241.sh:146-151); every other output is returned detached.
+dev_scripts/w_scannet_etf/scene241.sh:146-151) and, when asked for, coarse_depth (the compute_depth branch, :381-385, for a depth loss item,
+models/base_rendering_model.py:1209-1215); every other output is returned detached.
 
 Nothing here reads a device value: the library sizes every stage from device counters inside a workspace of `cap_samples` valid shading
 samples (default R * SR, always enough); `TrainPath.check_status` reads the overflow word when the caller wants to (a host sync).
@@ -21,7 +22,7 @@ import torch
 from . import _lib
 from ._lib import HnrError
 from . import querier as Q
-from .render import _f32, PointCloud
+from .render import _f32, PointCloud, ray_depth
 
 
 def drop_patch_rays(patch_size, patch_num, drop_ratio):
@@ -132,8 +133,10 @@ class TrainPath:
 
     # ---------------------------------------------------------------------------------------------- forward
     def forward(self, cloud, raydir, campos, camrot, bg_color, near, far, c2w_nearest, campos_nearest, intrinsic_nearest,
-                images_nearest, frame_weight=None, tmid=None, ray_drop=None, w2c_nearest=None):
-        """w2c_nearest [V,4,4]: inverse(c2w_nearest) computed by the caller (torch.inverse may synchronise the host: a captured step passes it in)."""
+                images_nearest, frame_weight=None, tmid=None, ray_drop=None, w2c_nearest=None, want_depth=False):
+        """w2c_nearest [V,4,4]: inverse(c2w_nearest) computed by the caller (torch.inverse may synchronise the host: a captured step passes it in).
+        want_depth: the outputs also hold coarse_depth [R] (render.ray_depth over the padded query outputs and the blend weights; 0 where
+        ray_mask = 0) -- one launch after the forward call; the backward takes its gradient (backward(g_depth=...))."""
         L = _lib.lib()
         r, opt = self.r, self.opt
         g, p = _lib.require_gpu, _lib.ptr
@@ -253,6 +256,8 @@ class TrainPath:
         S.keep = (lut, flags, grid)
         out = dict(coarse_raycolor=col, coarse_point_opacity=opa, coarse_is_background=isbg, blend_weight=bw, ray_mask=mask, decoded=decoded,
                    sample_pidx=pidx, sample_loc_w=loc, ray_nsamp=nsamp, counts=counts, status=status, weight=w_out, conf_coefficient=c_out)
+        if want_depth:
+            out["coarse_depth"] = ray_depth(bw, loc, None, mask, campos, camrot)
         S.outs = out
         self.last_step = (prm, nbytes)     # tools (bisect_train_forward.py): the step's parameter block and workspace size
         return out, S
@@ -277,14 +282,17 @@ class TrainPath:
             raise HnrError("render_train: %d valid shading samples exceed the workspace capacity (TrainPath.cap_samples); the extra ones were dropped" % int(st[1]))
 
     # ---------------------------------------------------------------------------------------------- backward
-    def backward(self, S, g_raycolor, g_conf_out=None):
-        """Returns (point grads dict, aggregator grads dict keyed by parameter name)."""
+    def backward(self, S, g_raycolor, g_conf_out=None, g_depth=None):
+        """Returns (point grads dict, aggregator grads dict keyed by parameter name).  g_depth [R]: gradient of the forward's coarse_depth
+        (hnr_render_train_backward_depth); None: hnr_render_train_backward."""
         L = _lib.lib()
         dev, p = S.dev, _lib.ptr
         N = int(S.cloud_t[0].shape[0])
         g_raycolor = _lib.require_gpu(g_raycolor, "grad coarse_raycolor", torch.float32).reshape(S.R, 3)
         if g_conf_out is not None:
             g_conf_out = _lib.require_gpu(g_conf_out, "grad conf_coefficient", torch.float32).reshape(S.R, S.SR, S.K)
+        if g_depth is not None:
+            g_depth = _lib.require_gpu(g_depth, "grad coarse_depth", torch.float32).reshape(S.R)
         bkey = ("bwd", N, S.no_views, id(S.wt), str(dev))
         if self.reuse_outputs and bkey in self._ocache:
             pg, ag, gw, cg, flat, payload = self._ocache[bkey]
@@ -310,16 +318,23 @@ class TrainPath:
             self.timers.setdefault("bwd", []).append(ev)
             S.out.stage_events = ev.arr
         with torch.cuda.device(dev):
-            _lib.check(L.hnr_render_train_backward(ctypes.byref(S.prm), ctypes.byref(S.cl), ctypes.byref(S.weights), ctypes.byref(S.cam),
-                                                   ctypes.byref(S.vw) if S.vw is not None else None, S.ws_ptr, S.nbytes, ctypes.byref(S.out), p(g_raycolor),
-                                                   p(g_conf_out) if g_conf_out is not None else None, ctypes.byref(cg), ctypes.byref(gw), _lib.stream()),
-                       "hnr_render_train_backward")
+            if g_depth is None:
+                _lib.check(L.hnr_render_train_backward(ctypes.byref(S.prm), ctypes.byref(S.cl), ctypes.byref(S.weights), ctypes.byref(S.cam),
+                                                       ctypes.byref(S.vw) if S.vw is not None else None, S.ws_ptr, S.nbytes, ctypes.byref(S.out), p(g_raycolor),
+                                                       p(g_conf_out) if g_conf_out is not None else None, ctypes.byref(cg), ctypes.byref(gw), _lib.stream()),
+                           "hnr_render_train_backward")
+            else:
+                _lib.check(L.hnr_render_train_backward_depth(ctypes.byref(S.prm), ctypes.byref(S.cl), ctypes.byref(S.weights), ctypes.byref(S.cam),
+                                                             ctypes.byref(S.vw) if S.vw is not None else None, S.ws_ptr, S.nbytes, ctypes.byref(S.out),
+                                                             p(g_raycolor), p(g_conf_out) if g_conf_out is not None else None, p(g_depth), ctypes.byref(cg),
+                                                             ctypes.byref(gw), _lib.stream()),
+                           "hnr_render_train_backward_depth")
         return pg, ag
 
 
 class _RenderFn(torch.autograd.Function):
-    """inputs: (path, static dict, emb, conf, dir, color, *aggregator parameters) -> (coarse_raycolor [R,3], conf_coefficient [R,SR,K],
-    then detached extras).  The static dict carries the geometry / camera / image inputs (no gradient)."""
+    """inputs: (path, static dict, emb, conf, dir, color, *aggregator parameters) -> (coarse_raycolor [R,3], conf_coefficient [R,SR,K]
+    [, coarse_depth [R] when static["want_depth"]]).  The static dict carries the geometry / camera / image inputs (no gradient)."""
 
     @staticmethod
     def forward(ctx, path, static, emb, conf, pdir, color, *params):
@@ -327,20 +342,27 @@ class _RenderFn(torch.autograd.Function):
         out, S = path.forward(cloud, static["raydir"], static["campos"], static["camrot"], static["bg_color"], static["near"],
                               static["far"], static["c2w_nearest"], static["campos_nearest"], static["intrinsic_nearest"],
                               static["images_nearest"], frame_weight=static.get("frame_weight"), tmid=static.get("tmid"),
-                              ray_drop=static.get("ray_drop"))
+                              ray_drop=static.get("ray_drop"), want_depth=static.get("want_depth", False))
         ctx.path, ctx.S = path, S
         ctx.shapes = (emb.shape, conf.shape, pdir.shape, color.shape)
         ctx.param_names = static["param_names"]
         static["_out"] = out
+        # an output the loss does not use arrives as None: the depth then takes the colour-only backward (no depth term at all), the colour and
+        # conf_coefficient get the zeros autograd would have materialised
+        ctx.set_materialize_grads(False)
         col, cc = out["coarse_raycolor"], out["conf_coefficient"]
+        if "coarse_depth" in out:
+            return col, cc, out["coarse_depth"]
         return col, cc
 
     @staticmethod
-    def backward(ctx, g_col, g_cc):
+    def backward(ctx, g_col, g_cc, g_depth=None):
         S = ctx.S
         if g_col is None:
             g_col = torch.zeros((S.R, 3), dtype=torch.float32, device=S.dev)
-        pg, ag = ctx.path.backward(S, g_col.contiguous(), None if g_cc is None else g_cc.contiguous())
+        if g_cc is None:
+            g_cc = torch.zeros((S.R, S.SR, S.K), dtype=torch.float32, device=S.dev)
+        pg, ag = ctx.path.backward(S, g_col.contiguous(), g_cc.contiguous(), None if g_depth is None else g_depth.contiguous())
         es, cs, ds, ks = ctx.shapes
         grads = [None, None, pg["points_embeding"].reshape(es), pg["points_conf"].reshape(cs), pg["points_dir"].reshape(ds),
                  pg["points_color"].reshape(ks)]
@@ -351,18 +373,20 @@ class _RenderFn(torch.autograd.Function):
 
 
 def render_train(path, aggregator, xyz, emb, conf, pdir, color, raydir, campos, camrot, bg_color, near, far, c2w_nearest,
-                 campos_nearest, intrinsic_nearest, images_nearest, frame_weight=None, tmid=None, ray_drop=None):
+                 campos_nearest, intrinsic_nearest, images_nearest, frame_weight=None, tmid=None, ray_drop=None, want_depth=False):
     """Differentiable render of one ray batch.  emb/conf/pdir/color may be nn.Parameters (reference shapes [1,N,32], [1,N,1],
     [1,N,3], [1,N,3]); aggregator parameters receive gradients through the returned tensors.  Returns the output dict of
-    TrainPath.forward with `coarse_raycolor` and `conf_coefficient` attached to the autograd graph."""
+    TrainPath.forward with `coarse_raycolor` and `conf_coefficient` (and with want_depth `coarse_depth` [R]) attached to the autograd graph."""
     names = [n for n, _ in aggregator.named_parameters()]
     params = [q for _, q in aggregator.named_parameters()]
     static = dict(xyz=xyz, raydir=raydir, campos=campos, camrot=camrot, bg_color=bg_color, near=near, far=far,
                   c2w_nearest=c2w_nearest, campos_nearest=campos_nearest, intrinsic_nearest=intrinsic_nearest,
-                  images_nearest=images_nearest, frame_weight=frame_weight, tmid=tmid, ray_drop=ray_drop, param_names=names)
-    col, cc = _RenderFn.apply(path, static, emb, conf, pdir, color, *params)
+                  images_nearest=images_nearest, frame_weight=frame_weight, tmid=tmid, ray_drop=ray_drop, param_names=names, want_depth=bool(want_depth))
+    res = _RenderFn.apply(path, static, emb, conf, pdir, color, *params)
     out = dict(static.pop("_out"))
-    out["coarse_raycolor"], out["conf_coefficient"] = col, cc
+    out["coarse_raycolor"], out["conf_coefficient"] = res[0], res[1]
+    if want_depth:
+        out["coarse_depth"] = res[2]
     return out
 
 

@@ -21,8 +21,8 @@
  * STABILITY.  Two tiers:
  *   STABLE  -- what a reference-side binding needs and what later versions keep source- and binary-compatible: hnr_version,
  *              hnr_last_error, hnr_points_bounds, hnr_grid_* (build / destroy / stats / bytes), hnr_march_query, hnr_ray_compact*, hnr_point_records,
- *              hnr_image_features*, hnr_render_forward* (+ workspace sizing), hnr_render_train_forward / _backward (+ sizing), hnr_shipped_loss*,
- *              hnr_composite, hnr_ray_march, hnr_voxel_downsample*, hnr_probe_select, hnr_blur_*.
+ *              hnr_image_features*, hnr_render_forward* (+ workspace sizing), hnr_render_train_forward / _backward / _backward_depth (+ sizing),
+ *              hnr_shipped_loss*, hnr_composite, hnr_ray_depth, hnr_ray_march, hnr_voxel_downsample*, hnr_probe_select, hnr_blur_*.
  *   STAGE   -- everything else (hnr_chain_*, hnr_mlp3_*, hnr_merge*, hnr_mixup_stage, hnr_proj_*, hnr_h2*, hnr_linear_*, hnr_gather_*, hnr_ksum*,
  *              hnr_segment_*, hnr_absmax, hnr_div_probe, ...): the individual stages the two single-call entries are built from.  They are exported so
  *              that tests/ can compare every stage with the oracle and so that tools/ can time them alone; their signatures, workspace layouts and
@@ -432,6 +432,15 @@ int hnr_composite(const float *d_decoded, const float *d_sample_loc_w, const int
                   int raydist_mode_unit, float *d_raycolor, float *d_opacity, float *d_is_background, float *d_blend_weight,
                   void *stream);
 
+/* Expected depth of every ray: the compute_depth branch of NeuralPointsRayMarching.forward (models/neural_points_volumetric_model.py:381-385),
+ *   d_depth[r] = sum_s w_s z_s / (sum_s w_s + 1e-6),
+ * w = d_blend_weight [R,SR] as hnr_composite / hnr_render_forward / hnr_render_train_forward write it (opacity x transmittance before the sample,
+ * :382-383), z = the sample's camera-space depth (w2pers z of d_sample_loc_w [R,SR,3] with the composite's rounding: the quantity ray_dist is
+ * built from, :331; the reference's `ray_ts`, which it never defines).  d_ray_nsamp: NULL for padded query outputs, else slots >= d_ray_nsamp[r]
+ * are not read.  d_depth = 0 where d_ray_mask = 0.  The sums run in a fixed order: identical bits run to run.  d_campos [3], d_camrot [3,3] c2w. */
+int hnr_ray_depth(const float *d_blend_weight, const float *d_sample_loc_w, const int32_t *d_ray_nsamp, const int8_t *d_ray_mask,
+                  const float *d_campos, const float *d_camrot, int R, int SR, float *d_depth, void *stream);
+
 /* Hole-probing outputs of opt.prob == 1 (models/neural_points_volumetric_model.py:392-416; consumed by the point-growing step
  * of run/train_ft.py:450-569): per ray the sample of maximum opacity -> d_max_opacity [R], its position d_max_loc_w [R,3],
  * the distance to the nearest of its K listed points d_far_dist [R] (empty slots read point 0, like the reference's clamped
@@ -461,6 +470,12 @@ int hnr_composite_bwd(const float *d_decoded, const float *d_sample_loc_w, const
                       const int32_t *d_ray_nsamp, const float *d_campos, const float *d_camrot, const float *d_bg_color,
                       int R, int SR, int K, float vsize_z, int raydist_mode_unit, const float *d_g_raycolor,
                       float *d_g_decoded, void *stream);
+/* The same with the gradient of the expected depth (hnr_ray_depth; :381-385) added: d_g_depth [R] (may be NULL: then the result is
+ * hnr_composite_bwd's, bit for bit).  dD/dw_s = (z_s - D) / (sum_s w_s + 1e-6), chained through w_s = opacity_s x transmittance_s. */
+int hnr_composite_bwd_depth(const float *d_decoded, const float *d_sample_loc_w, const int32_t *d_sample_pidx, const int8_t *d_ray_mask,
+                            const int32_t *d_ray_nsamp, const float *d_campos, const float *d_camrot, const float *d_bg_color,
+                            int R, int SR, int K, float vsize_z, int raydist_mode_unit, const float *d_g_raycolor,
+                            const float *d_g_depth, float *d_g_decoded, void *stream);
 
 /* color_final_block + sigmoid*1.002-0.001 + residual (point_aggregators.py:1294-1295, :1334, :478-482):
  * d_g_decoded -> d_gY [S,45] (mix-up output), d_gCF [S,128] (OVERWRITTEN), d_g_sigma [S]; weights: atomics. */
@@ -680,6 +695,13 @@ int hnr_render_train_backward(const hnr_train_params *p, const hnr_train_cloud *
                               const hnr_train_views *views, void *d_workspace, int64_t workspace_bytes, const hnr_render_outputs *forward_out,
                               const float *d_g_raycolor, const float *d_g_conf_coefficient /*may be NULL*/, const hnr_train_cloud_grads *cloud_grads,
                               const hnr_train_weights *weight_grads, void *stream);
+/* ... with the gradient of the expected depth, d_g_depth [R] (may be NULL: hnr_render_train_backward), as a third upstream gradient: the depth a
+ * caller forms with hnr_ray_depth from forward_out->d_blend_weight / d_sample_loc_w (the compute_depth branch, neural_points_volumetric_model.py:381-385,
+ * supervised by compute_losses' depth term, models/base_rendering_model.py:1209-1215). */
+int hnr_render_train_backward_depth(const hnr_train_params *p, const hnr_train_cloud *cloud, const hnr_train_weights *weights, const hnr_render_camera *camera,
+                                    const hnr_train_views *views, void *d_workspace, int64_t workspace_bytes, const hnr_render_outputs *forward_out,
+                                    const float *d_g_raycolor, const float *d_g_conf_coefficient /*may be NULL*/, const float *d_g_depth /*[R] or NULL*/,
+                                    const hnr_train_cloud_grads *cloud_grads, const hnr_train_weights *weight_grads, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * "Next" row: hole probing, run/train_ft.py:527-549 (`probe_hole`) + :571-581 (`bloat_inds`).  Per probed frame: a cast
