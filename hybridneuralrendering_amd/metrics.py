@@ -1,0 +1,175 @@
+"""Evaluation of rendered frames on the device: PSNR / SSIM / RMSE of the 8-bit images and the two test losses.
+
+The second half of the reference's test pass (the first is driver.render_image).  After its chunk loop the reference computes the two
+test losses per frame (run/test_ft.py:233-243), writes `coarse_raycolor` and `gt_image` as 8-bit PNGs (utils/visualizer.py:19-26) and
+reads them back for PSNR / SSIM / RMSE (run/evaluate.py:34-97, called at run/test_ft.py:260): about ten host round trips, a PNG
+encode and a PNG decode per frame, and scikit-image + OpenCV on the host.  Here a frame is one hnr_frame_metrics call behind the
+composite (csrc/metrics.hip) that leaves one fp64 row in a device table; the table is read once per test set (`summary()`).
+
+SSIM's `data_range`: the reference hands float images to scikit-image without a data_range, and scikit-image then uses the dtype range
+of floats (-1..1, L = 2), so the SSIM the reference publishes is the L = 2 value; that is the default here.  L = 1 is the textbook
+value for images in [0, 1].  LPIPS is not computed (it needs network weights this package does not ship).
+"""
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import HnrError
+
+# the row hnr_frame_metrics writes (include/hnr.h: HNR_FM_*)
+FM = dict(SQERR8=0, N8=1, SSIM=2, MSE_FULL=3, MSE_MASKED=4, N_MASKED=5)
+NCOLS = 6
+MAX_WIN = 31
+
+
+def _sq(t, nd):
+    return t.reshape(t.shape[-nd:])
+
+
+def scatter_gt(frame, device):
+    """gt_full [h,w,3]: the item's gt_image [R,3] placed by pixel_idx (x, y), zero where no ray was cast -- run/test_ft.py:203-204 -- on the device."""
+    h, w = int(frame["h"]), int(frame["w"])
+    gt = _lib.require_gpu(_sq(frame["gt_image"], 2).to(device), "gt_image", torch.float32)
+    pix = _sq(frame["pixel_idx"], 2)
+    if pix.shape[0] != gt.shape[0]:
+        raise HnrError("frame_metrics: pixel_idx and gt_image disagree on the number of rays")
+    full = torch.zeros((h, w, 3), dtype=torch.float32, device=device)
+    full[pix[:, 1].to(device, torch.long), pix[:, 0].to(device, torch.long)] = gt
+    return full, gt
+
+
+def frame_metrics(render_out, frame, win=11, data_range=2.0, out=None, row=0, images8=None):
+    """One frame's row of metrics, on the device, without a host synchronisation.
+
+    render_out: what driver.render_image returns (image [h,w,3], coarse_raycolor [R,3], ray_mask [R]); frame: the dataset item it was rendered
+    from, with gt_image [R,3] (batch dim optional).  out / row: a [capacity, NCOLS] float64 device table and the row to fill (default: a
+    fresh [1, NCOLS] table).  images8: optional pair of [h,w,3] uint8 device tensors that receive the quantised image and ground truth
+    (the bytes of the reference's PNGs).  Returns the table; columns are FM[...]; derive() turns rows into the reported numbers."""
+    L = _lib.lib()
+    img = _lib.require_gpu(render_out["image"], "image", torch.float32)
+    dev = img.device
+    if img.dim() != 3 or img.shape[2] != 3:
+        raise HnrError("frame_metrics: image must be [h, w, 3]")
+    h, w = int(img.shape[0]), int(img.shape[1])
+    if (h, w) != (int(frame["h"]), int(frame["w"])):
+        raise HnrError("frame_metrics: the image is %dx%d, the frame says %dx%d" % (h, w, int(frame["h"]), int(frame["w"])))
+    gt_full, gt = scatter_gt(frame, dev)
+    col = _lib.require_gpu(render_out["coarse_raycolor"], "coarse_raycolor", torch.float32).reshape(-1, 3)
+    mask = _lib.require_gpu(render_out["ray_mask"], "ray_mask").reshape(-1)
+    if mask.dtype != torch.int8:
+        mask = mask.to(torch.int8)
+    R = int(col.shape[0])
+    if gt.shape[0] != R or mask.shape[0] != R:
+        raise HnrError("frame_metrics: coarse_raycolor, gt_image and ray_mask disagree on the number of rays")
+    if out is None:
+        out = torch.zeros((1, NCOLS), dtype=torch.float64, device=dev)
+    if not (out.is_cuda and out.dtype == torch.float64 and out.dim() == 2 and out.shape[1] == NCOLS and out.is_contiguous()):
+        raise HnrError("frame_metrics: out must be a contiguous [capacity, %d] float64 table on the GPU" % NCOLS)
+    if not 0 <= row < out.shape[0]:
+        raise HnrError("frame_metrics: row %d outside the table (%d rows)" % (row, out.shape[0]))
+    a8 = b8 = None
+    if images8 is not None:
+        a8, b8 = images8
+        for t in (a8, b8):
+            if not (t.is_cuda and t.dtype == torch.uint8 and tuple(t.shape) == (h, w, 3) and t.is_contiguous()):
+                raise HnrError("frame_metrics: images8 must be two contiguous [h, w, 3] uint8 tensors on the GPU")
+    nbytes = int(L.hnr_frame_metrics_scratch_bytes(h, w, int(win)))
+    if nbytes < 0:
+        _lib.check(nbytes, "hnr_frame_metrics_scratch_bytes")
+    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    p = _lib.ptr
+    with torch.cuda.device(dev):
+        _lib.check(L.hnr_frame_metrics(p(img), p(gt_full), h, w, p(col) if R else None, p(gt) if R else None, p(mask) if R else None, R, int(win),
+                                       float(data_range), p(out[row]), p(a8), p(b8), p(scratch), _lib.stream()), "hnr_frame_metrics")
+    return out
+
+
+def derive(rows):
+    """Host side: [n, NCOLS] float64 rows -> the per-frame numbers the reference reports.  psnr / rmse / ssim are those of run/evaluate.py on
+    the 8-bit images (psnr = +inf for identical images, as compare_psnr gives); psnr_full / psnr_masked are mse2psnr of the two test losses."""
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, NCOLS)
+    S, n = rows[:, FM["SQERR8"]], rows[:, FM["N8"]]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mse8 = S / (65025.0 * n)
+        res = dict(psnr=10.0 * np.log10(1.0 / mse8), ssim=rows[:, FM["SSIM"]].copy(), rmse=np.sqrt(mse8),
+                   mse_full=rows[:, FM["MSE_FULL"]].copy(), psnr_full=-10.0 * np.log10(rows[:, FM["MSE_FULL"]]),
+                   mse_masked=rows[:, FM["MSE_MASKED"]].copy(), psnr_masked=-10.0 * np.log10(rows[:, FM["MSE_MASKED"]]),
+                   n_masked=rows[:, FM["N_MASKED"]].copy(), sqerr8=S.copy(), n8=n.copy())
+    return res
+
+
+class TestSetEvaluator:
+    """A [capacity, NCOLS] device table of per-frame rows: add() per frame (no host synchronisation), summary() = the one host read.
+
+    write(out_dir) leaves psnr.txt / ssim.txt / rmse.txt (np.savetxt) and scores.txt ("key: %.6f" lines) exactly as report_metrics does
+    (run/evaluate.py:89-97); with save_images=True also step-%04d-coarse_raycolor.png / step-%04d-gt_image.png from the kernel's own
+    uint8 images, so the reference's run/evaluate.py can be pointed at the same folder."""
+    __test__ = False            # (not a pytest class, whatever its name starts with)
+
+    def __init__(self, capacity, win=11, data_range=2.0, device="cuda:0", save_images=False):
+        if capacity <= 0:
+            raise HnrError("TestSetEvaluator: capacity must be positive")
+        self.capacity, self.win, self.data_range, self.save_images = int(capacity), int(win), float(data_range), bool(save_images)
+        self.table = torch.zeros((self.capacity, NCOLS), dtype=torch.float64, device=device)
+        self.n = 0
+        self.img8 = self.gt8 = None          # [capacity, h, w, 3] uint8, allocated by the first add()
+        self._host = None
+
+    @classmethod
+    def from_rows(cls, rows, img8=None, gt8=None, win=11, data_range=2.0):
+        """An evaluator over rows computed elsewhere (another rank's table, an earlier run): summary() / write() only."""
+        rows = torch.as_tensor(np.asarray(rows, dtype=np.float64).reshape(-1, NCOLS))
+        ev = cls(max(int(rows.shape[0]), 1), win=win, data_range=data_range, device=rows.device, save_images=img8 is not None)
+        ev.table[:rows.shape[0]] = rows
+        ev.n = int(rows.shape[0])
+        if img8 is not None:
+            ev.img8, ev.gt8 = torch.as_tensor(img8), torch.as_tensor(gt8)
+        return ev
+
+    def add(self, render_out, frame):
+        if self.n >= self.capacity:
+            raise HnrError("TestSetEvaluator: the table is full (%d frames)" % self.capacity)
+        pair = None
+        if self.save_images:
+            h, w = int(frame["h"]), int(frame["w"])
+            if self.img8 is None:
+                dev = render_out["image"].device
+                self.img8 = torch.zeros((self.capacity, h, w, 3), dtype=torch.uint8, device=dev)
+                self.gt8 = torch.zeros((self.capacity, h, w, 3), dtype=torch.uint8, device=dev)
+            if tuple(self.img8.shape[1:3]) != (h, w):
+                raise HnrError("TestSetEvaluator: save_images needs frames of one size")
+            pair = (self.img8[self.n], self.gt8[self.n])
+        frame_metrics(render_out, frame, win=self.win, data_range=self.data_range, out=self.table, row=self.n, images8=pair)
+        self.n += 1
+        self._host = None
+        return self.n - 1
+
+    def summary(self):
+        """Reads the table (the only host read) -> dict of per-frame float64 arrays (derive()) + "mean": their means over the frames."""
+        if self._host is None:
+            self._host = self.table[:self.n].cpu().numpy()
+        res = derive(self._host)
+        with np.errstate(invalid="ignore"):
+            res["mean"] = {k: (float(np.mean(v)) if len(v) else float("nan")) for k, v in res.items()}
+        return res
+
+    def write(self, out_dir, ids=None):
+        """The files of report_metrics (+ the PNGs when save_images); ids: the step numbers of the frames (default 0, 1, ...).  Returns summary()."""
+        res = self.summary()
+        os.makedirs(out_dir, exist_ok=True)
+        text = ""
+        for key in ("psnr", "ssim", "rmse"):
+            np.savetxt(os.path.join(out_dir, key + ".txt"), res[key].reshape(-1))
+            text += key + ": %.6f\n" % np.mean(res[key])
+        with open(os.path.join(out_dir, "scores.txt"), "w") as f:
+            f.write(text)
+        if self.save_images and self.img8 is not None:
+            from PIL import Image
+            ids = list(range(self.n)) if ids is None else list(ids)
+            a, b = self.img8[:self.n].cpu().numpy(), self.gt8[:self.n].cpu().numpy()
+            for k, i in enumerate(ids):
+                Image.fromarray(a[k]).save(os.path.join(out_dir, "step-%04d-coarse_raycolor.png" % i))
+                Image.fromarray(b[k]).save(os.path.join(out_dir, "step-%04d-gt_image.png" % i))
+        return res

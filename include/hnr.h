@@ -22,7 +22,8 @@
  *   STABLE  -- what a reference-side binding needs and what later versions keep source- and binary-compatible: hnr_version,
  *              hnr_last_error, hnr_points_bounds, hnr_grid_* (build / destroy / stats / bytes), hnr_march_query, hnr_ray_compact*, hnr_point_records,
  *              hnr_image_features*, hnr_render_forward* (+ workspace sizing), hnr_render_train_forward / _backward / _backward_depth (+ sizing),
- *              hnr_shipped_loss*, hnr_composite, hnr_ray_depth, hnr_ray_march, hnr_voxel_downsample*, hnr_probe_select, hnr_blur_*.
+ *              hnr_shipped_loss*, hnr_composite, hnr_ray_depth, hnr_ray_march, hnr_voxel_downsample*, hnr_probe_select, hnr_blur_*,
+ *              hnr_frame_metrics* (and the HNR_FM_* row layout).
  *   STAGE   -- everything else (hnr_chain_*, hnr_mlp3_*, hnr_merge*, hnr_mixup_stage, hnr_proj_*, hnr_h2*, hnr_linear_*, hnr_gather_*, hnr_ksum*,
  *              hnr_segment_*, hnr_absmax, hnr_div_probe, ...): the individual stages the two single-call entries are built from.  They are exported so
  *              that tests/ can compare every stage with the oracle and so that tools/ can time them alone; their signatures, workspace layouts and
@@ -763,6 +764,40 @@ int hnr_shipped_loss_rows(const float *d_color, const float *d_gt, const int8_t 
 int hnr_shipped_loss_rows_fw(const float *d_color, const float *d_gt, const int8_t *d_ray_mask, int R, const float *d_conf, int conf_per_ray,
                              float zero_epsilon, float w_color, float w_zero_one, const float *d_frame_weight, float *d_out4, float *d_g_color,
                              float *d_g_conf, void *d_scratch, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Evaluation of a rendered frame: what the reference's test pass reports per frame, as one fp64 row on the device.
+ * Replaces the two test losses of run/test_ft.py:233-243, the 8-bit quantisation of utils/visualizer.py:23-24 (the bytes of the PNGs it
+ * writes) and run/evaluate.py:34-97 on those bytes (compare_psnr, structural_similarity, sqrt(mean_squared_error)).
+ *   d_image, d_gt_full [h,w,3]: the rendered image and the ground truth scattered the same way (zero where no ray was cast: both count);
+ *   d_raycolor, d_gt_rays [R,3], d_ray_mask [R]: the cast rays, for the masked loss (R = 0: all three may be NULL).
+ *   A = q(image), B = q(gt_full), q(x) = (uint8) trunc(min(max(x, 0), 1) * 255.0f) in fp32 = (np.clip(x, 0, 1) * 255).astype(np.uint8);
+ *   d_img8 / d_gt8 (optional, both or neither) [h,w,3] uint8 receive A and B.
+ * d_row[HNR_FM_NCOLS] (fp64; the integers are exact):
+ *   HNR_FM_SQERR8     S = sum (A - B)^2 over the n = 3hw values      -> mse8 = S / (65025 n), psnr = 10 log10(1 / mse8), rmse = sqrt(mse8)
+ *   HNR_FM_N8         n
+ *   HNR_FM_SSIM       structural_similarity(B / 255, A / 255, win_size = win, multichannel): per channel the mean over the (h - win + 1)(w - win + 1)
+ *                     windows that lie inside the image of (2 ux uy + C1)(2 vxy + C2) / ((ux^2 + uy^2 + C1)(vx + vy + C2)) with the window means
+ *                     ux, uy, uxx, uyy, uxy of x = A / 255, y = B / 255, sample covariances vx = NP / (NP - 1) (uxx - ux^2) ..., NP = win^2,
+ *                     C1 = (0.01 L)^2, C2 = (0.03 L)^2, L = data_range; then the mean of the three channels.  Window sums exact (integers), the rest
+ *                     fp64.  data_range = 2: the value the reference publishes (it hands float images to scikit-image without a data_range, and
+ *                     scikit-image then takes the dtype range of floats, -1..1); data_range = 1: the textbook value for images in [0, 1].
+ *   HNR_FM_MSE_FULL   mean over 3hw of (image - gt_full)^2, squares in fp32, sum in fp64      (test_ft.py:233-236; psnr = -10 log10)
+ *   HNR_FM_MSE_MASKED mean over the rays with ray_mask > 0 of (raycolor - gt_rays)^2, NaN when there is none     (test_ft.py:238-243)
+ *   HNR_FM_N_MASKED   number of rays with ray_mask > 0
+ * win: odd, 3 <= win <= min(h, w, 31).  Deterministic (no atomics): the same inputs give the same bits.  Stream-ordered, nothing is read back.
+ * d_scratch: hnr_frame_metrics_scratch_bytes(h, w, win) bytes (negative: bad shape), private to the call until it has run. */
+#define HNR_FM_SQERR8      0
+#define HNR_FM_N8          1
+#define HNR_FM_SSIM        2
+#define HNR_FM_MSE_FULL    3
+#define HNR_FM_MSE_MASKED  4
+#define HNR_FM_N_MASKED    5
+#define HNR_FM_NCOLS       6
+int64_t hnr_frame_metrics_scratch_bytes(int h, int w, int win);
+int hnr_frame_metrics(const float *d_image, const float *d_gt_full, int h, int w, const float *d_raycolor, const float *d_gt_rays,
+                      const int8_t *d_ray_mask, int R, int win, float data_range, double *d_row, uint8_t *d_img8, uint8_t *d_gt8,
+                      void *d_scratch, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Multi-GPU training (BASELINE config C5): sparse exchange of the point-buffer gradients of a patch-sharded step.  No reference counterpart
