@@ -164,6 +164,13 @@ SIGNATURES = {
     "hnr_frame_metrics": (_I, [_P, _P, _I, _I, _P, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P]),
     "hnr_voxel_downsample_scratch_bytes": (ctypes.c_int64, [ctypes.c_int64]),
     "hnr_voxel_downsample": (_I, [_P, _I, ctypes.POINTER(_F), _F, _P, _P, _P, _P, _P, _P, ctypes.c_int64, _P]),
+    # initial cloud from depth frames (csrc/cloud_init.hip)
+    "hnr_depth_fuse_scratch_bytes": (ctypes.c_int64, [_I, _I]),
+    "hnr_depth_fuse_frame": (_I, [_P, _I, _I, _I, ctypes.POINTER(_F), ctypes.POINTER(_F), _F, _F, _F, _I, _P, ctypes.c_int64, _P, _P, _P, ctypes.c_int64, _P]),
+    "hnr_range_crop_scratch_bytes": (ctypes.c_int64, [ctypes.c_int64]),
+    "hnr_range_crop": (_I, [_P, _P, ctypes.c_int64, ctypes.POINTER(_F), _P, _P, _P, ctypes.c_int64, _P]),
+    "hnr_nearest_view": (_I, [_P, ctypes.c_int64, _P, _P, _I, _P, _P]),
+    "hnr_point_view_attrs": (_I, [_P, ctypes.c_int64] + [ctypes.POINTER(_F)] * 4 + [_I, _I, _P, _I, _I, _I, _P, _P, _P, _P]),
     "hnr_blur_gray_patches": (_I, [_P, _P, _I, _I, _P, _P]),
     "hnr_blur_gray_patches_bwd": (_I, [_P, _I, _I, _P, _P]),
     "hnr_blur_apply": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),

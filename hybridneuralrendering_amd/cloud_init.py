@@ -1,0 +1,276 @@
+"""The initial neural point cloud from posed depth frames, on the device (csrc/cloud_init.hip).
+
+Mirror of the reference's `load_points=2` start of a scene (run/train_ft.py:687-770): data/scannet_ft_dataset.py:616-647
+`load_init_depth_points` (back-projection + per-frame `construct_vox_points_xyz`), the range crop, `construct_vox_points_closest`, `nearest_view`
+(train_ft.py:48-57), the regrouping by view and `MvsPointsModel.query_embedding` (homo_warp_nongrid + extract_from_2d_grid + the `dir` branch).
+The reference's FeatureNet and premlp stay the user's torch modules: they produce `feature_maps` and consume `features`.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import HnrError
+
+OVERFLOW = 1          # HNR_CLOUD_OVERFLOW
+
+
+def _host_f32(a, shape, name):
+    if isinstance(a, torch.Tensor):
+        a = a.detach().cpu().numpy()
+    a = np.ascontiguousarray(np.asarray(a, dtype=np.float32))
+    if a.size != int(np.prod(shape)):
+        raise HnrError("%s must hold %s values, got shape %s" % (name, "x".join(str(s) for s in shape), a.shape))
+    return a.reshape(shape)
+
+
+def _cf(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+
+
+class DepthFusion:
+    """Fuses depth frames into one cloud [n,3] without a host read per frame.
+
+    `intrinsic` is the fp32 depth intrinsic [3,3] (or the [4,4] file of a ScanNet export); its inverse is taken on the CPU in fp32, as the
+    reference does (scannet_ft_dataset.py:624).  `.add(depth, c2w)` queues one frame: depth [H,W] uint16 (raw, divided by `depth_div`) or float32
+    (metres) -- a host array is uploaded, a GPU tensor is used in place.  torch has no uint16 arithmetic, so raw depth travels as torch.int16 with
+    the uint16 bit pattern: EVERY int16 tensor is read as uint16 (a negative value v means 65536 + v); genuinely signed data must be converted to
+    float32 metres by the caller.  `.points()` does the one host read.
+
+    Deliberately different from the reference: a frame without a valid depth pixel appends nothing (the reference raises: torch.min of an empty
+    tensor at mvs_utils.py:507)."""
+
+    def __init__(self, capacity, device, intrinsic, frame_vox_res=100, depth_div=1000., depth_min=0.3, depth_max=8.0):
+        if int(capacity) < 1:
+            raise HnrError("DepthFusion: capacity must be at least 1")
+        self.L = _lib.lib()
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise HnrError("DepthFusion: device must be a GPU (the HIP path has no CPU fallback)")
+        K = _host_f32(np.asarray(intrinsic, dtype=np.float32)[:3, :3], (3, 3), "intrinsic")
+        self.Ki = np.ascontiguousarray(torch.inverse(torch.from_numpy(K)).numpy())
+        self.capacity, self.frame_vox_res = int(capacity), int(frame_vox_res)
+        self.depth_div, self.depth_min, self.depth_max = float(depth_div), float(depth_min), float(depth_max)
+        self.cloud = torch.empty((self.capacity, 3), dtype=torch.float32, device=self.device)
+        self.count = torch.zeros((1,), dtype=torch.int64, device=self.device)
+        self.status = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        self._scratch, self._shape = None, None
+        self.frames = 0
+
+    def add(self, depth, c2w):
+        if not isinstance(depth, torch.Tensor):
+            d = np.asarray(depth)
+            if d.dtype == np.uint16:                       # torch has no uint16 arithmetic: the bytes travel as int16, the kernel reads uint16
+                depth = torch.from_numpy(np.ascontiguousarray(d).view(np.int16))
+            else:
+                depth = torch.from_numpy(np.ascontiguousarray(d, dtype=np.float32))
+        if depth.dim() != 2:
+            raise HnrError("DepthFusion.add: depth must be [H,W]")
+        if depth.dtype in (torch.int16, getattr(torch, "uint16", torch.int16)):
+            u16 = 1
+        elif depth.dtype == torch.float32:
+            u16 = 0
+        else:
+            raise HnrError("DepthFusion.add: depth must be uint16 (raw) or float32 (metres), got %s" % depth.dtype)
+        depth = depth.to(self.device).contiguous()
+        H, W = int(depth.shape[0]), int(depth.shape[1])
+        if self._shape != (H, W):
+            nbytes = int(self.L.hnr_depth_fuse_scratch_bytes(H, W))
+            if nbytes < 0:
+                raise HnrError("DepthFusion.add: unsupported frame size %dx%d" % (H, W))
+            self._scratch, self._shape = torch.empty((nbytes,), dtype=torch.uint8, device=self.device), (H, W)
+        M = _host_f32(c2w, (4, 4), "c2w")
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.hnr_depth_fuse_frame(_lib.ptr(depth), u16, H, W, _cf(self.Ki), _cf(M), self.depth_div, self.depth_min, self.depth_max,
+                                                   self.frame_vox_res, _lib.ptr(self.cloud), self.capacity, _lib.ptr(self.count), _lib.ptr(self.status),
+                                                   _lib.ptr(self._scratch), int(self._scratch.numel()), _lib.stream()), "hnr_depth_fuse_frame")
+        self.frames += 1
+        return self
+
+    def points(self):
+        n, st = int(self.count.item()), int(self.status.item())
+        if (st & OVERFLOW) or n > self.capacity:
+            raise HnrError("DepthFusion: the fused cloud needs capacity %d, the buffer holds %d" % (n, self.capacity))
+        return self.cloud[:n]
+
+
+def range_crop(xyz, ranges, count=None):
+    """xyz [n,3] -> (buffer [n,3], device count [1] int64): the points with ranges[:3] <= p <= ranges[3:], in order (train_ft.py:713-716).
+    `count` (device int64 [1]) limits the input to xyz[:count] without a host read.  ranges[0] <= -99 keeps everything."""
+    L = _lib.lib()
+    xyz = _lib.require_gpu(xyz, "xyz", torch.float32)
+    n, dev = int(xyz.shape[0]), xyz.device
+    out = torch.empty_like(xyz)
+    n_out = torch.zeros((1,), dtype=torch.int64, device=dev)
+    if n == 0:
+        return out, n_out
+    if count is None:
+        count = torch.full((1,), n, dtype=torch.int64, device=dev)
+    r = _host_f32(ranges, (6,), "ranges")
+    nbytes = int(L.hnr_range_crop_scratch_bytes(n))
+    if nbytes < 0:
+        raise HnrError("range_crop: too many points (%d)" % n)
+    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.hnr_range_crop(_lib.ptr(xyz), _lib.ptr(count), n, _cf(r), _lib.ptr(out), _lib.ptr(n_out), _lib.ptr(scratch), nbytes, _lib.stream()),
+                   "hnr_range_crop")
+    return out, n_out
+
+
+def nearest_view_ids(campos, raydir, xyz):
+    """int32 [N]: the camera of every point (hnr_nearest_view)."""
+    L = _lib.lib()
+    xyz = _lib.require_gpu(xyz, "xyz", torch.float32).reshape(-1, 3)
+    campos = _lib.require_gpu(campos, "campos", torch.float32).reshape(-1, 3)
+    raydir = _lib.require_gpu(raydir, "raydir", torch.float32).reshape(-1, 3)
+    if campos.shape != raydir.shape or campos.shape[0] == 0:
+        raise HnrError("nearest_view: campos and raydir must both be [M,3], M > 0")
+    out = torch.empty((xyz.shape[0],), dtype=torch.int32, device=xyz.device)
+    if xyz.shape[0] > 0:
+        with torch.cuda.device(xyz.device):
+            _lib.check(L.hnr_nearest_view(_lib.ptr(xyz), int(xyz.shape[0]), _lib.ptr(campos), _lib.ptr(raydir), int(campos.shape[0]), _lib.ptr(out),
+                                          _lib.stream()), "hnr_nearest_view")
+    return out
+
+
+def nearest_view(campos, raydir, xyz, id_list=None):
+    """The reference's signature (train_ft.py:48): [N,1] int64 camera index per point; `id_list` is unused there too."""
+    return nearest_view_ids(campos, raydir, xyz).long().view(-1, 1)
+
+
+def cam_pos_cam(c2w, w2c):
+    """(c2w[:,3] @ w2c.T)[:3] in fp32 on the CPU, as mvs_points_model.py:242-244 forms it: nearly, not exactly, zero."""
+    c2w, w2c = torch.from_numpy(_host_f32(c2w, (4, 4), "c2w")), torch.from_numpy(_host_f32(w2c, (4, 4), "w2c"))
+    return np.ascontiguousarray((c2w[:, 3][None] @ w2c.t())[0, :3].numpy())
+
+
+def point_view_attrs(xyz, w2c, c2w, cpc, intrinsic, H, W, feat=None, want_dir=True, want_mask=True):
+    """hnr_point_view_attrs: (features [n,C] or None, dir [n,3] or None, mask [n] uint8 or None) of world points seen from one view."""
+    L = _lib.lib()
+    xyz = _lib.require_gpu(xyz, "xyz", torch.float32).reshape(-1, 3)
+    n, dev = int(xyz.shape[0]), xyz.device
+    C = Hl = Wl = 0
+    out_f = None
+    if feat is not None:
+        feat = _lib.require_gpu(feat, "feature map", torch.float32)
+        if feat.dim() != 3:
+            raise HnrError("a feature map must be [C,Hl,Wl]")
+        C, Hl, Wl = (int(s) for s in feat.shape)
+        out_f = torch.empty((n, C), dtype=torch.float32, device=dev)
+    out_d = torch.empty((n, 3), dtype=torch.float32, device=dev) if want_dir else None
+    out_m = torch.empty((n,), dtype=torch.uint8, device=dev) if want_mask else None
+    if n > 0:
+        a = [_host_f32(w2c, (4, 4), "w2c"), _host_f32(c2w, (4, 4), "c2w"), _host_f32(cpc, (3,), "cam_pos_cam"), _host_f32(intrinsic, (3, 3), "intrinsic")]
+        with torch.cuda.device(dev):
+            _lib.check(L.hnr_point_view_attrs(_lib.ptr(xyz), n, _cf(a[0]), _cf(a[1]), _cf(a[2]), _cf(a[3]), int(H), int(W), _lib.ptr(feat), C, Hl, Wl,
+                                              _lib.ptr(out_f), _lib.ptr(out_d), _lib.ptr(out_m), _lib.stream()), "hnr_point_view_attrs")
+    return out_f, out_d, out_m
+
+
+def query_point_attributes(xyz, image_chw, c2w, w2c, intrinsic, feature_maps=None, default_conf=-1):
+    """World points [n,3] seen from one posed frame -> (features [1,n,sum C] or None, color [1,n,3], dir [1,n,3], conf [1,n,1]): what
+    `query_embedding` returns at train_ft.py:760 before premlp.  image_chw [3,H,W] (or [1,3,H,W]); feature_maps: list of [C,Hl,Wl]."""
+    img = _lib.require_gpu(image_chw, "image_chw", torch.float32)
+    img = img.reshape(img.shape[-3:]).contiguous()
+    if img.shape[0] != 3:
+        raise HnrError("image_chw must be [3,H,W]")
+    H, W = int(img.shape[1]), int(img.shape[2])
+    w2c = torch.inverse(torch.from_numpy(_host_f32(c2w, (4, 4), "c2w"))).numpy() if w2c is None else w2c
+    cpc = cam_pos_cam(c2w, w2c)
+    K = _host_f32(intrinsic, (3, 3), "intrinsic")
+    color, pdir, _ = point_view_attrs(xyz, w2c, c2w, cpc, K, H, W, feat=img, want_mask=False)
+    feats = None
+    if feature_maps:
+        feats = torch.cat([point_view_attrs(xyz, w2c, c2w, cpc, K, H, W, feat=f.reshape(f.shape[-3:]), want_dir=False, want_mask=False)[0]
+                           for f in feature_maps], dim=-1)[None]
+    return feats, color[None], pdir[None], point_conf(color.shape[0], default_conf, color.device)
+
+
+def point_conf(n, default_conf, device):
+    """[1,n,1]: ones (query_embedding's `point_conf` branch without a photometric confidence), times default_conf when 0 < default_conf < 1
+    (train_ft.py:761)."""
+    conf = torch.ones((1, n, 1), dtype=torch.float32, device=device)
+    return conf * default_conf if 0 < default_conf < 1.0 else conf
+
+
+def group_by_view(view_ids):
+    """Stable grouping (hnr_sort_rows_by_key): (perm [N] int64, sorted ids [N] int32) -- ascending view id, the original order inside a view
+    (train_ft.py:741-743: one boolean-mask pass per used view)."""
+    L = _lib.lib()
+    keys = _lib.require_gpu(view_ids, "view_ids", torch.int32).reshape(-1)
+    n, dev = int(keys.shape[0]), keys.device
+    ks, perm = torch.empty_like(keys), torch.empty_like(keys)
+    if n > 0:
+        nbytes = int(L.hnr_sort_rows_scratch_bytes(n))
+        scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.hnr_sort_rows_by_key(_lib.ptr(keys), n, _lib.ptr(ks), _lib.ptr(perm), _lib.ptr(scratch), nbytes, _lib.stream()), "hnr_sort_rows_by_key")
+    return perm.long(), ks
+
+
+def view_segments(sorted_ids):
+    """[(view id, start, end)] of a sorted id array (host)."""
+    ids = np.asarray(sorted_ids)
+    if ids.size == 0:
+        return []
+    cut = np.flatnonzero(np.diff(ids)) + 1
+    starts, ends = np.concatenate([[0], cut]), np.concatenate([cut, [ids.size]])
+    return [(int(ids[s]), int(s), int(e)) for s, e in zip(starts, ends)]
+
+
+def init_cloud_from_depth(frames, opt, campos, camdir, view_frame, capacity=None, frame_vox_res=100, device=None):
+    """run/train_ft.py:687-770 for `load_points=2`.
+
+    frames: iterable of (depth [H,W], c2w [4,4]) -- every depth frame of the scan; opt.depth_intrinsic is their intrinsic.  campos / camdir [M,3]: the
+    training cameras (`get_campos_ray`).  view_frame(view_id) -> dict(image [3,H,W], c2w, intrinsic[, feature_maps]) for a used training view.
+    Returns dict(xyz [N,3], embedding [1,N,C], color [1,N,3], dir [1,N,3], conf [1,N,1], view_of_point [N] int64): the arguments of
+    NeuralPoints.set_points, points grouped by view in ascending view id.  Without feature maps the embedding is
+    cloud_io.init_point_features(opt.feature_init_method).
+
+    capacity: points the fused cloud may hold (12 bytes each), allocated up front.  The default is the frames' upper bound
+    len(frames) * min(H*W, (frame_vox_res + 1)^3), CAPPED at 2^24 points (192 MiB).  A long scan can need more: the overflow is only known once every
+    frame has been fused, and the HnrError raised then names the capacity to pass on the next call."""
+    from . import cloud_io, voxel
+    if getattr(opt, "resample_pnts", 0) > 0:
+        raise HnrError("init_cloud_from_depth: opt.resample_pnts > 0 is not implemented")
+    campos = _lib.require_gpu(campos, "campos", torch.float32)
+    dev = campos.device if device is None else torch.device(device)
+    frames = list(frames)
+    if not frames:
+        raise HnrError("init_cloud_from_depth: no depth frame")
+    if capacity is None:
+        h, w = np.shape(frames[0][0])[-2:]
+        per = h * w if frame_vox_res <= 0 else min(h * w, (frame_vox_res + 1) ** 3)
+        capacity = min(len(frames) * per, 1 << 24)
+    fus = DepthFusion(capacity, dev, getattr(opt, "depth_intrinsic"), frame_vox_res=frame_vox_res)
+    for depth, c2w in frames:
+        fus.add(depth, c2w)
+    pts = fus.points()                                                      # the one host read of the fusion; raises on overflow before anything else is allocated
+    ranges = [float(r) for r in getattr(opt, "ranges", [-100.0] * 6)]
+    if ranges[0] > -99.0 and pts.shape[0] > 0:
+        buf, cnt = range_crop(pts, ranges)                                  # sized by the fused count, not by the capacity
+        pts = buf[:int(cnt.item())]
+    if pts.shape[0] == 0:
+        raise HnrError("init_cloud_from_depth: no point survives the depth range and opt.ranges")
+    if getattr(opt, "vox_res", 0) > 0:
+        _, _, min_idx = voxel.construct_vox_points_closest(pts.contiguous(), opt.vox_res)
+        pts = pts[min_idx]
+    cam_ind = nearest_view_ids(campos, camdir, pts)
+    perm, sorted_ids = group_by_view(cam_ind)
+    xyz = pts[perm].contiguous()
+    segs = view_segments(sorted_ids.cpu().numpy())
+    colors, dirs, confs, feats = [], [], [], []
+    for vid, s, e in segs:
+        fr = view_frame(vid)
+        f, c, d, cf = query_point_attributes(xyz[s:e], fr["image"], fr["c2w"], fr.get("w2c"), fr["intrinsic"], fr.get("feature_maps"),
+                                             getattr(opt, "default_conf", -1))
+        colors.append(c); dirs.append(d); confs.append(cf); feats.append(f)
+    if any(f is None for f in feats):
+        if not all(f is None for f in feats):
+            raise HnrError("init_cloud_from_depth: view_frame must return feature_maps for every view or for none")
+        emb, _ = cloud_io.init_point_features(xyz, opt.point_features_dim, opt.feature_init_method, xyz.device, opt.point_features_dim)
+    else:
+        emb = torch.cat(feats, dim=1)
+    return dict(xyz=xyz, embedding=emb, color=torch.cat(colors, dim=1), dir=torch.cat(dirs, dim=1), conf=torch.cat(confs, dim=1),
+                view_of_point=sorted_ids.long())

@@ -9,9 +9,12 @@
 //   hnr::march_query                     hnr_march_query                         (query_grid_point_index, :605-711)
 //   hnr::render_forward                  hnr_render_forward                      (NeuralPointsRayMarching.forward + fill_invalid, eval)
 //   hnr::render_train                    hnr_render_train_forward + _backward    (the same in train mode; autograd formula registered)
+//   hnr::nearest_view                    hnr_nearest_view                        (run/train_ft.py:48-57)
+//   hnr::point_view_attrs                hnr_point_view_attrs                    (homo_warp_nongrid + extract_from_2d_grid + the `dir` branch of query_embedding)
 // Nothing is computed here: every op validates its tensors, fills the C structs, takes the current HIP stream and calls the library.  Errors
 // of the library surface as c10::Error with hnr_last_error() as the message.  Host code only (no kernels): built by g++ against libtorch.
 #include <ATen/ATen.h>
+#include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
 #include <ATen/core/dispatch/Dispatcher.h>
@@ -378,6 +381,47 @@ std::vector<Tensor> render_train_nograd(int64_t grid, const OptList &in_l, c10::
     return outs;
 }
 
+// ---- hnr::nearest_view(Tensor xyz [N,3], Tensor campos [M,3], Tensor camdir [M,3]) -> Tensor [N] i32
+Tensor nearest_view(const Tensor &xyz, const Tensor &campos, const Tensor &camdir)
+{
+    TORCH_CHECK(xyz.dim() == 2 && xyz.size(1) == 3, "hnr::nearest_view: xyz must be [N,3]");
+    TORCH_CHECK(campos.dim() == 2 && campos.size(1) == 3 && campos.size(0) > 0 && camdir.sizes() == campos.sizes(), "hnr::nearest_view: campos / camdir must be [M,3], M > 0");
+    TORCH_CHECK(campos.device() == xyz.device() && camdir.device() == xyz.device(), "hnr::nearest_view: xyz, campos and camdir must be on one device");
+    const c10::DeviceGuard guard(xyz.device());              // the tensor's device is current for the allocations and the launch
+    Tensor out = at::empty({xyz.size(0)}, xyz.options().dtype(at::kInt));
+    if (xyz.size(0) > 0)
+        hnr_check(hnr_nearest_view(fptr(xyz, "xyz"), xyz.size(0), fptr(campos, "campos"), fptr(camdir, "camdir"), (int)campos.size(0), out.data_ptr<int32_t>(),
+                                   cur_stream(xyz)),
+                  "hnr_nearest_view");
+    return out;
+}
+
+// ---- hnr::point_view_attrs(Tensor xyz, float[] w2c, float[] c2w, float[] cam_pos_cam, float[] intrinsic, int H, int W, Tensor? feat [C,Hl,Wl])
+//      -> (features [n,C], dir [n,3], mask [n] u8).  The matrices are host values, row-major, as in the C ABI.  Without feat (the C ABI's NULL
+//      d_feat / d_out_feat) features is [n,0].
+std::tuple<Tensor, Tensor, Tensor> point_view_attrs(const Tensor &xyz, c10::ArrayRef<double> w2c, c10::ArrayRef<double> c2w, c10::ArrayRef<double> cam_pos_cam,
+                                                    c10::ArrayRef<double> intrinsic, int64_t H, int64_t W, const OptT &feat_opt)
+{
+    TORCH_CHECK(xyz.dim() == 2 && xyz.size(1) == 3, "hnr::point_view_attrs: xyz must be [n,3]");
+    TORCH_CHECK(w2c.size() == 16 && c2w.size() == 16 && cam_pos_cam.size() == 3 && intrinsic.size() == 9, "hnr::point_view_attrs: w2c / c2w hold 16 values, cam_pos_cam 3, intrinsic 9");
+    const bool sample = feat_opt.has_value() && feat_opt->defined();
+    if (sample) TORCH_CHECK(feat_opt->dim() == 3 && feat_opt->device() == xyz.device(), "hnr::point_view_attrs: feat must be [C,Hl,Wl] on xyz's device");
+    const c10::DeviceGuard guard(xyz.device());              // the tensor's device is current for the allocations and the launch
+    float m[16 + 16 + 3 + 9];
+    for (int i = 0; i < 16; ++i) { m[i] = (float)w2c[i]; m[16 + i] = (float)c2w[i]; }
+    for (int i = 0; i < 3; ++i) m[32 + i] = (float)cam_pos_cam[i];
+    for (int i = 0; i < 9; ++i) m[35 + i] = (float)intrinsic[i];
+    const int64_t n = xyz.size(0);
+    const int64_t C = sample ? feat_opt->size(0) : 0;
+    Tensor out = new_f32({n, C}, xyz), dir = new_f32({n, 3}, xyz), mask = at::empty({n}, xyz.options().dtype(at::kByte));
+    if (n > 0)
+        hnr_check(hnr_point_view_attrs(fptr(xyz, "xyz"), n, m, m + 16, m + 32, m + 35, (int)H, (int)W, sample ? fptr(*feat_opt, "feat") : nullptr, (int)C,
+                                       sample ? (int)feat_opt->size(1) : 0, sample ? (int)feat_opt->size(2) : 0, sample ? out.data_ptr<float>() : nullptr,
+                                       dir.data_ptr<float>(), mask.data_ptr<uint8_t>(), cur_stream(xyz)),
+                  "hnr_point_view_attrs");
+    return {out, dir, mask};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(hnr, m)
@@ -395,6 +439,8 @@ TORCH_LIBRARY(hnr, m)
           "int raydist_mode_unit, int knn_order, float slope, int cap_samples) -> Tensor[]");
     m.def("render_train_bwd(Tensor?[] inputs, Tensor[] weights, Tensor[] fwd, Tensor g_raycolor, Tensor? g_conf_coefficient, int SR, int[] kernel_size, float radius2, "
           "float vsize_z, int raydist_mode_unit, int knn_order, float slope, int cap_samples) -> Tensor[]");
+    m.def("nearest_view(Tensor xyz, Tensor campos, Tensor camdir) -> Tensor");
+    m.def("point_view_attrs(Tensor xyz, float[] w2c, float[] c2w, float[] cam_pos_cam, float[] intrinsic, int H, int W, Tensor? feat) -> (Tensor, Tensor, Tensor)");
 }
 TORCH_LIBRARY_IMPL(hnr, CompositeExplicitAutograd, m)
 {
@@ -408,6 +454,8 @@ TORCH_LIBRARY_IMPL(hnr, CUDA, m)
     m.impl("render_forward", &render_forward);
     m.impl("render_train_fwd", &render_train_fwd);
     m.impl("render_train_bwd", &render_train_bwd);
+    m.impl("nearest_view", &nearest_view);
+    m.impl("point_view_attrs", &point_view_attrs);
 }
 TORCH_LIBRARY_IMPL(hnr, Autograd, m)
 {

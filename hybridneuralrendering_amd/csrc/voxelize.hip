@@ -8,28 +8,25 @@
 // Here: 63-bit cell keys -> stable radix sort of (key, point id) (rocprim) -> head flags + scan = voxel ids in the reference's
 // lexicographic order -> one thread per voxel walks its (short) run twice: centroid as a sequential fp32 sum in point-id order
 // (torch_scatter's CPU order; its CUDA path uses atomics and is not reproducible), then the first point with the smallest
-// residual.  Deterministic; no atomics.
+// residual.  Deterministic; no atomics.  The sort / head flags / scan and the run walk are shared with the per-frame depth fusion of
+// cloud_init.hip (voxel_segments.h).
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 
-#include "hnr_common.h"
+#include "voxel_segments.h"
 
 namespace hnr {
-
-constexpr int VOX_BITS = 21;        // cells per axis < 2^21
 
 __global__ void vox_keys_kernel(const float *__restrict__ xyz, int n, float mx, float my, float mz, float sz, unsigned long long *__restrict__ keys,
                                 int *__restrict__ bad)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float qx = floorf(hnr_div(__fsub_rn(xyz[3 * i + 0], mx), sz));
-    const float qy = floorf(hnr_div(__fsub_rn(xyz[3 * i + 1], my), sz));
-    const float qz = floorf(hnr_div(__fsub_rn(xyz[3 * i + 2], mz), sz));
+    const float qx = vox_cell(xyz[3 * i + 0], mx, sz), qy = vox_cell(xyz[3 * i + 1], my, sz), qz = vox_cell(xyz[3 * i + 2], mz, sz);
     const float lim = (float)(1 << VOX_BITS);
     if (!(qx >= 0.f && qx < lim && qy >= 0.f && qy < lim && qz >= 0.f && qz < lim)) { atomicOr(bad, 1); keys[i] = ~0ull >> 1; return; }
-    keys[i] = ((unsigned long long)(unsigned)qx << (2 * VOX_BITS)) | ((unsigned long long)(unsigned)qy << VOX_BITS) | (unsigned long long)(unsigned)qz;
+    keys[i] = vox_pack_key(qx, qy, qz, VOX_BITS);
 }
 
 __global__ void vox_heads_kernel(const unsigned long long *__restrict__ keys_sorted, int n, int *__restrict__ head)
@@ -50,14 +47,8 @@ __global__ void vox_reduce_kernel(const float *__restrict__ xyz, const unsigned 
     if (!head[i]) return;
     const int v = vid1[i] - 1;
     const unsigned long long key = keys_sorted[i];
-    int e = i;
-    float sx = 0.f, sy = 0.f, sz = 0.f;
-    for (; e < n && keys_sorted[e] == key; ++e) {
-        const int p = perm[e];
-        sx += xyz[3 * p + 0]; sy += xyz[3 * p + 1]; sz += xyz[3 * p + 2];
-    }
-    const float cnt = (float)(e - i);
-    const float cx = hnr_div(sx, cnt), cy = hnr_div(sy, cnt), cz = hnr_div(sz, cnt);
+    float cx, cy, cz;
+    const int e = vox_run_centroid(xyz, keys_sorted, perm, i, n, key, cx, cy, cz);
     float best = 0.f;
     int arg = -1;
     for (int k = i; k < e; ++k) {
@@ -73,18 +64,12 @@ __global__ void vox_reduce_kernel(const float *__restrict__ xyz, const unsigned 
     min_idx[v] = arg;
 }
 
-}  // namespace hnr
-
-using namespace hnr;
-
-static size_t vox_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
-static int vox_layout(int64_t n, size_t *sort_bytes, size_t *scan_bytes, size_t *total)
+int vox_layout(int64_t n, int end_bit, size_t *sort_bytes, size_t *scan_bytes, size_t *total)
 {
     size_t sb = 0, cb = 0;
     rocprim::counting_iterator<int> iota(0);
     if (rocprim::radix_sort_pairs(nullptr, sb, (const unsigned long long *)nullptr, (unsigned long long *)nullptr, iota, (int *)nullptr, (size_t)n, 0,
-                                  3 * VOX_BITS, (hipStream_t) nullptr) != hipSuccess)
+                                  end_bit, (hipStream_t) nullptr) != hipSuccess)
         return -1;
     if (rocprim::inclusive_scan(nullptr, cb, (const int *)nullptr, (int *)nullptr, (size_t)n, rocprim::plus<int>(), (hipStream_t) nullptr) != hipSuccess)
         return -1;
@@ -95,11 +80,33 @@ static int vox_layout(int64_t n, size_t *sort_bytes, size_t *scan_bytes, size_t 
     return 0;
 }
 
+int vox_sort_segments(const unsigned long long *keys, int n, int end_bit, unsigned long long *keys_sorted, int *perm, int *head, int *vid1, void *tmp,
+                      size_t sort_bytes, size_t scan_bytes, hipStream_t st)
+{
+    rocprim::counting_iterator<int> iota(0);
+    size_t sz = sort_bytes;
+    HNR_HIP_CHECK(rocprim::radix_sort_pairs(tmp, sz, keys, keys_sorted, iota, perm, (size_t)n, 0, end_bit, st));
+    vox_heads_kernel<<<cdiv(n, 256), 256, 0, st>>>(keys_sorted, n, head);
+    HNR_LAUNCH_CHECK();
+    return vox_scan_flags(head, vid1, n, tmp, scan_bytes, st);
+}
+
+int vox_scan_flags(const int *flags, int *incl, int n, void *tmp, size_t scan_bytes, hipStream_t st)
+{
+    size_t sz = scan_bytes;
+    HNR_HIP_CHECK(rocprim::inclusive_scan(tmp, sz, flags, incl, (size_t)n, rocprim::plus<int>(), st));
+    return HNR_OK;
+}
+
+}  // namespace hnr
+
+using namespace hnr;
+
 extern "C" int64_t hnr_voxel_downsample_scratch_bytes(int64_t n)
 {
     if (n <= 0) return 256;
     size_t total = 0;
-    if (vox_layout(n, nullptr, nullptr, &total) != 0) return -1;
+    if (vox_layout(n, 3 * VOX_BITS, nullptr, nullptr, &total) != 0) return -1;
     return (int64_t)total;
 }
 
@@ -110,7 +117,7 @@ extern "C" int hnr_voxel_downsample(const float *d_xyz, int n, const float *spac
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) { if (d_count) HNR_HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(int64_t), st)); return HNR_OK; }
     size_t sb = 0, cb = 0, total = 0;
-    if (!d_xyz || !d_centroid || !d_grid_idx || !d_min_idx || !d_count || !d_scratch || vox_layout(n, &sb, &cb, &total) != 0 || (size_t)scratch_bytes < total) {
+    if (!d_xyz || !d_centroid || !d_grid_idx || !d_min_idx || !d_count || !d_scratch || vox_layout(n, 3 * VOX_BITS, &sb, &cb, &total) != 0 || (size_t)scratch_bytes < total) {
         set_error("hnr_voxel_downsample: NULL argument or scratch smaller than hnr_voxel_downsample_scratch_bytes(n)"); return HNR_ERR_BADARG;
     }
     char *p = (char *)d_scratch;
@@ -124,13 +131,7 @@ extern "C" int hnr_voxel_downsample(const float *d_xyz, int n, const float *spac
     HNR_HIP_CHECK(hipMemsetAsync(bad, 0, sizeof(int), st));
     vox_keys_kernel<<<cdiv(n, 256), 256, 0, st>>>(d_xyz, n, space_min[0], space_min[1], space_min[2], vox_size, keys, bad);
     HNR_LAUNCH_CHECK();
-    rocprim::counting_iterator<int> iota(0);
-    size_t sz = sb;
-    HNR_HIP_CHECK(rocprim::radix_sort_pairs(tmp, sz, keys, keys_sorted, iota, perm, (size_t)n, 0, 3 * VOX_BITS, st));
-    vox_heads_kernel<<<cdiv(n, 256), 256, 0, st>>>(keys_sorted, n, head);
-    HNR_LAUNCH_CHECK();
-    sz = cb;
-    HNR_HIP_CHECK(rocprim::inclusive_scan(tmp, sz, head, vid, (size_t)n, rocprim::plus<int>(), st));
+    if (int rc = vox_sort_segments(keys, n, 3 * VOX_BITS, keys_sorted, perm, head, vid, tmp, sb, cb, st)) return rc;
     vox_reduce_kernel<<<cdiv(n, 256), 256, 0, st>>>(d_xyz, keys_sorted, perm, head, vid, n, d_centroid, d_grid_idx, d_min_idx, d_inverse, (long long *)d_count);
     HNR_LAUNCH_CHECK();
     int h_bad = 0;

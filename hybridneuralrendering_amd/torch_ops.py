@@ -1,7 +1,8 @@
 """torch.ops.hnr.*: the path as dispatcher-visible PyTorch ops (csrc/torch_ops/hnr_torch.cpp, TORCH_LIBRARY(hnr) over the C ABI of libhnr_hip.so).
 
 SURVEY 8b asks for both op layers: the C ABI (include/hnr.h, bound by ctypes in _lib.py -- needs no torch headers) and registered torch ops.  The
-ops are the same library calls with schemas: `hnr::grid_build`, `hnr::grid_free`, `hnr::march_query`, `hnr::render_forward`
+ops are the same library calls with schemas: `hnr::grid_build`, `hnr::grid_free`, `hnr::march_query`, `hnr::nearest_view`, `hnr::point_view_attrs`
+(the cloud initialisation of cloud_init.py), `hnr::render_forward`
 (NeuralPointsRayMarching.forward + fill_invalid in eval mode, /root/reference/models/neural_points_volumetric_model.py:257-391, :87-126) and
 `hnr::render_train` (the same in train mode with the backward pass registered as its autograd formula; the reference leaves that to torch autograd,
 models/mvs_points_volumetric_model.py:111-131).  This module loads the extension and builds the ops' argument lists from the host-side objects
@@ -94,6 +95,16 @@ def _register_fakes():
                [torch.empty_like(w) if (views or not image_branch(i)) else w.new_empty((0,)) for i, w in enumerate(weights)]
 
 
+    @torch.library.register_fake("hnr::nearest_view")
+    def _(xyz, campos, camdir):
+        return xyz.new_empty((xyz.shape[0],), dtype=i32)
+
+    @torch.library.register_fake("hnr::point_view_attrs")
+    def _(xyz, w2c, c2w, cam_pos_cam, intrinsic, H, W, feat):
+        n, e = xyz.shape[0], xyz.new_empty
+        return (e((n, feat.shape[0] if feat is not None else 0), dtype=f32), e((n, 3), dtype=f32), e((n,), dtype=torch.uint8))
+
+
 def load():
     """Registers torch.ops.hnr (once), with shape functions for tracing.  libhnr_torch.so links libhnr_hip.so next to it."""
     global _loaded
@@ -174,3 +185,20 @@ def render_train(renderer, aggregator, xyz, emb, conf, pdir, color, raydir, camp
                            float(np.float32(hp[0] ** 2)), float(np.float32(opt.vsize[2])), int(getattr(opt, "raydist_mode_unit", 0) > 0), 0,
                            float(aggregator.block1[1].negative_slope), 0)
     return dict(zip(TRAIN_OUTPUTS, out))
+
+
+def nearest_view(campos, raydir, xyz, id_list=None):
+    """cloud_init.nearest_view through torch.ops.hnr.nearest_view: [N,1] int64 (run/train_ft.py:48-57)."""
+    ops = load()
+    g = _lib.require_gpu
+    return ops.nearest_view(g(xyz, "xyz", torch.float32).reshape(-1, 3), g(campos, "campos", torch.float32).reshape(-1, 3),
+                            g(raydir, "raydir", torch.float32).reshape(-1, 3)).long().view(-1, 1)
+
+
+def point_view_attrs(xyz, w2c, c2w, cam_pos_cam, intrinsic, H, W, feat=None):
+    """cloud_init.point_view_attrs through torch.ops.hnr.point_view_attrs: (features [n,C], dir [n,3], mask [n] uint8); without `feat` the features are
+    [n,0].  The matrices are host arrays (fp32 values travel exactly through the op's float[] arguments)."""
+    ops = load()
+    flat = lambda a, n: [float(v) for v in np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float32).reshape(n)]
+    return ops.point_view_attrs(_lib.require_gpu(xyz, "xyz", torch.float32).reshape(-1, 3), flat(w2c, 16), flat(c2w, 16), flat(cam_pos_cam, 3), flat(intrinsic, 9),
+                                int(H), int(W), None if feat is None else _lib.require_gpu(feat, "feat", torch.float32))

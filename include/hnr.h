@@ -23,7 +23,7 @@
  *              hnr_last_error, hnr_points_bounds, hnr_grid_* (build / destroy / stats / bytes), hnr_march_query, hnr_ray_compact*, hnr_point_records,
  *              hnr_image_features*, hnr_render_forward* (+ workspace sizing), hnr_render_train_forward / _backward / _backward_depth (+ sizing),
  *              hnr_shipped_loss*, hnr_composite, hnr_ray_depth, hnr_ray_march, hnr_voxel_downsample*, hnr_probe_select, hnr_blur_*,
- *              hnr_frame_metrics* (and the HNR_FM_* row layout).
+ *              hnr_frame_metrics* (and the HNR_FM_* row layout), hnr_depth_fuse*, hnr_range_crop*, hnr_nearest_view, hnr_point_view_attrs.
  *   STAGE   -- everything else (hnr_chain_*, hnr_mlp3_*, hnr_merge*, hnr_mixup_stage, hnr_proj_*, hnr_h2*, hnr_linear_*, hnr_gather_*, hnr_ksum*,
  *              hnr_segment_*, hnr_absmax, hnr_div_probe, ...): the individual stages the two single-call entries are built from.  They are exported so
  *              that tests/ can compare every stage with the oracle and so that tools/ can time them alone; their signatures, workspace layouts and
@@ -825,6 +825,48 @@ int hnr_point_grad_apply(const float *d_all_rec, int n_ranks, int capacity, floa
 int64_t hnr_voxel_downsample_scratch_bytes(int64_t n);
 int hnr_voxel_downsample(const float *d_xyz, int n, const float *space_min, float vox_size, float *d_centroid, int32_t *d_grid_idx,
                          int32_t *d_min_idx, int32_t *d_inverse, int64_t *d_count, void *d_scratch, int64_t scratch_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The initial point cloud from posed depth frames (`load_points=2`, run/train_ft.py:687-770).  Stream-ordered, nothing is read back; every fp32
+ * operation is rounded on its own in the order given (tests/cloud_init_ref.py restates them).
+ *
+ * hnr_depth_fuse_frame -- one depth frame: data/scannet_ft_dataset.py:609-642 (read_depth's scaling and range rule, back-projection,
+ * `construct_vox_points_xyz`, models/mvs/mvs_utils.py:503-517, on the frame's own bounds) + the torch.cat at :642 as an append at a device count.
+ *   d_depth [H,W] uint16 (raw / depth_div) or float32 (metres); Ki [3,3] inverse depth intrinsic, c2w [4,4]: host floats, row-major.
+ *   Per pixel (px, py), row-major: d = 0 where d > depth_max or d < depth_min; v = (px*d, py*d, d); cam[c] = (v0*Ki[c][0] + v1*Ki[c][1]) + v2*Ki[c][2];
+ *   kept when cam[2] > 0; world[c] = ((cam0*M[c][0] + cam1*M[c][1]) + cam2*M[c][2]) + M[c][3].  The kept points are voxelised with frame_vox_res
+ *   cells on their own bounding cube (x 1.05) and the per-voxel centroids (sequential fp32 sum in pixel order / count), in lexicographic cell order,
+ *   are written to d_cloud [capacity,3] at d_count[0], which grows by their number.  frame_vox_res <= 0: the kept points themselves, pixel order.
+ *   A frame without a kept pixel appends nothing (the reference raises there).  Nothing is written past capacity: d_status[0] |= HNR_CLOUD_OVERFLOW and
+ *   d_count[0] keeps counting, so it ends as the capacity the run needed.  d_scratch: hnr_depth_fuse_scratch_bytes(H, W) bytes (negative: bad shape). */
+#define HNR_CLOUD_OVERFLOW 1
+int64_t hnr_depth_fuse_scratch_bytes(int H, int W);
+int hnr_depth_fuse_frame(const void *d_depth, int depth_is_u16, int H, int W, const float *Ki, const float *c2w, float depth_div, float depth_min,
+                         float depth_max, int frame_vox_res, float *d_cloud, int64_t capacity, int64_t *d_count, int32_t *d_status, void *d_scratch,
+                         int64_t scratch_bytes, void *stream);
+
+/* Range crop (run/train_ft.py:713-716, data/scannet_ft_dataset.py:643-646): d_out = the points of d_xyz[0 : d_n_in[0]] with
+ * ranges[0:3] <= p <= ranges[3:6], in their order; d_n_out[0] = their number.  ranges: 6 host floats; ranges[0] <= -99 keeps every point.
+ * n_max >= d_n_in[0] sizes the launch, d_out [n_max,3] and the scratch (hnr_range_crop_scratch_bytes(n_max); negative: n_max outside 1 .. 2^30). */
+int64_t hnr_range_crop_scratch_bytes(int64_t n_max);
+int hnr_range_crop(const float *d_xyz, const int64_t *d_n_in, int64_t n_max, const float *ranges, float *d_out, int64_t *d_n_out, void *d_scratch,
+                   int64_t scratch_bytes, void *stream);
+
+/* `nearest_view` (run/train_ft.py:48-57) in one launch: d_view[i] = argmin over the M cameras of
+ *   n / 200 + (1.1 - ((ux*rx + uy*ry) + uz*rz)),  d = p - campos, n = sqrt((dx*dx + dy*dy) + dz*dz), u = d / (n + 1e-6), r = camdir;
+ * the first strict minimum wins (torch.argmin).  d_xyz [N,3], d_campos / d_camdir [M,3], d_view [N] int32. */
+int hnr_nearest_view(const float *d_xyz, int64_t N, const float *d_campos, const float *d_camdir, int M, int32_t *d_view, void *stream);
+
+/* Per-point attributes from the view a point was assigned to: `homo_warp_nongrid` + `extract_from_2d_grid` (models/mvs/mvs_utils.py:299-315, :411-420)
+ * and the `dir` branch of `query_embedding` with pointdir_w=True (models/mvs/mvs_points_model.py:239-251), called at run/train_ft.py:759-760.
+ *   cam[c] = ((x*w2c[c][0] + y*w2c[c][1]) + z*w2c[c][2]) + w2c[c][3];  q = cam / cam[2];  gx = (q0*K00 + q1*K01) + K02, gy likewise with row 1;
+ *   mask = 0 <= gx <= W-1 && 0 <= gy <= H-1 (NaN: 0; no z > 0 test, as in the reference);
+ *   d_out_feat [n,C]: bilinear sample of d_feat [C,Hl,Wl] at (gx*(Wl-1)/(W-1), gy*(Hl-1)/(H-1)), zero padding, align_corners=True; zeros where mask = 0;
+ *   d_out_dir [n,3], for every point: e = cam - cam_pos_cam, u = e / (|e| + 1e-6), dir[c] = (u0*R[c][0] + u1*R[c][1]) + u2*R[c][2], R = c2w[:3,:3].
+ * w2c, c2w [4,4], cam_pos_cam [3] (= (c2w[:,3] @ w2c^T)[:3], computed by the caller as the reference does), K [3,3]: host floats.  Any of the three
+ * outputs may be NULL (not all); d_feat / C / Hl / Wl are read only with d_out_feat. */
+int hnr_point_view_attrs(const float *d_xyz, int64_t n, const float *w2c, const float *c2w, const float *cam_pos_cam, const float *K, int H, int W,
+                         const float *d_feat, int C, int Hl, int Wl, float *d_out_feat, float *d_out_dir, uint8_t *d_out_mask, void *stream);
 
 #ifdef __cplusplus
 }

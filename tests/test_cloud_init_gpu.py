@@ -1,0 +1,340 @@
+"""Cloud initialisation from depth frames on the GPU (csrc/cloud_init.hip, hybridneuralrendering_amd/cloud_init.py): every stage bit-equal to the
+NumPy restatement (tests/cloud_init_ref.py) on the reference-generated fixture and on seeded cases that are deliberately NOT boundary-safe, within
+the CPU test's bounds of the reference golden, plus the DepthFusion / torch-op / end-to-end behaviour.  Reads only the fixture and the restatement."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests import cloud_init_ref as R
+from tests.golden_io import GOLD
+from tests.test_cloud_init import attr_bounds, backproject_bound, centroid_bound, frame_slices
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+
+
+@pytest.fixture(scope="module")
+def gold():
+    z = np.load(os.path.join(GOLD, "cloud_init.npz"))
+    return {k: z[k] for k in z.files}
+
+
+def bits(a):
+    a = np.ascontiguousarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a)
+    return a.view(np.uint32) if a.dtype == np.float32 else a
+
+
+def assert_bits_equal(got, want):
+    got, want = bits(got), bits(want)
+    assert got.shape == want.shape, (got.shape, want.shape)
+    np.testing.assert_array_equal(got, want)
+
+
+def t(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def fuse_one(depth, K, c2w, res, capacity=None, **kw):
+    from hybridneuralrendering_amd.cloud_init import DepthFusion
+    f = DepthFusion(capacity or depth.size, DEV, K, frame_vox_res=res, **kw)
+    f.add(depth, c2w)
+    return f.points()
+
+
+@pytest.mark.parametrize("res", [12, 100, 0])
+def test_fusion_is_bit_equal_to_the_restatement_and_within_bounds_of_the_reference(gold, res):
+    K, Ki = gold["depth_intrinsic"], gold["depth_intrinsic_inv"]
+    sl = frame_slices(gold["fuse%d_counts" % res]) if res else frame_slices(gold["bp_counts"])
+    ref_all = gold["fuse%d_xyz" % res] if res else gold["bp_xyz"]
+    for i in range(5):
+        got = fuse_one(gold["frames"][i], K, gold["poses"][i], res).cpu().numpy()
+        assert_bits_equal(got, R.fuse_frame(gold["frames"][i], Ki, gold["poses"][i], res))
+        if i == 4:
+            assert got.shape == (0, 3)                                                            # the all-zero frame appends nothing
+            continue
+        ref = ref_all[sl[i]]
+        world, kept = R.backproject(gold["frames"][i], Ki, gold["poses"][i])
+        e_pt = 2 * backproject_bound(gold["frames"][i], Ki, gold["poses"][i])[kept]
+        if res:
+            bound, _ = centroid_bound(world[kept], R.vox_centroids(world[kept], res)[2], e_pt)
+        else:
+            bound = e_pt
+        assert got.shape == ref.shape and (np.abs(got.astype(np.float64) - ref.astype(np.float64)) <= bound).all()
+
+
+def test_float_depth_equals_uint16_depth(gold):
+    """float32 metres in = the uint16 path's own d = raw / 1000"""
+    K = gold["depth_intrinsic"]
+    metres = gold["frames"][1].astype(np.float32) / np.float32(1000)
+    assert_bits_equal(fuse_one(metres, K, gold["poses"][1], 100), fuse_one(gold["frames"][1], K, gold["poses"][1], 100))
+    on_dev = torch.from_numpy(gold["frames"][1].view(np.int16)).to(DEV)                             # a frame already on the device
+    assert_bits_equal(fuse_one(on_dev, K, gold["poses"][1], 100, capacity=10000), fuse_one(gold["frames"][1], K, gold["poses"][1], 100))
+
+
+def boundary_case():
+    """61x45 float depth whose world z is the depth itself (Ki and c2w keep z apart), with interior pixels moved onto exact multiples of the cell size
+    above space_min: floor((p - space_min) / size) lands on integers there, where one ulp decides the cell."""
+    rng = np.random.default_rng(11)
+    H, W, res = 45, 61, 48
+    K = np.array([[8, 0, 30], [0, 8, 22], [0, 0, 1]], np.float32)
+    Ki = torch.inverse(torch.from_numpy(K)).numpy()                                                 # what DepthFusion forms
+    assert np.array_equal(Ki[2], [0, 0, 1])
+    c2w = np.eye(4, dtype=np.float32)
+    c2w[:3, 3] = [0.5, -0.25, 0.125]
+    depth = rng.uniform(1.0, 3.0, size=(H, W)).astype(np.float32)
+    depth[rng.uniform(size=(H, W)) < 0.2] = 0
+    depth[0, 0], depth[H - 1, W - 1], depth[0, W - 1], depth[H - 1, 0] = 1.0, 3.0, 3.0, 3.0          # pin the bounds
+    world, kept = R.backproject(depth, Ki, c2w, depth_min=0.3, depth_max=8.0)
+    smin, vsz = R.space_of(world[kept], res)
+    ys, xs = rng.integers(5, H - 5, size=300), rng.integers(5, W - 5, size=300)
+    ks = rng.integers(int(np.ceil((1.3 - smin[2]) / vsz)), int(np.floor((2.9 - smin[2]) / vsz)) + 1, size=300)
+    z = (smin[2] + ks.astype(np.float32) * vsz).astype(np.float32)
+    ok = (z > 1.25) & (z < 2.95)
+    depth[ys[ok], xs[ok]] = (z[ok] - np.float32(0.125)).astype(np.float32)
+    world, kept = R.backproject(depth, Ki, c2w)
+    smin2, vsz2 = R.space_of(world[kept], res)
+    assert np.array_equal(smin, smin2) and vsz == vsz2
+    q = (world[kept][:, 2] - smin[2]) / vsz
+    hits = int((q == np.floor(q)).sum())
+    assert hits >= 20, hits
+    return depth, K, Ki, c2w, res, hits
+
+
+def test_fusion_on_exact_cell_boundaries_is_bit_equal():
+    depth, K, Ki, c2w, res, hits = boundary_case()
+    for r in (res, 100, 0):
+        assert_bits_equal(fuse_one(depth, K, c2w, r), R.fuse_frame(depth, Ki, c2w, r))
+
+
+def test_depth_fusion_appends_frames_in_order_and_is_deterministic(gold):
+    from hybridneuralrendering_amd.cloud_init import DepthFusion
+    K = gold["depth_intrinsic"]
+    runs = []
+    for _ in range(2):
+        f = DepthFusion(20000, DEV, K, frame_vox_res=100)
+        for i in (0, 4, 1, 2, 3):
+            f.add(gold["frames"][i], gold["poses"][i])
+        runs.append(f.points().clone())
+    single = torch.cat([fuse_one(gold["frames"][i], K, gold["poses"][i], 100) for i in (0, 4, 1, 2, 3)])
+    assert_bits_equal(runs[0], single)
+    assert_bits_equal(runs[0], runs[1])
+    assert runs[0].shape[0] == int(gold["fuse100_counts"].sum())
+
+
+def test_overflow_raises_with_the_needed_capacity_and_writes_nothing_past_the_buffer(gold):
+    from hybridneuralrendering_amd.cloud_init import DepthFusion
+    from hybridneuralrendering_amd._lib import HnrError, lib
+    K = gold["depth_intrinsic"]
+    need = int(gold["fuse100_counts"].sum())
+    cap, guard = need - 10, 64
+    for res, want in ((100, need), (0, int(gold["bp_counts"].sum()))):
+        cap = want - 10
+        f = DepthFusion(cap, DEV, K, frame_vox_res=res)
+        big = torch.full((cap + guard, 3), -777.0, device=DEV)
+        f.cloud = big[:cap]
+        for i in range(4):
+            f.add(gold["frames"][i], gold["poses"][i])
+        with pytest.raises(HnrError, match="needs capacity %d" % want):
+            f.points()
+        assert torch.all(big[cap:] == -777.0)
+        ok = DepthFusion(want, DEV, K, frame_vox_res=res)
+        for i in range(4):
+            ok.add(gold["frames"][i], gold["poses"][i])
+        assert_bits_equal(big[:cap], ok.points()[:cap])                                            # what fitted is what an ample buffer holds
+    assert lib().hnr_depth_fuse_scratch_bytes(480, 640) > 480 * 640 * 40 and lib().hnr_range_crop_scratch_bytes(1000) >= 8000
+
+
+def test_range_crop_is_bit_equal_and_equals_the_reference(gold):
+    from hybridneuralrendering_amd.cloud_init import range_crop
+    x = t(gold["fuse100_xyz"])
+    buf, n = range_crop(x, gold["ranges"])
+    got = buf[:int(n.item())]
+    assert_bits_equal(got, R.range_crop(gold["fuse100_xyz"], gold["ranges"]))
+    assert_bits_equal(got, gold["crop_xyz"])
+    # a device-side input count, and the keep-everything rule
+    k = 1500
+    buf, n = range_crop(x, gold["ranges"], count=torch.tensor([k], device=DEV))
+    assert_bits_equal(buf[:int(n.item())], R.range_crop(gold["fuse100_xyz"][:k], gold["ranges"]))
+    buf, n = range_crop(x, [-100.0, 0, 0, 0, 0, 0])
+    assert int(n.item()) == x.shape[0] and torch.equal(buf, x)
+    # points exactly on the range faces stay (<=, >=)
+    r = gold["ranges"]
+    edge = np.array([[r[0], r[1], r[2]], [r[3], r[4], r[5]], [np.nextafter(r[3], np.float32(99)), r[4], r[5]], [r[0], np.nextafter(r[1], np.float32(-99)), r[2]]], np.float32)
+    buf, n = range_crop(t(edge), r)
+    assert int(n.item()) == 2 and torch.equal(buf[:2].cpu(), torch.from_numpy(edge[:2]))
+
+
+def test_final_voxel_stage_selects_the_reference_points(gold):
+    from hybridneuralrendering_amd.voxel import construct_vox_points_closest
+    cen, grid, midx = construct_vox_points_closest(t(gold["s2_xyz"]), int(gold["s2_res"][0]))
+    np.testing.assert_array_equal(grid.cpu().numpy(), gold["s2_grid"])
+    np.testing.assert_array_equal(midx.cpu().numpy(), gold["s2_min_idx"])
+    assert_bits_equal(cen, R.vox_centroids(gold["s2_xyz"], int(gold["s2_res"][0]))[0])
+
+
+@pytest.mark.parametrize("M", [5, 70])
+def test_nearest_view_on_the_fixture(gold, M):
+    from hybridneuralrendering_amd.cloud_init import nearest_view
+    ind = nearest_view(t(gold["nv_campos%d" % M]), t(gold["nv_camdir%d" % M]), t(gold["nv_xyz"]), None)
+    assert ind.dtype == torch.int64 and tuple(ind.shape) == (gold["nv_xyz"].shape[0], 1)
+    np.testing.assert_array_equal(ind.cpu().numpy()[:, 0], R.nearest_view(gold["nv_xyz"], gold["nv_campos%d" % M], gold["nv_camdir%d" % M]))
+    np.testing.assert_array_equal(ind.cpu().numpy(), gold["nv_ind%d" % M])
+
+
+@pytest.fixture(scope="module")
+def tie_case():
+    rng = np.random.default_rng(7)
+    xyz = (rng.uniform(-1, 1, size=(3001, 3)) * np.array([3.0, 2.0, 1.0])).astype(np.float32)
+    pos = (rng.uniform(-1, 1, size=(257, 3)) * np.array([3.0, 2.0, 1.0])).astype(np.float32)
+    d = rng.normal(size=(257, 3))
+    d = (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(np.float32)
+    # exact ties: duplicated cameras, inside a 64-camera chunk, across the chunk boundary and in the last partial chunk
+    for dst, src in ((9, 2), (40, 39), (64, 3), (100, 63), (130, 5), (256, 7), (200, 190)):
+        pos[dst], d[dst] = pos[src], d[src]
+    return xyz, pos, d
+
+
+@pytest.mark.parametrize("M", [1, 64, 65, 257])
+def test_nearest_view_ties_go_to_the_lowest_index(tie_case, M):
+    from hybridneuralrendering_amd.cloud_init import nearest_view_ids
+    xyz, pos, d = tie_case
+    got = nearest_view_ids(t(pos[:M]), t(d[:M]), t(xyz)).cpu().numpy()
+    want = R.nearest_view(xyz, pos[:M], d[:M])
+    np.testing.assert_array_equal(got, want)
+    if M > 9:                                                                                      # the ties are really there, and the first copy won
+        dup = {9: 2, 40: 39, 64: 3, 100: 63, 130: 5, 256: 7, 200: 190}
+        firsts = [s for k, s in dup.items() if k < M]
+        assert np.isin(want, firsts).sum() > 0 and not np.isin(want, [k for k in dup if k < M]).any()
+
+
+def _attrs(gold, feat):
+    from hybridneuralrendering_amd import cloud_init as ci
+    H, W = gold["at_image"].shape[1:]
+    cpc = ci.cam_pos_cam(gold["at_c2w"], gold["at_w2c"])
+    return ci.point_view_attrs(t(gold["at_xyz"]), gold["at_w2c"], gold["at_c2w"], cpc, gold["at_K"], H, W, feat=t(feat)), cpc
+
+
+def test_point_attributes_on_the_fixture(gold):
+    from hybridneuralrendering_amd import cloud_init as ci
+    H, W = gold["at_image"].shape[1:]
+    for name, ref in (("at_image", gold["at_color"]), ("at_fmap", gold["at_feat"])):
+        (f, d, m), cpc = _attrs(gold, gold[name])
+        rf, rd, rm = R.view_attrs(gold["at_xyz"], gold["at_w2c"], gold["at_c2w"], cpc, gold["at_K"], H, W, gold[name])
+        assert_bits_equal(f, rf); assert_bits_equal(d, rd); assert_bits_equal(m, rm)
+        np.testing.assert_array_equal(m.cpu().numpy(), gold["at_mask"])
+        inside = gold["at_mask"] > 0
+        err = np.abs(f.cpu().numpy().astype(np.float64) - ref.astype(np.float64))
+        assert (err[inside] <= np.broadcast_to(attr_bounds(gold, gold[name])[:, None], err.shape)[inside]).all() and (err[~inside] == 0).all()
+        assert np.abs(d.cpu().numpy().astype(np.float64) - gold["at_dir"]).max() <= 2e-6
+    # the public call: shapes of query_embedding's return, default_conf
+    feats, col, pdir, conf = ci.query_point_attributes(t(gold["at_xyz"]), t(gold["at_image"]), gold["at_c2w"], gold["at_w2c"], gold["at_K"],
+                                                       feature_maps=[t(gold["at_fmap"]), t(gold["at_image"])], default_conf=0.15)
+    n = gold["at_xyz"].shape[0]
+    assert tuple(feats.shape) == (1, n, 11) and tuple(col.shape) == (1, n, 3) and tuple(pdir.shape) == (1, n, 3) and tuple(conf.shape) == (1, n, 1)
+    assert torch.all(conf == np.float32(0.15)) and torch.equal(feats[0, :, 8:], col[0])
+    (f, _, _), _ = _attrs(gold, gold["at_fmap"])
+    assert torch.equal(feats[0, :, :8], f)
+
+
+def test_point_attributes_on_integer_pixel_coordinates():
+    """n = 1025 (more than one block, odd): identity camera, so gx = x / z with z = 1 is the pixel coordinate itself -- integers, the frame's
+    borders included -- on a map of another size than the frame."""
+    from hybridneuralrendering_amd import cloud_init as ci
+    rng = np.random.default_rng(3)
+    H, W, n = 21, 33, 1025
+    fmap = rng.normal(size=(5, 11, 17)).astype(np.float32)
+    pts = np.stack([rng.integers(-2, W + 2, n), rng.integers(-2, H + 2, n), np.ones(n)], -1).astype(np.float32)
+    pts[:4] = [[0, 0, 1], [W - 1, H - 1, 1], [W - 1, 0, 1], [0, H - 1, 1]]
+    pts[4:200, :2] += rng.uniform(-0.5, 0.5, size=(196, 2)).astype(np.float32)
+    pts[200:230, 2] = [-1.0] * 10 + [0.0] * 10 + [2.0] * 10                                        # behind the camera, on its plane, farther away
+    eye4, eye3, zero = np.eye(4, dtype=np.float32), np.eye(3, dtype=np.float32), np.zeros(3, np.float32)
+    f, d, m = ci.point_view_attrs(t(pts), eye4, eye4, zero, eye3, H, W, feat=t(fmap))
+    rf, rd, rm = R.view_attrs(pts, eye4, eye4, zero, eye3, H, W, fmap)
+    assert_bits_equal(m, rm); assert_bits_equal(f, rf); assert_bits_equal(d, rd)
+    assert 0 < int(rm.sum()) < n and rm[:4].all()
+
+
+def test_torch_ops_equal_the_ctypes_path(gold, tie_case):
+    from hybridneuralrendering_amd import cloud_init as ci, torch_ops
+    xyz, pos, d = tie_case
+    a = torch_ops.nearest_view(t(pos), t(d), t(xyz))
+    b = ci.nearest_view(t(pos), t(d), t(xyz))
+    assert a.dtype == b.dtype and torch.equal(a, b)
+    H, W = gold["at_image"].shape[1:]
+    (f, dr, m), cpc = _attrs(gold, gold["at_fmap"])
+    f2, d2, m2 = torch_ops.point_view_attrs(t(gold["at_xyz"]), gold["at_w2c"], gold["at_c2w"], cpc, gold["at_K"], H, W, t(gold["at_fmap"]))
+    assert_bits_equal(f2, f); assert_bits_equal(d2, dr); assert_bits_equal(m2, m)
+    f3, d3, m3 = torch_ops.point_view_attrs(t(gold["at_xyz"]), gold["at_w2c"], gold["at_c2w"], cpc, gold["at_K"], H, W)                 # no map: direction and mask only
+    assert tuple(f3.shape) == (gold["at_xyz"].shape[0], 0)
+    assert_bits_equal(d3, dr); assert_bits_equal(m3, m)
+
+
+def test_init_cloud_from_depth_end_to_end(gold):
+    """frames -> fused, cropped, thinned cloud -> views -> attributes; every stage against the restatement chained the same way; the result is
+    accepted by NeuralPoints.set_points and renders."""
+    from types import SimpleNamespace
+    from hybridneuralrendering_amd import cloud_init as ci, scenes
+    from hybridneuralrendering_amd._lib import HnrError
+    from hybridneuralrendering_amd.aggregator import PointAggregator
+    from hybridneuralrendering_amd.modules import NeuralPoints
+    from hybridneuralrendering_amd.render import HybridRenderer, PointCloud
+    from oracle import voxel_oracle as vo
+    sc = scenes.make_scene("scene0241", 2000, 2, w=64, h=48)
+    opt = sc.opt
+    opt.ranges, opt.vox_res, opt.depth_intrinsic, opt.default_conf, opt.resample_pnts = [float(r) for r in gold["ranges"]], 120, gold["depth_intrinsic"], 0.15, 0
+    opt.feature_init_method, opt.load_points = "rand", 0
+    frames = [(gold["frames"][i], gold["poses"][i]) for i in range(5)]
+    campos, camdir = gold["nv_campos5"], gold["nv_camdir5"]
+    Kv = gold["at_K"]
+    rng = np.random.default_rng(1)
+    images = rng.uniform(0, 1, size=(5, 3, 48, 64)).astype(np.float32)
+    c2ws = [gold["poses"][i % 4] for i in range(5)]
+    asked = []
+
+    def view_frame(v):
+        asked.append(v)
+        return dict(image=t(images[v]), c2w=c2ws[v], intrinsic=Kv)
+    out = ci.init_cloud_from_depth(frames, opt, t(campos), t(camdir), view_frame)
+    # the same chain in the restatement
+    Ki = gold["depth_intrinsic_inv"]
+    fused = np.concatenate([R.fuse_frame(d, Ki, p, 100) for d, p in frames])
+    crop = R.range_crop(fused, gold["ranges"])
+    _, _, midx, _, _ = vo.construct_vox_points_closest(crop, 120)
+    sel = crop[midx]
+    view = R.nearest_view(sel, campos, camdir)
+    order = np.argsort(view, kind="stable")
+    assert_bits_equal(out["xyz"], sel[order])
+    np.testing.assert_array_equal(out["view_of_point"].cpu().numpy(), view[order])
+    assert asked == sorted(set(view.tolist())) and len(asked) > 1
+    n = sel.shape[0]
+    col, pdir = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
+    for v in asked:
+        rows = np.flatnonzero(view[order] == v)
+        w2c = torch.inverse(torch.from_numpy(c2ws[v])).numpy()
+        c, d, _ = R.view_attrs(sel[order][rows], w2c, c2ws[v], ci.cam_pos_cam(c2ws[v], w2c), Kv, 48, 64, images[v])
+        col[rows], pdir[rows] = c, d
+    assert_bits_equal(out["color"][0], col); assert_bits_equal(out["dir"][0], pdir)
+    assert tuple(out["embedding"].shape) == (1, n, opt.point_features_dim) and tuple(out["conf"].shape) == (1, n, 1) and torch.all(out["conf"] == np.float32(0.15))
+    opt.resample_pnts = 5
+    with pytest.raises(HnrError):
+        ci.init_cloud_from_depth(frames, opt, t(campos), t(camdir), view_frame)
+    opt.resample_pnts, opt.default_conf = 0, -1.0
+    # NeuralPoints takes it, and a camera at the first depth pose sees it
+    npts = NeuralPoints(opt.point_features_dim, n, opt, torch.device(DEV))
+    npts.set_points(out["xyz"], out["embedding"], points_color=out["color"], points_dir=out["dir"], points_conf=out["conf"])
+    assert npts.xyz.shape == (n, 3) and npts.points_embeding.shape == (1, n, opt.point_features_dim)
+    torch.manual_seed(0)
+    agg = PointAggregator(opt).to(DEV)
+    rnd = HybridRenderer(opt, agg, DEV)
+    cloud = PointCloud(npts.xyz, npts.points_embeding, npts.points_conf, npts.points_dir, npts.points_color)
+    K64 = gold["depth_intrinsic"][:3, :3].copy()
+    K64[:2] /= 10.0
+    pose = gold["poses"][0]
+    rays = scenes.camera_rays(scenes.pixel_grid(64, 48), K64, pose)
+    o = rnd.render_rays(cloud, t(rays), t(pose[:3, 3]), t(pose[:3, :3]), t(sc.bg_color), 0.5, 4.0, t(sc.c2w_nearest), t(sc.c2w_nearest[:, :3, 3]),
+                        t(sc.intrinsic), t(sc.images_nearest))
+    assert tuple(o["coarse_raycolor"].shape) == (rays.shape[0], 3) and torch.isfinite(o["coarse_raycolor"]).all()
+    assert int((o["ray_mask"] > 0).sum()) > 0
