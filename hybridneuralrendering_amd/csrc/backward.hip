@@ -482,22 +482,32 @@ __device__ __forceinline__ void upsample_bwd_body(int64_t block, const float *__
     int xlo = xs == 0 ? 0 : (int)floorf(hnr_div((float)xs - 0.5f, sx) - 0.5f) - 1, xhi = (int)ceilf(hnr_div((float)xs + 1.5f, sx) - 0.5f) + 1;
     ylo = ylo < by0 ? by0 : ylo; yhi = yhi > by1 + 1 ? by1 + 1 : yhi;
     xlo = xlo < bx0 ? bx0 : xlo; xhi = xhi > bx1 + 1 ? bx1 + 1 : xhi;
+    // The weights in exact integer arithmetic: the source coordinate of destination row y is q = ((2 y + 1) Hs - H) / (2 H), clamped up to 0; with
+    // q = y0 + r / (2 H) the two taps weigh (2 H - r) / (2 H) and r / (2 H).  Numerators below 2^24 are exact in float32, so every weight carries a
+    // RELATIVE error of 2^-23 however small it is.  (The float32 form of the forward, (y + 0.5) sy - 0.5, rounds at the magnitude of q: an absolute
+    // error of q 2^-24 in a weight, 8 x the summation error of a level-1 cell on a 37-row image and growing with the image --
+    // tests/test_image_branch_gpu.py holds a cell to (n + 4) 2^-23 sum |w g|.)
+    const int deny = 2 * H, denx = 2 * W;
+    const float ideny = hnr_div(1.f, (float)deny), idenx = hnr_div(1.f, (float)denx);
     float acc = 0.f;
     for (int y = ylo; y < yhi; ++y) {
-        float qy = ((float)y + 0.5f) * sy - 0.5f;
-        if (qy < 0.f) qy = 0.f;
-        const int y0 = (int)qy, y1 = y0 + (y0 < Hs - 1 ? 1 : 0);
-        const float ly = qy - (float)y0;
-        const float wy = (y0 == ys ? 1.f - ly : 0.f) + (y1 == ys ? ly : 0.f);
-        if (wy == 0.f) continue;
+        int ny = (2 * y + 1) * Hs - H;
+        if (ny < 0) ny = 0;
+        int y0 = (int)((float)ny * ideny), ry = ny - y0 * deny;                       // (the estimate is off by one at most)
+        if (ry < 0) { --y0; ry += deny; } else if (ry >= deny) { ++y0; ry -= deny; }
+        const int y1 = y0 + (y0 < Hs - 1 ? 1 : 0);
+        const int wyi = (y0 == ys ? deny - ry : 0) + (y1 == ys ? ry : 0);
+        if (wyi == 0) continue;
+        const float wy = (float)wyi * ideny;
         for (int x = xlo; x < xhi; ++x) {
-            float qx = ((float)x + 0.5f) * sx - 0.5f;
-            if (qx < 0.f) qx = 0.f;
-            const int x0 = (int)qx, x1 = x0 + (x0 < Ws - 1 ? 1 : 0);
-            const float lx = qx - (float)x0;
-            const float wx = (x0 == xs ? 1.f - lx : 0.f) + (x1 == xs ? lx : 0.f);
-            if (wx == 0.f) continue;
-            acc += wy * wx * g_fm[(((size_t)v * H + y) * W + x) * 48 + c0 + cl];
+            int nx = (2 * x + 1) * Ws - W;
+            if (nx < 0) nx = 0;
+            int x0 = (int)((float)nx * idenx), rx = nx - x0 * denx;
+            if (rx < 0) { --x0; rx += denx; } else if (rx >= denx) { ++x0; rx -= denx; }
+            const int x1 = x0 + (x0 < Ws - 1 ? 1 : 0);
+            const int wxi = (x0 == xs ? denx - rx : 0) + (x1 == xs ? rx : 0);
+            if (wxi == 0) continue;
+            acc += wy * ((float)wxi * idenx) * g_fm[(((size_t)v * H + y) * W + x) * 48 + c0 + cl];
         }
     }
     g_level[(((size_t)v * C + cl) * Hs + ys) * Ws + xs] = acc;
@@ -1110,6 +1120,15 @@ int image_features_bwd_bbox(const float *d_img, int V, int H, int W, const float
 {
     return image_features_bwd_impl(d_img, V, H, W, conv_w, slope, d_scratch, d_g_pyramid, g_conv_w, g_conv_b, d_bbox, stream);
 }
+}
+
+// the same as a STAGE-tier export (include/hnr.h): tests/test_image_branch_gpu.py drives the clipped form alone, at image sizes where tiles are skipped
+extern "C" int hnr_image_features_bwd_bbox(const float *d_img, int V, int H, int W, const float *const *conv_w, float slope,
+                                           const float *d_scratch, float *d_g_pyramid, float *const *g_conv_w, float *const *g_conv_b,
+                                           const int32_t *d_bbox, void *stream)
+{
+    if (!d_bbox) { set_error("hnr_image_features_bwd_bbox: NULL d_bbox (hnr_image_features_bwd is the unclipped form)"); return HNR_ERR_BADARG; }
+    return image_features_bwd_impl(d_img, V, H, W, conv_w, slope, d_scratch, d_g_pyramid, g_conv_w, g_conv_b, d_bbox, stream);
 }
 
 static int image_features_bwd_impl(const float *d_img, int V, int H, int W, const float *const *conv_w, float slope,

@@ -25,7 +25,7 @@
  *              hnr_shipped_loss*, hnr_composite, hnr_ray_depth, hnr_ray_march, hnr_voxel_downsample*, hnr_probe_select, hnr_blur_*,
  *              hnr_frame_metrics* (and the HNR_FM_* row layout), hnr_depth_fuse*, hnr_range_crop*, hnr_nearest_view, hnr_point_view_attrs.
  *   STAGE   -- everything else (hnr_chain_*, hnr_mlp3_*, hnr_merge*, hnr_mixup_stage, hnr_proj_*, hnr_h2*, hnr_linear_*, hnr_gather_*, hnr_ksum*,
- *              hnr_segment_*, hnr_absmax, hnr_div_probe, ...): the individual stages the two single-call entries are built from.  They are exported so
+ *              hnr_segment_*, hnr_absmax, hnr_div_probe, hnr_image_features_bwd_bbox, ...): the individual stages the two single-call entries are built from.  They are exported so
  *              that tests/ can compare every stage with the oracle and so that tools/ can time them alone; their signatures, workspace layouts and
  *              packed-image formats follow the kernels and MAY CHANGE from one version to the next (round 4 changed what hnr_chain_forward leaves
  *              in the workspace's row scalars, for example).  Do not bind to them from outside this repository.
@@ -522,6 +522,14 @@ int hnr_segment_sum_rows(const float *d_A, int lda, const float *d_B, int ldb, c
 int hnr_image_features_bwd(const float *d_img, int V, int H, int W, const float *const *conv_w, float slope,
                            const float *d_scratch, float *d_g_pyramid, float *const *g_conv_w, float *const *g_conv_b,
                            void *stream);
+/* Test hook: the form the training step runs (csrc/render_train.hip).  d_bbox int32[V,4] = the per-view rectangle of touched pixels {min x, min y, max x,
+ * max y} as hnr_proj_rows_bwd leaves it ({W, H, -1, -1}: view untouched); every convolution tile outside the rectangle's image at its level, dilated by
+ * 30 / 14 / 6 cells at resolution divisor 2 / 4 / 8, is skipped.  d_g_pyramid MUST BE ZERO outside what hnr_proj_rows_bwd wrote: a skipped tile does
+ * not write its share of the input gradients, and the tiles that run add to what is there.  Same results as hnr_image_features_bwd up to the order of
+ * the atomic weight-gradient sums (tests/test_image_branch_gpu.py). */
+int hnr_image_features_bwd_bbox(const float *d_img, int V, int H, int W, const float *const *conv_w, float slope,
+                                const float *d_scratch, float *d_g_pyramid, float *const *g_conv_w, float *const *g_conv_b,
+                                const int32_t *d_bbox, void *stream);
 
 /* NeuralPoints gather (neural_points.py:709-720), block3 extras (:957-971), conf straight-through clamp (:1422-1424, :1508-1512) transposed:
  * d_gX3[:, 256:263], d_g_wagg, optional d_g_conf_out [R,SR,K] (gradient of the conf_coefficient output) -> per-row contributions

@@ -1,0 +1,750 @@
+"""The reference-view ("image") branch at view counts other than 4 and under bounding-box clipping, stage by stage through the C ABI against float64
+restatements (tests/image_branch_ref.py; its inputs are checked without a GPU in tests/test_image_branch.py), then as a whole at V = 1, 3, 6, 8:
+
+ * hnr_proj_pixels / hnr_proj_rows (both layouts): pixels, masks and gathered features exactly, delta view directions to 8 x 2^-24;
+ * hnr_merge: frame weights (a zero among them), dropped rays, samples masked in every view; zero-weight views change no bit;
+ * hnr_proj_rows_bwd: bounding boxes exactly, the pixel scatter and the transposed bilinear upsample with per-element bounds, V up to 9;
+ * hnr_image_features_bwd_bbox: the clipped CNN backward on a 203 x 301 image where most tiles ARE skipped, against float64 autograd through the
+   whole chain and beside the unclipped form;
+ * hnr_render_forward / render_train with 1, 3, 6 and 8 reference views against the CPU oracle.
+
+Physical rows differ from logical ones throughout (cap_samples = n_valid + 13); everything beyond the device count is NaN on the way in and a
+sentinel on the way out.
+
+Values recorded on an MI355X (profiles/image_branch_tests.txt):
+  pixels: 0 of 52 table rows and 0 of 38 692 generated (view, sample) rows differ from the float64 restatement; delta view direction: max 2.89e-7
+  (bound 4.77e-7); hnr_merge, 48 runs: e32 up to 6.19e-7, error up to 1.02e-6, at most 3.86 x e32 and 0.79 of the bound;
+  hnr_proj_rows_bwd, 30 runs: scatter error at most 0.50 of its bound, upsample at most 0.12 of its bound (with the float32 coordinate weights the
+  kernel had before this module: 8 x the bound at level 1 of a 37 x 51 image); clipped CNN backward: 3.6e-7 .. 7.6e-7 x max|ref| per tensor
+  (unclipped 3.6e-7 .. 6.8e-7; bound 2e-5);
+  render at V = 1 / 3 / 6 / 8: 5 686 valid samples, 0 on another pixel than float64, max |d colour| 2.4e-7, max |d opacity| 3.0e-7, PSNR 144 dB;
+  training at V = 1 / 3 / 8: loss terms within 8e-8 relative; point gradients 6.2e-4 x max off the float32 oracle and 5.7e-7 off its float64 run,
+  weight gradients 3.6e-5 / 9.6e-7; at V = 1 the eight aux_merge_weight_block gradients (1e-9: the 1e-6 residue) 2.1e-3 .. 2.4e-3 off float64 where
+  the oracle's own float32 run is 2.6e-3 off.
+"""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+from tests import image_branch_ref as ib
+
+pytestmark = pytest.mark.gpu
+
+CNT_VALID = 6                                       # HNR_CNT_SAMPLES_VALID (include/hnr.h)
+PAD = 13                                            # cap_samples - n_valid
+SENT_F = -7.25                                      # sentinel of float outputs
+SENT_I = 0x5A5A5A5A
+U23 = 2.0 ** -23
+CAMPOS = np.array([0.3, -0.2, 0.1], np.float32)
+
+
+def _dev():
+    return torch.device("cuda:0")
+
+
+def _t(a, dtype=None):
+    x = torch.as_tensor(np.ascontiguousarray(a) if isinstance(a, np.ndarray) else a)
+    if dtype is not None:
+        x = x.to(dtype)
+    return x.to(_dev()).contiguous()
+
+
+def _sample_buffers(xyz, seed):
+    """World positions [n,3] -> (loc_w [n + 7, 3] with the samples at permuted items and NaN elsewhere, vs_item [n + PAD] whose entries beyond n
+    point at a NaN item, counts).  Logical sample s lives at item vs_item[s]."""
+    n = xyz.shape[0]
+    rng = np.random.default_rng(seed + 5)
+    items = rng.permutation(n + 7)[:n].astype(np.int32)
+    spare = int(np.setdiff1d(np.arange(n + 7), items)[0])
+    loc = np.full((n + 7, 3), np.nan, np.float32)
+    loc[items] = xyz
+    vs = np.full((n + PAD,), spare, np.int32)
+    vs[:n] = items
+    counts = np.zeros((16,), np.int64)
+    counts[CNT_VALID] = n
+    return _t(loc), _t(vs), _t(counts)
+
+
+def _rows(V, n):
+    """Physical row of (view, sample): v * cap + s."""
+    return (torch.arange(V)[:, None] * (n + PAD) + torch.arange(n)[None, :]).to(_dev())
+
+
+def _beyond(V, n):
+    cap = n + PAD
+    m = torch.ones((V * cap,), dtype=torch.bool)
+    m[_rows(V, n).cpu().reshape(-1)] = False
+    return m.to(_dev())
+
+
+def _random_featmap(V, H, W, seed):
+    fm = torch.randn((V, H, W, 48), generator=torch.Generator().manual_seed(seed))
+    fm[..., 45:] = 0
+    fm[:, 0, 0, :] = 0                                # hnr_image_features zeroes pixel (0,0): what a masked row gathers
+    return fm
+
+
+_SET_IDS = ["edge"] + ["V%d_n%d_%dx%d" % (V, n, H, W) for V, n, (H, W) in ib.FWD_CASES]
+
+
+def _input_set(name):
+    """(V, n, H, W, views, xyz, expected pixels [V,n,2]) of a forward-stage case: the hand-built table or a generated case."""
+    if name == "edge":
+        e = ib.edge_samples()
+        return 2, e["xyz"].shape[0], e["H"], e["W"], e, e["xyz"], e["expect"]
+    V, n, (H, W) = ib.FWD_CASES[_SET_IDS.index(name) - 1]
+    seed = ib.case_seed(V, n, (H, W))
+    views = ib.make_views(seed, V, H, W)
+    xyz = ib.random_samples(seed, n, views, H, W)
+    return V, n, H, W, views, xyz, ib.restated_pixels(xyz, views["w2c"], views["intrinsic"], H, W)
+
+
+# ================================================================================================ forward stages
+@pytest.mark.parametrize("name", _SET_IDS)
+def test_projection_and_gather_match_the_fp64_restatement(name):
+    from hybridneuralrendering_amd import _lib
+    V, n, H, W, views, xyz, want = _input_set(name)
+    L, p = _lib.lib(), _lib.ptr
+    cap = n + PAD
+    # the float64 restatement (with the reference's float32 rounding of `depth + 1e-10`, visible only on the hand-built integer coordinates)
+    assert torch.equal(ib.restated_pixels(xyz, views["w2c"], views["intrinsic"], H, W, torch.float64, den32=True), want)
+    loc, vs, counts = _sample_buffers(xyz, n)
+    w2c, K, cn, cp = _t(views["w2c"]), _t(views["intrinsic"]), _t(views["campos_n"]), _t(CAMPOS)
+    rows, beyond = _rows(V, n), _beyond(V, n)
+    # ---- hnr_proj_pixels
+    pix = torch.full((V * cap, 2), SENT_I, dtype=torch.int32, device=_dev())
+    _lib.check(L.hnr_proj_pixels(p(loc), p(vs), p(counts), p(w2c), p(K), V, H, W, cap, p(pix), _lib.stream()), "hnr_proj_pixels")
+    got = pix[rows].cpu().long()
+    flips = int((got != want).any(-1).sum())
+    print("%s: hnr_proj_pixels rows that differ from the restatement: %d of %d" % (name, flips, V * n))
+    assert flips == 0, [(v, s, got[v, s].tolist(), want[v, s].tolist()) for v, s in (got != want).any(-1).nonzero().tolist()][:8]
+    assert bool((pix[beyond] == SENT_I).all())
+    # ---- hnr_proj_rows, both layouts
+    valid = want[..., 0] >= 0
+    px, py = want[..., 0].clamp(min=0), want[..., 1].clamp(min=0)                      # masked rows read the zeroed pixel (0,0)
+    fm = _random_featmap(V, H, W, n)
+    want_f = fm[torch.arange(V)[:, None], py, px][..., :45]                            # [V,n,45]
+    dd64 = ib.delta_dirs(xyz, CAMPOS, views["campos_n"])                               # [V,n,3]
+    CF = torch.full((cap, 128), float("nan"))
+    CF[:n] = torch.randn((n, 128), generator=torch.Generator().manual_seed(n + 1))
+    fmd, CFd = _t(fm), _t(CF)
+    for split in (True, False):
+        ld6 = 48 if split else 176
+        X6 = torch.full((V * cap, ld6), SENT_F, device=_dev())
+        vm = torch.full((V * cap,), SENT_F, device=_dev())
+        rs = torch.full((V * cap,), SENT_I, dtype=torch.int32, device=_dev())
+        _lib.check(L.hnr_proj_rows(p(loc), p(vs), p(counts), p(w2c), p(K), p(cp), p(cn), p(fmd), V, H, W, p(CFd), 128, cap, p(X6), ld6, p(vm),
+                                   p(rs) if split else None, _lib.stream()), "hnr_proj_rows")
+        x6 = X6[rows].cpu()
+        assert torch.equal(vm[rows].cpu(), valid.float()), (name, split)
+        assert torch.equal(x6[..., :45], want_f), (name, split)                        # a copy: bit-equal
+        dcol = 45 if split else 173
+        # Delta view direction nea - cur, each a quotient c_i / (|c| + 1e-6) of float32 operations that are each correctly rounded (u = 2^-24):
+        # c = x - campos <= u; |c|^2 = three squares (2 u + u each) and two additions of non-negative terms <= 5 u; the root halves it and rounds
+        # <= 3.5 u; + 1e-6 <= 4.5 u; the quotient <= u + 4.5 u + u = 6.5 u of a value of at most 1; two quotients and the subtraction (<= u of a
+        # value of at most 2): <= 15 u to first order if every rounding were at its maximum with the sign that hurts.  The ~20 roundings are
+        # independent; the bound is 8 u = 8 x 2^-24, about five times their root sum of squares.
+        err = float((x6[..., dcol:dcol + 3].double() - dd64).abs().max())
+        print("%s split=%d: max |ddir - fp64| = %.3e  (bound %.3e)" % (name, split, err, 8 * 2.0 ** -24))
+        assert err <= 8 * 2.0 ** -24, (name, split, err)
+        if split:
+            assert torch.equal(rs[rows].cpu().long(), torch.arange(n)[None, :].expand(V, n)), name
+            assert bool((rs[beyond] == SENT_I).all())
+        else:
+            assert torch.equal(x6[..., 45:173], CF[:n][None].expand(V, n, 128)), name  # the copied colour feature: bit-equal
+            assert bool((rs == SENT_I).all())
+        assert bool((X6[beyond] == SENT_F).all()) and bool((vm[beyond] == SENT_F).all()), (name, split)
+
+
+def _merge_inputs(V, n, seed, mask_all_every=7):
+    cap = n + PAD
+    g = torch.Generator().manual_seed(seed)
+    nan = float("nan")
+    X6 = torch.full((V * cap, 48), nan)
+    Hm = torch.full((V * cap, 64), nan)
+    vm = torch.full((V * cap,), nan)
+    CF = torch.full((cap, 128), nan)
+    rows = _rows(V, n).cpu()
+    X6[rows] = torch.randn((V, n, 48), generator=g)
+    Hm[rows] = torch.randn((V, n, 64), generator=g)
+    m = (torch.rand((V, n), generator=g) > 0.3).float()
+    m[:, 3::mask_all_every] = 0                                                       # samples masked in every view
+    vm[rows] = m
+    CF[:n] = torch.randn((n, 128), generator=g)
+    w_last = torch.randn(64, generator=g) * 0.3
+    b_last = torch.randn(1, generator=g) * 0.1
+    return dict(X6=X6, Hm=Hm, vm=vm, CF=CF, w=w_last, b=b_last, rows=rows, mask=m)
+
+
+def _run_merge(V, n, a, frame_w=None, ray_drop=None, vs_item=None, SR=0):
+    from hybridneuralrendering_amd import _lib
+    L, p = _lib.lib(), _lib.ptr
+    cap = n + PAD
+    counts = np.zeros((16,), np.int64)
+    counts[CNT_VALID] = n
+    X7 = torch.full((cap, 92), SENT_F, device=_dev())
+    keep = [_t(a[k]) for k in ("X6", "Hm", "w", "b", "vm", "CF")] + [_t(counts)]
+    fw = _t(frame_w) if frame_w is not None else None
+    rd = _t(ray_drop) if ray_drop is not None else None
+    vs = _t(vs_item) if vs_item is not None else None
+    X6, Hm, w, b, vm, CF, cnt = keep
+    _lib.check(L.hnr_merge(p(X6), 48, p(Hm), 64, p(w), p(b), p(vm), p(fw), p(CF), 128, p(cnt), V, cap, p(X7), 92, p(rd), p(vs), SR, _lib.stream()), "hnr_merge")
+    out = X7.cpu()
+    assert bool((out[n:] == SENT_F).all()) and bool((out[:n, 90:] == SENT_F).all())   # nothing beyond the count, nothing beyond column 90
+    assert torch.equal(out[:n, :45], a["CF"][:n, :45])                                # X7[:, :45] is the colour feature, always
+    return out[:n, 45:90]
+
+
+@pytest.mark.parametrize("V", ib.FWD_V)
+@pytest.mark.parametrize("n", ib.FWD_N)
+def test_merge_matches_the_fp64_formula(V, n):
+    a = _merge_inputs(V, n, 1000 * V + n)
+    rows = a["rows"]
+    f, hm, m = a["X6"][rows][..., :45], a["Hm"][rows], a["mask"]
+    g = torch.Generator().manual_seed(n)
+    fw = torch.rand(V, generator=g) + 0.5
+    fw[V // 2] = 0.0                                                                  # a zero frame weight
+    SR = 3
+    n_rays = (n + 7 + SR - 1) // SR + 1
+    vs_item = np.full((n + PAD,), 0, np.int32)
+    vs_item[:n] = np.sort(np.random.default_rng(n).permutation(n + 7)[:n])
+    drop = (torch.rand(n_rays, generator=g) < 0.3).to(torch.uint8)
+    drop[int(vs_item[0]) // SR] = 1
+    dropped = drop[torch.from_numpy(vs_item[:n]).long() // SR].bool()
+    for use_fw in (False, True):
+        for use_drop in (False, True):
+            ref64 = ib.merge_ref(f, hm, a["w"], a["b"], m, fw if use_fw else None, torch.float64)
+            ref32 = ib.merge_ref(f, hm, a["w"], a["b"], m, fw if use_fw else None, torch.float32)
+            e32 = float((ref32.double() - ref64).abs().max())
+            got = _run_merge(V, n, a, fw if use_fw else None, drop if use_drop else None, vs_item if use_drop else None, SR if use_drop else 0)
+            if use_drop:
+                assert bool(dropped.any()) and bool((got[dropped] == 0).all())        # dropped rays: exactly 0
+                ref64 = torch.where(dropped[:, None], torch.zeros_like(ref64), ref64)
+            err = float((got.double() - ref64).abs().max())
+            # the same formula in float32 on the CPU errs by e32; another order of the 64-term dot product and of the V-term sums: factor 4
+            print("hnr_merge V=%d n=%d frame_w=%d drop=%d: e32 = %.3e  max |got - fp64| = %.3e  (bound %.3e)" % (V, n, use_fw, use_drop, e32, err, 4 * e32 + 1e-7))
+            assert err <= 4 * e32 + 1e-7, (V, n, use_fw, use_drop, err, e32)
+            none = (m * (fw[:, None] if use_fw else 1.0)).sum(0) == 0                 # masked (or weighted 0) in every view: exactly 0
+            assert (bool(none.any()) or n < 4) and bool((got[none] == 0).all())
+
+
+@pytest.mark.parametrize("V,n", [(8, 1100), (8, 37), (5, 1100), (5, 37), (5, 1)])
+def test_zero_weight_views_change_no_bit(V, n):
+    """V = 8 with frame_w = [1,1,1,1,0,0,0,0] and V = 5 with the last weight 0 against V = 4 with unit weights on the same first four views: adding
+    f x 0 and 0 is exact, so X7 is equal bit for bit -- which pins the v * cap row stride, the frame-weight index and the tail of the 4-view batches."""
+    a = _merge_inputs(V, n, 77 * V + n)
+    cap = n + PAD
+    a4 = dict(a, X6=a["X6"][:4 * cap].clone(), Hm=a["Hm"][:4 * cap].clone(), vm=a["vm"][:4 * cap].clone())
+    fw = torch.tensor([1.0] * 4 + [0.0] * (V - 4))
+    want = _run_merge(4, n, a4, torch.ones(4))
+    assert torch.equal(want, _run_merge(4, n, a4, None))
+    got = _run_merge(V, n, a, fw)
+    assert float(a["X6"][a["rows"]][4:].abs().min()) > 0                               # the zero-weight views carry features
+    assert torch.equal(got, want)
+    assert not torch.equal(_run_merge(V, n, a, None), want) or n == 1                 # (with their weights on, they do change the result)
+
+
+# ================================================================================================ backward of the gather and the upsample
+def _bbox_of(pix, keep, V, H, W):
+    out = []
+    for v in range(V):
+        k = keep[v]
+        if not bool(k.any()):
+            out.append([W, H, -1, -1])
+        else:
+            x, y = pix[v, k, 0], pix[v, k, 1]
+            out.append([int(x.min()), int(y.min()), int(x.max()), int(y.max())])
+    return torch.tensor(out, dtype=torch.int32)
+
+
+def _proj_rows_bwd(xyz, w2c, K, V, H, W, gA, gB, seed):
+    """Runs hnr_proj_rows_bwd on [V,n,lda] / [V,n,48] rows placed at their physical rows (NaN beyond the count).
+    Returns (g_featmap [V,H,W,48], bbox [V,4], g_pyramid flat) on the host."""
+    from hybridneuralrendering_amd import _lib
+    L, p = _lib.lib(), _lib.ptr
+    n = xyz.shape[0]
+    cap = n + PAD
+    lda = gA.shape[-1]
+    loc, vs, counts = _sample_buffers(xyz, seed)
+    rows = _rows(V, n).cpu()
+    A = torch.full((V * cap, lda), float("nan"))
+    A[rows] = gA
+    B = None
+    if gB is not None:
+        B = torch.full((V * cap, 48), float("nan"))
+        B[rows] = gB
+    Ad, Bd = _t(A), (_t(B) if B is not None else None)
+    gfm = torch.zeros((V, H, W, 48), device=_dev())
+    bbox = torch.tensor([[W, H, -1, -1]] * V, dtype=torch.int32, device=_dev())
+    gpyr = torch.zeros((int(L.hnr_image_features_scratch_elems(V, H, W)),), device=_dev())
+    keys = torch.full((3 * V * cap,), SENT_I, dtype=torch.int32, device=_dev())
+    nsort = max(int(L.hnr_sort_rows_scratch_bytes(V * cap)), 256)
+    sort = torch.zeros((nsort,), dtype=torch.uint8, device=_dev())
+    w2cd, Kd = _t(w2c), _t(K)
+    _lib.check(L.hnr_proj_rows_bwd(p(loc), p(vs), p(counts), p(w2cd), p(Kd), V, H, W, cap, p(Ad), lda, p(Bd), 48, p(gfm), p(bbox), p(gpyr), p(keys),
+                                   p(sort), nsort, _lib.stream()), "hnr_proj_rows_bwd")
+    torch.cuda.synchronize()
+    return gfm.cpu(), bbox.cpu(), gpyr.cpu(), (loc, vs, counts, gpyr, bbox)
+
+
+def _check_proj_rows_bwd(name, xyz, w2c, K, V, H, W, gA, gB, seed, pix=None):
+    n = xyz.shape[0]
+    if pix is None:
+        pix = ib.restated_pixels(xyz, w2c, K, H, W)
+    gfm, bbox, gpyr, _ = _proj_rows_bwd(xyz, w2c, K, V, H, W, gA, gB, seed)
+    ref, ref_abs, cnt, keep = ib.scatter_rows(gA[..., :48], pix, V, H, W)
+    if gB is not None:
+        r2, a2, _, _ = ib.scatter_rows(gB, pix, V, H, W)
+        ref, ref_abs = ref + r2, ref_abs + a2
+    # ---- bounding boxes: exactly the min / max of the restated pixels that receive a gradient
+    assert torch.equal(bbox, _bbox_of(pix, keep, V, H, W)), (name, bbox.tolist())
+    # ---- pixel scatter: m rows (2 m terms with the second source) added in float32 in any order: |error| <= m 2^-23 sum |terms|
+    err = (gfm.double() - ref).abs()
+    bound = cnt[..., None] * U23 * ref_abs
+    ratio = float((err / bound.clamp(min=1e-300)).max()) if bool((bound > 0).any()) else 0.0
+    assert bool((err <= bound).all()), (name, ratio)
+    assert float(gfm[:, 0, 0].abs().max()) == 0.0                                      # pixel (0,0) gets no gradient
+    # ---- transposed upsample: a cell sums at most n = (2 ceil(H / Hs) + 1)^2 products w g: |error| <= (n + 4) 2^-23 sum |w g|
+    # The kernel upsamples ITS OWN g_featmap, which may differ from the float64 one by the scatter bound above (two rows that cancel in a pixel leave
+    # a rounding error far above 2^-23 |g|): that allowance passes through the same non-negative weights and is added to the cell's bound.
+    lv, lv_abs, lv_in = ib.level_grads(ref, H, W), ib.level_grads(ref.abs(), H, W), ib.level_grads(bound, H, W)
+    sizes = ib.pyramid_sizes(H, W)
+    off, worst = 0, []
+    for (c0, C), (Hs, Ws), r, ra, rin in zip(ib.LEVEL_CH, sizes, lv, lv_abs, lv_in):
+        nel = V * C * Hs * Ws
+        assert float(gpyr[off:off + nel].abs().max()) == 0.0, (name, "the first-activation slot of a level is not this kernel's to write")
+        got = gpyr[off + nel:off + 2 * nel].view(V, C, Hs, Ws).double()
+        nterm = (2 * -(-H // Hs) + 1) ** 2
+        # (+ the reference's own error: torch computes its float64 weights from a coordinate of magnitude < 2^10, so a weight is off by up to 2^-42 --
+        # where the exact weight is 0 the reference holds 1e-16 x g and the kernel, whose weights are exact integers over 2 H, holds 0)
+        b = (nterm + 4) * U23 * ra + rin + nterm * 2.0 ** -41 * float(ref.abs().max())
+        e = (got - r).abs()
+        worst.append(float((e / b.clamp(min=1e-300)).max()) if bool((b > 0).any()) else 0.0)
+        bad = e > b
+        assert not bool(bad.any()), (name, "level %dx%d" % (Hs, Ws), int(bad.sum()), worst[-1], [(i, float(e[tuple(i)]), float(b[tuple(i)])) for i in bad.nonzero().tolist()[:4]])
+        off += 2 * nel
+    assert off == gpyr.numel()
+    print("%s: bbox ok; scatter max err / bound %.3f; upsample max err / bound per level %s" % (name, ratio, ", ".join("%.3f" % w for w in worst)))
+    return bbox, keep
+
+
+@pytest.mark.parametrize("V,n,hw,two", ib.BWD_CASES, ids=["V%d_n%d_%dx%d_%s" % (V, n, hw[0], hw[1], "ab" if two else "a") for V, n, hw, two in ib.BWD_CASES])
+def test_gather_and_upsample_backward_match_fp64_autograd(V, n, hw, two):
+    H, W = hw
+    seed = ib.case_seed(V, n, hw)
+    views = ib.make_views(seed, V, H, W)
+    xyz = ib.random_samples(seed, n, views, H, W)
+    g = torch.Generator().manual_seed(seed)
+    gA = torch.randn((V, n, 52), generator=g)                                         # lda = 52: columns 48.. are not the kernel's to read
+    gA[..., 48:] = float("nan")
+    gB = torch.randn((V, n, 48), generator=g) if two else None
+    _check_proj_rows_bwd("V%d n%d %dx%d" % (V, n, H, W), xyz, views["w2c"], views["intrinsic"], V, H, W, gA, gB, seed)
+
+
+def _pixel_views(V, dead=()):
+    """Views whose pixel is read off the position: w2c = identity, K = identity, z = 1 -> (fx, fy) = (x, y); a `dead` view looks away (every row masked)."""
+    w2c = np.stack([np.eye(4, dtype=np.float32) for _ in range(V)])
+    for v in dead:
+        w2c[v, 0, 3] = -100000.0
+    return w2c, np.eye(3, dtype=np.float32)
+
+
+def _at_pixels(px, py, seed):
+    rng = np.random.default_rng(seed)
+    px, py = np.asarray(px, np.float64), np.asarray(py, np.float64)
+    return np.stack([px + rng.uniform(0.2, 0.8, size=px.shape), py + rng.uniform(0.2, 0.8, size=py.shape), np.ones_like(px)], axis=-1).astype(np.float32)
+
+
+PLACEMENTS = ["top_left", "top_right", "bottom_left", "bottom_right", "middle", "one_pixel_all_samples", "dead_view"]
+
+
+@pytest.mark.parametrize("H,W", [(37, 51), (203, 301)])
+@pytest.mark.parametrize("where", PLACEMENTS)
+def test_gather_backward_placement_cases(where, H, W):
+    """A single touched pixel at each corner and in the middle; all samples in ONE pixel (the contention case of the float atomics; rows without
+    cancellation, so that the summation-error bound is met by any order); all rows of one view masked (its box stays {W, H, -1, -1}, its level
+    gradients stay zero)."""
+    V = 3
+    g = torch.Generator().manual_seed(H + len(where))
+    spot = dict(top_left=(1, 0), top_right=(W - 1, 0), bottom_left=(0, H - 1), bottom_right=(W - 1, H - 1), middle=(W // 2, H // 2))
+    if where in spot:
+        # one sample on the pixel, the others on pixel (0,0) (no gradient) or outside the image
+        px = [spot[where][0], 0, -5, W + 3]
+        py = [spot[where][1], 0, 2, 1]
+        dead = ()
+        gA = torch.randn((V, 4, 52), generator=g)
+    elif where == "one_pixel_all_samples":
+        px, py, dead = [W // 3] * 1100, [H // 2] * 1100, ()
+        gA = torch.rand((V, 1100, 52), generator=g) + 0.5
+    else:
+        n = 37
+        rng = np.random.default_rng(H)
+        px, py, dead = rng.integers(0, W, size=n), rng.integers(0, H, size=n), (1,)
+        gA = torch.randn((V, n, 52), generator=g)
+    xyz = _at_pixels(px, py, H)
+    w2c, K = _pixel_views(V, dead)
+    want = torch.tensor(np.stack([np.asarray(px), np.asarray(py)], -1))[None].expand(V, -1, -1).clone().long()
+    want[(want[..., 0] < 0) | (want[..., 0] >= W) | (want[..., 1] < 0) | (want[..., 1] >= H)] = -1
+    for v in dead:
+        want[v] = -1
+    pix = ib.restated_pixels(xyz, w2c, K, H, W)
+    assert torch.equal(pix, want)
+    bbox, keep = _check_proj_rows_bwd("%s %dx%d" % (where, H, W), xyz, w2c, K, V, H, W, gA, None, H, pix=pix)
+    if where in spot:
+        assert bbox.tolist() == [[spot[where][0], spot[where][1]] * 2] * V and int(keep.sum()) == V
+    if where == "dead_view":
+        assert bbox[1].tolist() == [W, H, -1, -1] and int(keep[1].sum()) == 0 and int(keep[0].sum()) > 30
+
+
+# ================================================================================================ clipped CNN backward
+CH = [(3, 6, 2), (6, 6, 1), (6, 12, 2), (12, 12, 1), (12, 24, 2), (24, 24, 1)]
+RECTS = {                                              # (x0, y0, x1, y1) inclusive, in view 0 of a 203 x 301 image; view 1 is untouched
+    "top_left_20x20": (0, 0, 19, 19),
+    "bottom_right_20x20": (301 - 20, 203 - 20, 300, 202),
+    "middle_24x18": (140, 90, 163, 107),
+    "column_3_wide_at_W-2": (301 - 3, 0, 300, 202),
+    "single_pixel": (173, 61, 173, 61),
+}
+
+
+def _cnn_case(H, W, rect, both_views, seed):
+    """Forward scratch by hnr_image_features, rows confined to `rect` through hnr_proj_rows_bwd, then the clipped and the unclipped CNN backward on
+    copies of the same gradient pyramid; float64 autograd through the whole chain in one graph as the reference."""
+    from hybridneuralrendering_amd import _lib
+    L, p = _lib.lib(), _lib.ptr
+    V, slope = 2, 0.01
+    g = torch.Generator().manual_seed(seed)
+    img = torch.rand((V, H, W, 3), generator=g)
+    ws = [torch.randn((co, ci, 3, 3), generator=g) * (1.5 / (ci * 9) ** 0.5) for ci, co, _ in CH]
+    bs = [torch.randn((co,), generator=g) * 0.1 for _, co, _ in CH]
+    x0, y0, x1, y1 = rect
+    rng = np.random.default_rng(seed)
+    n = min(300, 4 * (x1 - x0 + 1) * (y1 - y0 + 1))
+    px = np.concatenate([[x0, x1, x0, x1], rng.integers(x0, x1 + 1, size=n)])[:max(n, 1)]
+    py = np.concatenate([[y0, y1, y1, y0], rng.integers(y0, y1 + 1, size=n)])[:max(n, 1)]
+    n = px.shape[0]
+    xyz = _at_pixels(px, py, seed)
+    w2c, K = _pixel_views(V, () if both_views else (1,))
+    pix = ib.restated_pixels(xyz, w2c, K, H, W)
+    assert torch.equal(pix[0], torch.tensor(np.stack([px, py], -1)).long()) and (both_views or bool((pix[1] == -1).all()))
+    G = torch.randn((V, n, 48), generator=g)
+    G[..., 45:] = 0
+    # ---- float64 autograd: six convolutions + LeakyReLU, three interpolations, concatenation, zeroed pixel (0,0), pixel gather, sum rows . G
+    w64 = [w.double().requires_grad_(True) for w in ws]
+    b64 = [b.double().requires_grad_(True) for b in bs]
+    x = img.double().permute(0, 3, 1, 2)
+    acts = []
+    for (ci, co, st), w, b in zip(CH, w64, b64):
+        x = torch.nn.functional.leaky_relu(torch.nn.functional.conv2d(x, w, b, stride=st, padding=1), slope)
+        acts.append(x)
+    fm = torch.cat([img.double().permute(0, 3, 1, 2)] + [ib.upsample(acts[i], H, W) for i in (1, 3, 5)], dim=1)       # [V,45,H,W]
+    zero00 = torch.ones((1, 1, H, W), dtype=torch.float64)
+    zero00[..., 0, 0] = 0
+    fm = fm * zero00
+    vpx, vpy = pix[..., 0].clamp(min=0), pix[..., 1].clamp(min=0)                                                       # masked rows gather the zeroed pixel
+    rows = fm[torch.arange(V)[:, None], :, vpy, vpx]                                                                    # [V,n,45]
+    (rows * G[..., :45].double()).sum().backward()
+    # ---- device
+    dev = _dev()
+    imgd = img.to(dev)
+    wd = [w.to(dev).contiguous() for w in ws]
+    bd = [b.to(dev).contiguous() for b in bs]
+    n_scr = int(L.hnr_image_features_scratch_elems(V, H, W))
+    scratch = torch.zeros((n_scr,), device=dev)
+    fmd = torch.empty((V, H, W, 48), device=dev)
+    wp = (ctypes.c_void_p * 6)(*[t.data_ptr() for t in wd])
+    bp = (ctypes.c_void_p * 6)(*[t.data_ptr() for t in bd])
+    _lib.check(L.hnr_image_features(p(imgd), V, H, W, wp, bp, slope, p(scratch), p(fmd), _lib.stream()), "hnr_image_features")
+    _, bbox, _, (loc, vs, counts, gpyr, bboxd) = _proj_rows_bwd(xyz, w2c, K, V, H, W, G, None, seed)
+    want_box = [[x0, y0, x1, y1], [x0, y0, x1, y1] if both_views else [W, H, -1, -1]]
+    assert bbox.tolist() == want_box, bbox.tolist()
+    out = {}
+    for which in ("clipped", "unclipped"):
+        gp = gpyr.clone()
+        gw = [torch.zeros_like(t) for t in wd]
+        gb = [torch.zeros_like(t) for t in bd]
+        gwp = (ctypes.c_void_p * 6)(*[t.data_ptr() for t in gw])
+        gbp = (ctypes.c_void_p * 6)(*[t.data_ptr() for t in gb])
+        if which == "clipped":
+            _lib.check(L.hnr_image_features_bwd_bbox(p(imgd), V, H, W, wp, slope, p(scratch), p(gp), gwp, gbp, p(bboxd), _lib.stream()), "hnr_image_features_bwd_bbox")
+        else:
+            _lib.check(L.hnr_image_features_bwd(p(imgd), V, H, W, wp, slope, p(scratch), p(gp), gwp, gbp, _lib.stream()), "hnr_image_features_bwd")
+        torch.cuda.synchronize()
+        out[which] = ([t.cpu() for t in gw], [t.cpu() for t in gb])
+    return out, [w.grad for w in w64], [b.grad for b in b64]
+
+
+def _check_cnn(name, out, rw, rb):
+    msgs, worst = [], {}
+    for which, (gw, gb) in out.items():
+        worst[which] = 0.0
+        for i in range(6):
+            for got, ref, what in ((gw[i], rw[i], "weight"), (gb[i], rb[i], "bias")):
+                scale = max(float(ref.abs().max()), 1e-6)
+                e = float((got.double() - ref).abs().max()) / scale
+                worst[which] = max(worst[which], e)
+                if not e <= 2e-5:
+                    msgs.append("%s conv%d %s: %.3e x max|ref|" % (which, i, what, e))
+    print("%s: max err / max|ref| over the 12 tensors: clipped %.3e, unclipped %.3e  (bound 2e-5)" % (name, worst["clipped"], worst["unclipped"]))
+    assert not msgs, (name, msgs)
+
+
+@pytest.mark.parametrize("where", sorted(RECTS))
+def test_clipped_cnn_backward_matches_fp64_autograd(where):
+    out, rw, rb = _cnn_case(203, 301, RECTS[where], False, 11 + len(where))
+    _check_cnn(where, out, rw, rb)
+
+
+def test_clipped_cnn_backward_with_nothing_to_skip():
+    out, rw, rb = _cnn_case(37, 51, (0, 0, 50, 36), True, 5)
+    _check_cnn("37x51 whole image", out, rw, rb)
+
+
+# ================================================================================================ the whole path at V != 4
+def _views_for(d, V, dev):
+    """The scannet_small fixture's first min(V, 4) reference views, then copies of its cameras moved by a few centimetres with synthetic images
+    (tests/test_image_branch.py: no sample of the fixtures projects within float32 rounding of a pixel border of any of them)."""
+    from hybridneuralrendering_amd import scenes
+    c2w = ib.extended_c2w(d["c2w_nearest"], V)
+    H, W = d["images_nearest"].shape[1:3]
+    img = d["images_nearest"][:min(V, 4)]
+    if V > 4:
+        img = np.concatenate([img, scenes.reference_images(V - 4, H, W, 11)], axis=0)
+    c = dict(c2w=torch.from_numpy(c2w), campos_n=torch.from_numpy(np.ascontiguousarray(c2w[:, :3, 3])), K=torch.from_numpy(d["intrinsic"]),
+             img=torch.from_numpy(np.ascontiguousarray(img.astype(np.float32))))
+    c["w2c"] = torch.inverse(c["c2w"])                                                # the CPU's LU, like the reference's run
+    return c, {k: v.to(dev).contiguous() for k, v in c.items()}
+
+
+def _render_setup(V):
+    from hybridneuralrendering_amd import scenes
+    from hybridneuralrendering_amd.aggregator import PointAggregator
+    from hybridneuralrendering_amd.render import HybridRenderer, PointCloud
+    from tests.golden_io import load_render, torch_inputs
+    d = load_render("scannet_small")
+    dev = _dev()
+    opt = scenes.default_opt(**dict(d["opt"], use_nearest=V))
+    agg = PointAggregator(opt)
+    agg.load_state_dict(d["sd"], strict=True)
+    agg = agg.to(dev)
+    ti = torch_inputs(d, dev)
+    cloud = PointCloud(ti["xyz"], ti["emb"], ti["conf"], ti["pdir"], ti["color"])
+    return d, ti, opt, cloud, HybridRenderer(opt, agg, dev)
+
+
+def _render_v(rnd, cloud, ti, d, vd, **kw):
+    near, far = d["near_far"]
+    return rnd.render_rays(cloud, ti["raydir"][0], ti["campos"][0], ti["camrotc2w"][0], ti["bg_color"][0], float(near), float(far), vd["c2w"], vd["campos_n"],
+                           vd["K"], vd["img"], w2c_nearest=vd["w2c"], **kw)
+
+
+def _flipped_rays(d, vc, vd, V):
+    """Valid samples whose hnr_proj_pixels pixel differs from the float64 restatement of the oracle in some view -> (their full-frame ray indices,
+    number of valid samples)."""
+    from hybridneuralrendering_amd import _lib
+    from oracle import render_oracle as ro
+    L, p = _lib.lib(), _lib.ptr
+    pidx, loc = d["q_sample_pidx"], d["q_sample_loc_w"]
+    Rv, SR = pidx.shape[:2]
+    H, W = d["images_nearest"].shape[1:3]
+    items = np.nonzero((pidx >= 0).any(-1).reshape(-1))[0].astype(np.int32)
+    n = items.shape[0]
+    counts = np.zeros((16,), np.int64)
+    counts[CNT_VALID] = n
+    pix = torch.full((V * n, 2), SENT_I, dtype=torch.int32, device=_dev())
+    locd, vsd, cd = _t(loc), _t(items), _t(counts)
+    _lib.check(L.hnr_proj_pixels(p(locd), p(vsd), p(cd), p(vd["w2c"]), p(vd["K"]), V, H, W, n, p(pix), _lib.stream()), "hnr_proj_pixels")
+    want = ro.gathered_pixels(torch.from_numpy(loc).double(), vc["c2w"].double()[None], vc["K"].double()[None], H, W).reshape(V, Rv * SR, 2)[:, items]
+    diff = (pix.view(V, n, 2).cpu().long() != want).any(-1).any(0)
+    rows = np.nonzero(d["q_ray_mask"])[0]
+    return np.unique(rows[items[diff.numpy()] // SR]), n, int(diff.sum())
+
+
+@pytest.mark.parametrize("V", [1, 3, 6, 8])
+def test_single_call_render_at_other_view_counts(V):
+    from oracle import render_oracle as ro
+    from tests.golden_io import torch_inputs
+    from tests.test_render_gpu import TOL_RAYCOLOR, TOL_OPACITY, _psnr
+    d, ti, opt, cloud, rnd = _render_setup(V)
+    vc, vd = _views_for(d, V, _dev())
+    assert rnd.single_call and rnd.dense == "f16x2" and int(opt.use_nearest) == V
+    out = _render_v(rnd, cloud, ti, d, vd, want_weights=True)
+    torch.cuda.synchronize()
+    assert "status" in out and int(out["status"][0]) == 0 and int(out["status"][1]) == int(out["counts"][CNT_VALID])
+    # the stage-by-stage path (hnr_proj_rows + the merge-weight MLP in segment mode + hnr_merge, exactly sized buffers): identical bits
+    rnd.single_call = False
+    ref = _render_v(rnd, cloud, ti, d, vd, want_weights=True)
+    assert "status" not in ref
+    for k in ("coarse_raycolor", "coarse_point_opacity", "coarse_is_background", "decoded", "ray_mask", "weight", "conf_coefficient", "blend_weight"):
+        assert torch.equal(out[k], ref[k]), k
+    # the CPU oracle on the fixture's query result
+    np.testing.assert_array_equal(out["ray_mask"].cpu().numpy(), d["q_ray_mask"])
+    tc = torch_inputs(d)
+    q = dict(sample_pidx=d["q_sample_pidx"], sample_loc_w=d["q_sample_loc_w"], ray_mask=d["q_ray_mask"])
+    with torch.no_grad():
+        o = ro.render(tc["xyz"], tc["emb"], tc["conf"], tc["pdir"], tc["color"], d["sd"], q, tc["campos"], tc["camrotc2w"], tc["raydir"], tc["bg_color"],
+                      vc["c2w"][None], vc["campos_n"][None], vc["K"][None], vc["img"][None], d["opt"]["vsize"], use_nearest=V)
+    bad_rays, n_valid, n_flip = _flipped_rays(d, vc, vd, V)
+    assert n_valid == int(out["counts"][CNT_VALID]) and n_flip <= 2e-3 * n_valid, (n_flip, n_valid)
+    ok = np.ones(out["ray_mask"].shape[0], bool)
+    ok[bad_rays] = False
+    col, refc = out["coarse_raycolor"].cpu().numpy(), o["full_coarse_raycolor"][0].numpy()
+    opa, isbg = out["coarse_point_opacity"].cpu().numpy(), out["coarse_is_background"].cpu().numpy()
+    e_col, e_opa = float(np.abs(col[ok] - refc[ok]).max()), float(np.abs(opa - o["full_coarse_point_opacity"][0].numpy()).max())
+    psnr = _psnr(col[ok], refc[ok])
+    print("render V=%d: valid samples %d, samples on another pixel than fp64 %d (rays excluded %d); max|dColor| %.2e  max|dOpacity| %.2e  PSNR %.1f dB" % (
+        V, n_valid, n_flip, len(bad_rays), e_col, e_opa, psnr))
+    assert e_col < TOL_RAYCOLOR and e_opa < TOL_OPACITY and psnr > 60.0
+    assert float(np.abs(isbg - o["full_coarse_is_background"][0, :, 0].numpy()).max()) < TOL_OPACITY
+    # the views matter: the same frame with other views is another image (V = 1 drops three of the fixture's four)
+    assert float(np.abs(col - d["full_coarse_raycolor"][0]).max()) > 10 * TOL_RAYCOLOR
+
+
+@pytest.mark.parametrize("V", [3, 8])
+def test_workspace_carve_at_other_view_counts_stays_inside_its_bytes(V):
+    """The canary arrangement of tests/test_render_forward_gpu.py::test_workspace_capacity_overflow_is_reported_not_overrun with the un-fused carve
+    (V != 4: four more buffers): a workspace of exactly hnr_render_workspace_bytes bytes with 0xAB behind it, once with cap_samples = the number of
+    valid samples (complete frame) and once 100 below it (overflow reported, nothing overrun)."""
+    from hybridneuralrendering_amd import _lib
+    d, ti, opt, cloud, rnd = _render_setup(V)
+    vc, vd = _views_for(d, V, _dev())
+    full = _render_v(rnd, cloud, ti, d, vd)
+    torch.cuda.synchronize()
+    n_valid = int(full["counts"][CNT_VALID])
+    L, p = _lib.lib(), _lib.ptr
+    dev = _dev()
+    raydir = ti["raydir"][0].contiguous()
+    R, SR, K = raydir.shape[0], int(opt.SR), int(opt.K)
+    grid, hp = rnd.querier._grid_for(cloud.xyz[None])
+    near, far = d["near_far"]
+    tmid = rnd.querier._tmid_for(float(near), float(far), opt.z_depth_dim, R, dev)
+    fm = rnd.feature_map(vd["img"])
+    assert fm.shape[0] == V
+    pk, agg, m3, ptab = rnd.agg.packed(), rnd.agg, rnd.agg.packed_mlp3(), rnd.point_table(cloud)
+    cl = _lib.RenderCloud(p(cloud.xyz), p(cloud.conf), p(cloud.dir), p(cloud.color), p(ptab), int(ptab.stride(0)))
+    wt = _lib.RenderWeights(p(agg.packed_chain()), p(m3["cf"].packed), p(m3["mw"].packed), p(m3["mx"].packed),
+                            p(pk["mw_last_w"]), p(pk["mw_last_b"]), p(pk["fin_w"]), p(pk["fin_b"]), float(pk["slope"]))
+    campos, camrot, bg = ti["campos"][0].contiguous(), ti["camrotc2w"][0].contiguous(), ti["bg_color"][0].contiguous()
+    cam = _lib.RenderCamera(p(campos), p(camrot), p(raydir), p(tmid), p(bg))
+    vw = _lib.RenderViews(p(vd["w2c"]), p(vd["K"]), p(vd["campos_n"]), p(fm), int(fm.shape[1]), int(fm.shape[2]), None)
+    for cap in (n_valid, n_valid - 100):
+        prm = _lib.RenderParams()
+        prm.R, prm.SR, prm.K, prm.D, prm.tmid_stride = R, SR, K, int(tmid.shape[-1]), 0
+        for i in range(3):
+            prm.kernel_size[i] = int(opt.kernel_size[i])
+        prm.radius2, prm.vsize_z, prm.raydist_mode_unit, prm.V, prm.cap_samples = float(np.float32(hp[0] ** 2)), float(np.float32(opt.vsize[2])), 1, V, cap
+        nbytes = int(L.hnr_render_workspace_bytes(ctypes.byref(prm)))
+        guard = 4096
+        ws = torch.zeros((nbytes + 256 + guard,), dtype=torch.uint8, device=dev)
+        off = (-ws.data_ptr()) % 256
+        ws[off + nbytes:] = 0xAB
+        f = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
+        col, opa, isbg, dec, loc = f(R, 3), f(R, SR), f(R), f(R, SR, 4), f(R, SR, 3)
+        mask = torch.empty((R,), dtype=torch.int8, device=dev)
+        pidx = torch.empty((R, SR, K), dtype=torch.int32, device=dev)
+        nsamp = torch.empty((R,), dtype=torch.int32, device=dev)
+        counts = torch.empty((_lib.NCOUNTS,), dtype=torch.int64, device=dev)
+        status = torch.empty((2,), dtype=torch.int32, device=dev)
+        o = _lib.RenderOutputs(p(col), p(opa), p(isbg), None, p(mask), p(dec), p(pidx), p(loc), p(nsamp), p(counts), p(status), None, None, None)
+        _lib.check(L.hnr_render_forward(grid.handle, ctypes.byref(prm), ctypes.byref(cl), ctypes.byref(wt), ctypes.byref(cam), ctypes.byref(vw),
+                                        ctypes.c_void_p(ws.data_ptr() + off), nbytes, ctypes.byref(o), _lib.stream()), "hnr_render_forward")
+        torch.cuda.synchronize()
+        assert bool((ws[off + nbytes:] == 0xAB).all()), (V, cap)                      # nothing written past the workspace
+        assert bool(torch.isfinite(col).all())
+        if cap == n_valid:
+            assert int(status[0]) == 0 and int(status[1]) == n_valid and int(counts[CNT_VALID]) == n_valid
+            assert torch.equal(col, full["coarse_raycolor"]) and torch.equal(opa, full["coarse_point_opacity"])
+        else:
+            assert int(status[0]) == 1 and int(status[1]) == n_valid and int(counts[CNT_VALID]) == cap
+            same = (col == full["coarse_raycolor"]).all(dim=1)                        # rays whose samples all fit below the capacity are complete
+            assert int(same.sum()) > 0.9 * R
+
+
+def _train_setup(V):
+    from hybridneuralrendering_amd import scenes
+    from hybridneuralrendering_amd.aggregator import PointAggregator
+    from hybridneuralrendering_amd.render import HybridRenderer
+    from hybridneuralrendering_amd.train import TrainPath
+    from tests.golden_io import load_train, torch_inputs
+    d = load_train("scannet_small")
+    dev = _dev()
+    opt = scenes.default_opt(**dict(d["opt"], use_nearest=V))
+    assert opt.is_train == 1
+    agg = PointAggregator(opt)
+    agg.load_state_dict(d["sd"], strict=True)
+    agg = agg.to(dev)
+    return d, torch_inputs(d, dev), opt, agg, TrainPath(HybridRenderer(opt, agg, dev))
+
+
+def _train_once(d, ti, agg, path, vd):
+    from hybridneuralrendering_amd.train import render_train
+    from tests.test_train_gpu import _leaves, _loss
+    emb, conf, pdir, color = _leaves(ti)
+    agg.zero_grad(set_to_none=True)
+    near, far = d["near_far"]
+    tmid = torch.from_numpy(d["tmid"]).to(emb.device)
+    out = render_train(path, agg, ti["xyz"], emb, conf, pdir, color, ti["raydir"][0], ti["campos"][0], ti["camrotc2w"][0], ti["bg_color"][0], near, far,
+                       vd["c2w"], vd["campos_n"], vd["K"], vd["img"], tmid=tmid)
+    loss, lc, lz = _loss(out, torch.from_numpy(d["gt"][0]).to(emb.device), float(d["zero_epsilon"]))
+    loss.backward()
+    got = {"neural_points.points_embeding": emb.grad, "neural_points.points_conf": conf.grad, "neural_points.points_dir": pdir.grad,
+           "neural_points.points_color": color.grad}
+    for k, prm in agg.named_parameters():
+        if prm.grad is not None:
+            got["aggregator." + k] = prm.grad.clone()
+    return out, (loss.item(), lc.item(), lz.item()), got
+
+
+@pytest.mark.parametrize("V", [1, 3, 8])
+def test_train_step_at_other_view_counts_matches_the_oracle(V):
+    """The fixture batch (its jittered depths, its patch drop) with 1, 3 and 8 reference views: the backward runs merge_bwd_kernel<MAXV> (V = 8),
+    sum_views / hnr_h2lin / hnr_h2wgrad with n_seg = V, and the un-fused forward carve."""
+    from oracle import render_oracle as ro
+    from tests.golden_io import torch_inputs
+    from tests.test_train_gpu import _check_grads, TOL_POINTS
+    d, ti, opt, agg, path = _train_setup(V)
+    vc, vd = _views_for(d, V, _dev())
+    out, losses, got = _train_once(d, ti, agg, path, vd)
+    np.testing.assert_array_equal(out["ray_mask"].cpu().numpy(), d["q_ray_mask"])
+    assert int(out["status"][0]) == 0
+    o = d["opt"]
+    tc = torch_inputs(d)
+    q = dict(sample_pidx=d["q_sample_pidx"], sample_loc_w=d["q_sample_loc_w"], ray_mask=d["q_ray_mask"])
+    drop = ro.drop_patch_rays(int(o["dilation_setup"].split("_")[1]), int(o["dilation_setup"].split("_")[0]), o["drop_ratio"])
+    args = (tc["xyz"], tc["emb"], tc["conf"], tc["pdir"], tc["color"], d["sd"], q, tc["campos"], tc["camrotc2w"], tc["raydir"], tc["bg_color"],
+            vc["c2w"][None], vc["campos_n"][None], vc["K"][None], vc["img"][None], o["vsize"], torch.from_numpy(d["gt"]), float(d["zero_epsilon"]), drop)
+    _, ref_losses, ref = ro.train_step(*args, use_nearest=V)
+    print("train V=%d: loss terms HIP %s oracle %s" % (V, losses, ref_losses))
+    np.testing.assert_allclose(losses, ref_losses, rtol=2e-5)
+    assert sorted(got) == sorted(ref), set(got) ^ set(ref)                             # the same parameters receive a gradient
+    _, _, ref64 = ro.train_step(*args, use_nearest=V, dtype=torch.float64)
+    # With ONE view the merge is f w / (w + 1e-6): the merge weight cancels but for the 1e-6, the gradients of aux_merge_weight_block are that residue
+    # (1e-9, six orders below every other weight gradient) and come out of f / (w + eps) - f w / (w + eps)^2 in float32 -- in torch's autograd as in
+    # the kernel.  The oracle's own float32 run misses its float64 run there by 1.1e-3 .. 3.4e-3 x max (l2 up to 2.4e-3), above the tolerance of
+    # _check_grads, so no float32 path can be held to it; those eight tensors are held to 4 x the oracle's own float32 error instead (the yardstick
+    # hnr_merge is held to above), every other tensor to _check_grads as at V = 3 and 8.
+    ill = sorted(k for k in ref if V == 1 and k.startswith("aggregator.aux_merge_weight_block."))
+    assert len(ill) == (8 if V == 1 else 0)
+    rest = lambda g: {k: v for k, v in g.items() if k not in ill}
+    # (weight gradients at the point-gradient tolerance, for the reason given in tests/test_train_gpu.py::test_train_step_matches_oracle_on_a_fresh_batch:
+    # a hidden unit within rounding of the LeakyReLU kink sits on either side in two float32 forwards)
+    _check_grads(rest(got), rest(ref), "V=%d vs oracle" % V, tol_weights=TOL_POINTS)
+    _check_grads(rest(got), rest(ref64), "V=%d vs fp64" % V, tol_weights=TOL_POINTS)
+    if ill:
+        n64 = lambda t: t.detach().cpu().numpy().astype(np.float64)
+        rel = lambda x, r: (float(np.abs(x - r).max() / np.abs(r).max()), float(np.linalg.norm(x - r) / np.linalg.norm(r)))
+        own = [rel(n64(ref[k]), n64(ref64[k])) for k in ill]
+        e32_max, e32_l2 = max(e[0] for e in own), max(e[1] for e in own)
+        big = float(np.abs(n64(ref64["aggregator.color_mixup_block.0.weight"])).max())
+        for k in ill:
+            assert float(np.abs(n64(ref64[k])).max()) < 1e-5 * big, k                 # the 1e-6 residue
+            emax, el2 = rel(n64(got[k]).reshape(n64(ref64[k]).shape), n64(ref64[k]))
+            print("V=1 vs fp64   %-45s max err / max|ref| %.2e  rel l2 %.2e  (oracle float32 vs float64 over the block: %.2e, %.2e; bound 4 x)" % (k, emax, el2, e32_max, e32_l2))
+            assert emax <= 4 * e32_max and el2 <= 4 * e32_l2, (k, emax, el2, e32_max, e32_l2)
+    if V == 3:
+        _, _, again = _train_once(d, ti, agg, path, vd)
+        for k in got:
+            if k.startswith("neural_points."):
+                assert torch.equal(got[k], again[k]), k                              # point gradients: fixed summation order, identical bits
