@@ -92,6 +92,25 @@ class TrainViews(ctypes.Structure):
     _fields_ = [("d_w2c", _P), ("d_intrinsic", _P), ("d_campos_nearest", _P), ("d_images", _P), ("d_frame_w", _P)]
 
 
+class FrameBankC(ctypes.Structure):
+    """hnr_frame_bank"""
+    _fields_ = [("d_images", _P), ("d_c2w", _P), ("d_w2c", _P), ("d_intrinsic", _P), ("d_weight", _P), ("d_angle", _P), ("images_f32", _I), ("F", _I),
+                ("H", _I), ("W", _I), ("intrinsic_per_frame", _I)]
+
+
+class FrameBatchParams(ctypes.Structure):
+    _fields_ = [(n, _I) for n in ("mode", "size", "patch_num", "patch_size", "dilation_lo", "dilation_hi", "margin", "dir_norm", "bg_random",
+                                  "downweight_blurry_feats")] + [("bg_color", _F * 3), ("seed", ctypes.c_uint64)]
+
+
+FRAME_OUTPUTS = ("raydir", "pixel_idx", "gt_image", "campos", "camrot", "c2w", "intrinsic", "c2w_nearest", "w2c_nearest", "campos_nearest", "intrinsic_nearest",
+                 "images_nearest", "frame_weight_nearest", "vid_angle_nearest", "frame_weight", "bg_color", "frame_row", "patch_table")
+
+
+class FrameBatchOut(ctypes.Structure):
+    _fields_ = [("d_" + n, _P) for n in FRAME_OUTPUTS]
+
+
 RENDER_STAGES = ("query", "plan_gather", "chain_gather", "chain", "mlp_colorfeat", "proj_rows", "mlp_merge", "merge", "mlp_mixup", "final_color",
                  "composite")
 
@@ -171,6 +190,12 @@ SIGNATURES = {
     "hnr_range_crop": (_I, [_P, _P, ctypes.c_int64, ctypes.POINTER(_F), _P, _P, _P, ctypes.c_int64, _P]),
     "hnr_nearest_view": (_I, [_P, ctypes.c_int64, _P, _P, _I, _P, _P]),
     "hnr_point_view_attrs": (_I, [_P, ctypes.c_int64] + [ctypes.POINTER(_F)] * 4 + [_I, _I, _P, _I, _I, _I, _P, _P, _P, _P]),
+    # device-resident frame bank + batch sampler (csrc/frames.hip)
+    "hnr_frame_batch_scratch_bytes": (ctypes.c_int64, [_I, _I]),
+    "hnr_frame_batch": (_I, [ctypes.POINTER(FrameBankC), ctypes.POINTER(FrameBankC), _P, _I, ctypes.POINTER(FrameBatchParams), _P, _I, _P,
+                             ctypes.POINTER(FrameBatchOut), _P, ctypes.c_int64, _P]),
+    "hnr_frame_item": (_I, [ctypes.POINTER(FrameBankC), ctypes.POINTER(FrameBankC), _P, _I, _I, _P, ctypes.c_int64, _I, _I, ctypes.POINTER(_F), _I,
+                            ctypes.POINTER(FrameBatchOut), _P, ctypes.c_int64, _P]),
     "hnr_blur_gray_patches": (_I, [_P, _P, _I, _I, _P, _P]),
     "hnr_blur_gray_patches_bwd": (_I, [_P, _I, _I, _P, _P]),
     "hnr_blur_apply": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),

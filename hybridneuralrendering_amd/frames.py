@@ -1,0 +1,328 @@
+"""A scene's frames resident on the device and the ray batch of every training step drawn there (csrc/frames.hip).
+
+The reference builds a batch on the host, per step: data/scannet_ft_dataset.py:736-976 (nerf_synth360_ft_dataset.py:643-800) decodes the target frame
+and its nearest frames, draws pixel coordinates with numpy, builds `raydir` with get_dtu_raydir, gathers `gt_image` and uploads ~15 MB of float
+reference images.  A train split is 200 - 1000 frames of 480 x 640 x 3 bytes: it fits on the device as it is.  `FrameBank` holds it there,
+`BatchSampler.next()` writes the dataset item of the next step with at most three launches that read the frame number and the step counter from
+device memory -- no upload, no host read, capturable in a hipGraph.  Image decoding and resizing stay the caller's (once per scene).
+
+The nearest-view tables are per-frame constants and are computed on the host: `nearest_by_id` (ScanNet), `nearest_by_pose` (synthetic scenes).
+tests/frames_ref.py restates the sampler's arithmetic in NumPy; the GPU results equal it bit for bit.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import HnrError
+
+MODES = {"random": 0, "patch": 1, "dilated": 2}
+
+
+def nearest_by_id(query_ids, train_ids, V, exclude_self, weights=None, select_high_quality=False, dynamic_nearest=False):
+    """data/scannet_ft_dataset.py:771-812: for every query frame id the V train frames with the closest ids -> rows into train_ids, int32 [Q,V].
+    exclude_self: drop a train frame whose id IS the query's (find_nearest_mode 0 always; find_nearest_mode 1 for the train split only).
+    select_high_quality: of the int(1.5 V) closest, the V with the largest `weights` (train_weight_list).  Equal distances (frames at -5 and +5) keep
+    the order of train_ids (a stable sort; the reference's np.argsort leaves it unspecified)."""
+    if dynamic_nearest:
+        raise HnrError("nearest_by_id: dynamic_nearest draws the number of views afresh every step, which changes tensor shapes; not supported")
+    train_ids = np.asarray(train_ids)
+    V = int(V)
+    if V < 1 or train_ids.ndim != 1:
+        raise HnrError("nearest_by_id: V >= 1 and a flat list of train ids")
+    if select_high_quality and weights is None:
+        raise HnrError("nearest_by_id: select_high_quality needs the train frames' weights")
+    rows = []
+    for vid in np.asarray(query_ids).reshape(-1):
+        dist = np.abs(train_ids - vid)
+        order = np.argsort(dist, kind="stable")
+        skip = 1 if (exclude_self and dist[order[0]] == 0) else 0
+        if select_high_quality:
+            cand = order[skip:skip + int(V * 1.5)]
+            cand = cand[np.argsort(-np.asarray(weights, dtype=np.float64)[cand], kind="stable")]
+            pick = cand[:V]
+        else:
+            pick = order[skip:skip + V]
+        if len(pick) != V:
+            raise HnrError("nearest_by_id: %d train frames cannot give %d nearest views" % (len(train_ids), V))
+        rows.append(pick)
+    return np.asarray(rows, dtype=np.int32).reshape(-1, V)
+
+
+def center_raydir(intrinsic, c2w, width, height):
+    """nerf_synth360_ft_dataset.py:740-741: the normalised direction of pixel (width // 2, height // 2), get_dtu_raydir in NumPy as the reference runs it."""
+    K, R = np.asarray(intrinsic, dtype=np.float32), np.asarray(c2w, dtype=np.float32)[:3, :3]
+    pix = np.asarray([width, height]).astype(np.float32)[None, :] // 2
+    x = (pix[..., 0] + 0.5 - K[0, 2]) / K[0, 0]
+    y = (pix[..., 1] + 0.5 - K[1, 2]) / K[1, 1]
+    d = np.stack([x, y, np.ones_like(x)], axis=-1) @ R.T
+    return d / (np.linalg.norm(d, axis=-1, keepdims=True) + 1e-5)
+
+
+def nearest_by_pose(query_c2w, query_intrinsic, query_ids, train_pos, train_dirs, train_ids, V, width, height, is_train, num_times=3):
+    """`get_nearest_cam_id` (nerf_synth360_ft_dataset.py:49-74) for every query camera -> int32 [Q,V], entries of train_ids (which the reference uses as
+    rows of its train arrays).  Step 1: the num_times * V train cameras (at most a tenth of them) whose direction train_dirs [T,3] is closest to
+    the query's centre-pixel direction; step 2: of those the V closest in position train_pos [T,3]; the query itself is skipped when is_train.
+    query_intrinsic: [3,3] or one per query."""
+    train_pos, train_dirs, train_ids = np.asarray(train_pos), np.asarray(train_dirs), np.asarray(train_ids)
+    K = np.asarray(query_intrinsic, dtype=np.float32)
+    V = int(V)
+    n1 = min(int(num_times) * V, int(len(train_ids) * 0.1))
+    rows = []
+    for q, (M, cid) in enumerate(zip(np.asarray(query_c2w, dtype=np.float32), np.asarray(query_ids).reshape(-1))):
+        d = center_raydir(K[q] if K.ndim == 3 else K, M, width, height)
+        idx1 = np.argsort(-train_dirs.dot(d[0]), kind="stable")[:n1]
+        ids1, pos1 = train_ids[idx1], train_pos[idx1]
+        idx2 = np.argsort(np.linalg.norm(pos1 - M[:3, 3], axis=1), kind="stable")
+        skip = 1 if (len(idx2) and ids1[idx2[0]] == cid and is_train) else 0
+        pick = ids1[idx2[skip:skip + V]]
+        if len(pick) != V:
+            raise HnrError("nearest_by_pose: %d train cameras leave %d candidates, fewer than the %d views asked for" % (len(train_ids), len(idx2) - skip, V))
+        rows.append(pick)
+    return np.asarray(rows, dtype=np.int32).reshape(-1, V)
+
+
+class FrameBank:
+    """All frames of one split on the device: images [F,H,W,3] uint8 (stored as they are) or float32, c2w [F,4,4], w2c = torch.inverse(c2w) (computed
+    once, on the device), intrinsic [3,3] shared or [F,3,3], weight[f] = float32(weights[f] ** weight_exp) (float64 arithmetic, as
+    scannet_ft_dataset.py:758; ones without weights) and angle[f] = float32(ids[f] / total_num_image * 2 pi) (:830).  `ids`: the frames' vids
+    (default 0..F-1); total_num_image defaults to max(ids) + 1."""
+
+    def __init__(self, images, c2w, intrinsic, device, ids=None, weights=None, weight_exp=1.0, total_num_image=None):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise HnrError("FrameBank: device must be a GPU (the HIP path has no CPU fallback)")
+        images = torch.from_numpy(np.ascontiguousarray(images)) if isinstance(images, np.ndarray) else images
+        if not isinstance(images, torch.Tensor) or images.dim() != 4 or images.shape[3] != 3 or images.dtype not in (torch.uint8, torch.float32):
+            raise HnrError("FrameBank: images must be [F,H,W,3] uint8 or float32")
+        F, H, W = (int(s) for s in images.shape[:3])
+        if F < 1 or H < 1 or W < 1 or H * W > (1 << 26):
+            raise HnrError("FrameBank: F, H, W >= 1 and H * W <= 2^26")
+        self.F, self.H, self.W = F, H, W
+        self.images = images.to(self.device).contiguous()
+        c2w = torch.as_tensor(np.asarray(c2w.detach().cpu() if isinstance(c2w, torch.Tensor) else c2w, dtype=np.float32))
+        if tuple(c2w.shape) != (F, 4, 4):
+            raise HnrError("FrameBank: c2w must be [%d,4,4], got %s" % (F, tuple(c2w.shape)))
+        self.c2w = c2w.to(self.device).contiguous()
+        self.w2c = torch.inverse(self.c2w).contiguous()
+        K = torch.as_tensor(np.asarray(intrinsic.detach().cpu() if isinstance(intrinsic, torch.Tensor) else intrinsic, dtype=np.float32))
+        if tuple(K.shape) not in ((3, 3), (F, 3, 3)):
+            raise HnrError("FrameBank: intrinsic must be [3,3] or [%d,3,3], got %s" % (F, tuple(K.shape)))
+        self.intrinsic = K.to(self.device).contiguous()
+        self.ids = np.arange(F) if ids is None else np.asarray(ids).reshape(-1)
+        if self.ids.shape[0] != F:
+            raise HnrError("FrameBank: %d ids for %d frames" % (self.ids.shape[0], F))
+        total = int(self.ids.max()) + 1 if total_num_image is None else total_num_image
+        if not total > 0:
+            raise HnrError("FrameBank: total_num_image must be positive")
+        if weights is None:
+            w = np.ones((F,), np.float32)
+        else:
+            if len(weights) != F:
+                raise HnrError("FrameBank: %d weights for %d frames" % (len(weights), F))
+            w = np.array([np.float32(float(x) ** float(weight_exp)) for x in weights], dtype=np.float32)
+        ang = np.array([np.float32((float(i) / float(total)) * 2 * np.pi) for i in self.ids], dtype=np.float32)
+        self.weight, self.angle = torch.from_numpy(w).to(self.device), torch.from_numpy(ang).to(self.device)
+        self.nearest, self.reference, self.V = None, self, 0
+        self._c = _lib.FrameBankC(_lib.ptr(self.images), _lib.ptr(self.c2w), _lib.ptr(self.w2c), _lib.ptr(self.intrinsic), _lib.ptr(self.weight),
+                                  _lib.ptr(self.angle), 1 if self.images.dtype == torch.float32 else 0, F, H, W, 1 if K.dim() == 3 else 0)
+
+    def set_nearest(self, table, reference=None):
+        """table [F,V] int32: the rows of every frame's nearest reference frames in `reference` (default: this bank; a test-set bank names its
+        train-set bank)."""
+        ref = self if reference is None else reference
+        if not isinstance(ref, FrameBank) or ref.device != self.device or (ref.H, ref.W) != (self.H, self.W):
+            raise HnrError("FrameBank.set_nearest: the reference must be a FrameBank on the same device with the same frame size")
+        t = np.asarray(table.detach().cpu() if isinstance(table, torch.Tensor) else table)
+        if t.ndim != 2 or t.shape[0] != self.F or t.shape[1] < 1 or t.shape[1] > 64 or not np.issubdtype(t.dtype, np.integer):
+            raise HnrError("FrameBank.set_nearest: the table must be integer [%d,V], 1 <= V <= 64, got %s %s" % (self.F, t.dtype, t.shape))
+        if t.min() < 0 or t.max() >= ref.F:
+            raise HnrError("FrameBank.set_nearest: a nearest row is outside the reference bank (0 .. %d)" % (ref.F - 1))
+        self.nearest = torch.from_numpy(np.ascontiguousarray(t, dtype=np.int32)).to(self.device)
+        self.reference, self.V = ref, int(t.shape[1])
+        return self
+
+
+class BatchSampler:
+    """The dataset item of every step, written on the device.
+
+    mode "random" | "patch" (size x size rays) | "dilated" (dilation_setup "pn_ps_dlo_dhi": (pn ps)^2 rays in the layout of scenes.dilated_patch_batch and
+    the blur module's "grid"); margin = opt.edge_filter; bg_color a triple or "random"; the definitions are in include/hnr.h and tests/frames_ref.py.
+    `set_schedule(rows)` uploads the bank rows to visit (an epoch's permutation), used cyclically; `next()` writes the batch of step `step` -- the
+    frame is schedule[step % len] -- and advances `step` on the device.  It returns the same static tensors on every call, allocates nothing after
+    the first call, reads nothing back and is at most three launches on the current stream (capturable with torch.cuda.graph on one stream).
+    `item(row, pixels=None)` is the explicit form without a counter (evaluation frames; fresh tensors).
+
+    The dict has the dataset item's keys: raydir [R,3], pixel_idx [R,2] float32 (x, y), gt_image [R,3]; campos [3], camrotc2w = camrot [3,3], c2w [4,4],
+    intrinsic [3,3]; c2w_nearest, w2c_nearest [V,4,4], campos_nearest [V,3], intrinsic_nearest [3,3], images_nearest [V,H,W,3] float32,
+    frame_weight_nearest [V], vid_angle_nearest [V]; frame_weight [1] (device), bg_color [3], near, far, h, w; frame_row [1] int32 and, for
+    patch / dilated, patch_table [pn^2,3] int32 (d, x0, y0)."""
+
+    def __init__(self, bank, mode, size=None, dilation_setup=None, margin=0, seed=0, dir_norm=0, bg_color=(1, 1, 1), near=None, far=None,
+                 downweight_blurry_feats=0):
+        if not isinstance(bank, FrameBank):
+            raise HnrError("BatchSampler: bank must be a FrameBank")
+        if mode not in MODES:
+            raise HnrError("BatchSampler: mode must be one of %s (random2, proportional_random and dynamic_nearest are not supported)" % sorted(MODES))
+        if near is None or far is None:
+            raise HnrError("BatchSampler: near and far (the item's depth range) are required")
+        self.L = _lib.lib()
+        self.bank, self.mode, self.margin = bank, mode, int(margin)
+        self.near, self.far = float(near), float(far)
+        H, W, m = bank.H, bank.W, self.margin
+        if m < 0 or W - 2 * m <= 0 or H - 2 * m <= 0:
+            raise HnrError("BatchSampler: margin %d leaves no pixel of a %dx%d frame (an empty range)" % (m, H, W))
+        pn = ps = dlo = dhi = 0
+        if mode == "dilated":
+            try:
+                pn, ps, dlo, dhi = (int(float(x)) for x in str(dilation_setup).split("_"))
+            except ValueError:
+                raise HnrError("BatchSampler: dilation_setup must be 'pn_ps_dlo_dhi', got %r" % (dilation_setup,))
+            if pn < 1 or ps < 1 or dlo < 1 or dhi < dlo or pn * ps > 8192:
+                raise HnrError("BatchSampler: dilation_setup %r: pn, ps >= 1, 1 <= dlo <= dhi" % (dilation_setup,))
+            reach, S = (ps - 1) * dhi, pn * ps
+        else:
+            if size is None or int(size) < 1 or int(size) > 8192:
+                raise HnrError("BatchSampler: mode %r needs 1 <= size <= 8192" % mode)
+            S = int(size)
+            reach = S - 1 if mode == "patch" else 0
+        if mode != "random" and (W - m - reach <= m or H - m - reach <= m):
+            raise HnrError("BatchSampler: a patch reaching %d pixels does not fit a %dx%d frame with margin %d (size larger than the frame: an empty range)"
+                           % (reach + 1, H, W, m))
+        self.S, self.R, self.pn, self.ps = S, S * S, (1 if mode == "patch" else pn), (S if mode == "patch" else ps)
+        bg_random = isinstance(bg_color, str)
+        if bg_random and bg_color != "random":
+            raise HnrError("BatchSampler: bg_color must be a triple or 'random'")
+        self.bg = (1.0, 1.0, 1.0) if bg_random else tuple(float(c) for c in bg_color)
+        if len(self.bg) != 3:
+            raise HnrError("BatchSampler: bg_color must have three components")
+        self.dir_norm, self.downweight = int(bool(dir_norm)), int(bool(downweight_blurry_feats))
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.seed = seed
+        self.prm = _lib.FrameBatchParams(MODES[mode], S, pn, ps, dlo, dhi, m, self.dir_norm, int(bg_random), self.downweight, (ctypes.c_float * 3)(*self.bg), seed)
+        dev = bank.device
+        nbytes = int(self.L.hnr_frame_batch_scratch_bytes(MODES[mode], pn))
+        if nbytes < 0:
+            raise HnrError("BatchSampler: unsupported mode / patch count")
+        self._scratch = torch.zeros((max(nbytes, 16),), dtype=torch.uint8, device=dev)
+        self._item_scratch = torch.zeros((16,), dtype=torch.uint8, device=dev)
+        self.step = torch.zeros((1,), dtype=torch.int64, device=dev)          # the step counter (read and advanced by the header kernel)
+        self.schedule, self._n_schedule = None, 0
+        self._static, self._bound = None, {}
+
+    # ------------------------------------------------------------------------------------------------ plumbing
+    def _shapes(self, R):
+        b = self.bank
+        V, H, W = b.V, b.H, b.W
+        f, i = torch.float32, torch.int32
+        sh = dict(raydir=((R, 3), f), pixel_idx=((R, 2), f), gt_image=((R, 3), f), campos=((3,), f), camrot=((3, 3), f), c2w=((4, 4), f), intrinsic=((3, 3), f),
+                  frame_weight=((1,), f), bg_color=((3,), f), frame_row=((1,), i))
+        if V > 0:
+            sh.update(c2w_nearest=((V, 4, 4), f), w2c_nearest=((V, 4, 4), f), campos_nearest=((V, 3), f), intrinsic_nearest=((3, 3), f),
+                      images_nearest=((V, H, W, 3), f), frame_weight_nearest=((V,), f), vid_angle_nearest=((V,), f))
+        if self.mode != "random" and R == self.R:
+            sh["patch_table"] = ((self.pn * self.pn, 3), i)
+        return sh
+
+    def _alloc(self, R, with_table):
+        dev = self.bank.device
+        t = {k: torch.empty(s, dtype=d, device=dev) for k, (s, d) in self._shapes(R).items() if with_table or k != "patch_table"}
+        return t
+
+    def _finish(self, t):
+        d = dict(t)
+        d["camrotc2w"] = d["camrot"]
+        d.update(near=self.near, far=self.far, h=self.bank.H, w=self.bank.W)
+        return d
+
+    def _bind(self, tensors, R, what):
+        """name -> tensor  =>  hnr_frame_batch_out; every tensor checked against the expected element count and dtype"""
+        sh = self._shapes(R)
+        o = _lib.FrameBatchOut()
+        for k, t in tensors.items():
+            if k not in sh:
+                continue
+            shape, dt = sh[k]
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != self.bank.device or t.dtype != dt or not t.is_contiguous() or \
+                    t.numel() != int(np.prod(shape)):
+                raise HnrError("%s: output %r must be a contiguous %s tensor of %s on %s, got %s %s" % (
+                    what, k, dt, "x".join(str(s) for s in shape), self.bank.device, getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
+            if k == "images_nearest" and t.data_ptr() % 16:
+                raise HnrError("%s: images_nearest must be 16-byte aligned" % what)
+            setattr(o, "d_" + k, t.data_ptr())
+        return o
+
+    def _views(self):
+        b = self.bank
+        return (ctypes.byref(b.reference._c) if b.V > 0 else None), (_lib.ptr(b.nearest) if b.V > 0 else None), b.V
+
+    # ------------------------------------------------------------------------------------------------ the interface
+    def set_schedule(self, rows):
+        """rows: the bank rows to visit, in order (an epoch's permutation); uploaded once, used cyclically.  The step counter keeps its value."""
+        r = np.asarray(rows.detach().cpu() if isinstance(rows, torch.Tensor) else rows).reshape(-1)
+        if r.size < 1 or r.size >= (1 << 31) or not np.issubdtype(r.dtype, np.integer):
+            raise HnrError("BatchSampler.set_schedule: a non-empty list of integer bank rows")
+        if r.min() < 0 or r.max() >= self.bank.F:
+            raise HnrError("BatchSampler.set_schedule: a row is outside the bank (0 .. %d)" % (self.bank.F - 1))
+        self.schedule, self._n_schedule = torch.from_numpy(np.ascontiguousarray(r, dtype=np.int32)).to(self.bank.device), int(r.size)
+        return self
+
+    def set_step(self, step):
+        """Sets the device step counter (a host -> device fill; resuming a run)."""
+        self.step.fill_(int(step))
+        return self
+
+    def next(self, out=None):
+        """The batch of step `step`; step += 1 on the device.  out=None: the sampler's own static tensors (the same on every call).  out = a dict: the
+        outputs whose keys are present in it ("camrot" or "camrotc2w" for the rotation) are written into those tensors and no others are touched
+        -- `sampler.next(out=cap.inputs); cap.step()` is a training step with no copy and no host read.  Returns the dict written to."""
+        if self.schedule is None:
+            raise HnrError("BatchSampler.next: no schedule (set_schedule(rows) first)")
+        if out is None:
+            if self._static is None:
+                t = self._alloc(self.R, True)
+                self._static = (self._finish(t), self._bind(t, self.R, "BatchSampler.next"))
+            res, o = self._static
+        else:
+            key = tuple((k, v.data_ptr(), v.numel(), v.dtype) for k, v in out.items() if isinstance(v, torch.Tensor))
+            o = self._bound.get(key)
+            if o is None:                                     # shapes and dtypes are checked once per set of tensors
+                t = {k: v for k, v in out.items() if isinstance(v, torch.Tensor)}
+                if "camrotc2w" in t:
+                    if "camrot" in t and t["camrot"].data_ptr() != t["camrotc2w"].data_ptr():
+                        raise HnrError("BatchSampler.next: out has both camrot and camrotc2w, and they are different tensors")
+                    t["camrot"] = t.pop("camrotc2w")
+                if len(self._bound) > 16:
+                    self._bound.clear()
+                o = self._bound[key] = self._bind(t, self.R, "BatchSampler.next")
+            res = out
+        ref, nearest, V = self._views()
+        with torch.cuda.device(self.bank.device):
+            _lib.check(self.L.hnr_frame_batch(ctypes.byref(self.bank._c), ref, nearest, V, ctypes.byref(self.prm), _lib.ptr(self.schedule), self._n_schedule,
+                                              _lib.ptr(self.step), ctypes.byref(o), _lib.ptr(self._scratch), int(self._scratch.numel()), _lib.stream()),
+                       "hnr_frame_batch")
+        return res
+
+    def item(self, row, pixels=None):
+        """The item of bank row `row` with no counter: every pixel minus `margin` in scan-line order ('no_crop', scannet_ft_dataset.py:946-949), or the
+        given pixel_idx [R,2] float32 (x, y; fractional pixels truncate for gt_image).  bg_color "random" gives white here."""
+        row = int(row)
+        if row < 0 or row >= self.bank.F:
+            raise HnrError("BatchSampler.item: row %d is outside the bank (0 .. %d)" % (row, self.bank.F - 1))
+        dev = self.bank.device
+        if pixels is not None:
+            pixels = torch.as_tensor(pixels, dtype=torch.float32).to(dev).reshape(-1, 2).contiguous()
+            R = int(pixels.shape[0])
+            if R < 1:
+                raise HnrError("BatchSampler.item: pixels must be [R,2], R >= 1")
+        else:
+            R = (self.bank.W - 2 * self.margin) * (self.bank.H - 2 * self.margin)
+        t = self._alloc(R, False)
+        o = self._bind(t, R, "BatchSampler.item")
+        ref, nearest, V = self._views()
+        with torch.cuda.device(dev):
+            _lib.check(self.L.hnr_frame_item(ctypes.byref(self.bank._c), ref, nearest, V, row, _lib.ptr(pixels), R, self.margin, self.dir_norm,
+                                             (ctypes.c_float * 3)(*self.bg), self.downweight, ctypes.byref(o), _lib.ptr(self._item_scratch), 16, _lib.stream()),
+                       "hnr_frame_item")
+        return self._finish(t)

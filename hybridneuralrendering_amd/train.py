@@ -451,7 +451,7 @@ def _assign_grads(aggregator, emb, conf, pdir, color, pg, ag, accumulate=True, c
 def train_step(path, aggregator, xyz, emb, conf, pdir, color, raydir, campos, camrot, bg_color, near, far, c2w_nearest, campos_nearest,
                intrinsic_nearest, images_nearest, gt_image, zero_epsilon=1e-3, w_color=1.0, w_zero_one=1e-4, frame_weight=None, tmid=None,
                ray_drop=None, assign_grads=True, frame_weight_nearest=None, blur_kernels=None, patch_num=None, patch_size=None, patch_layout="grid",
-               w2c_nearest=None, accumulate_grads=True):
+               w2c_nearest=None, accumulate_grads=True, device_frame_weight=None):
     """forward -> [blur module] -> shipped loss terms -> backward of one ray batch as groups of library launches queued back to back: no autograd
     graph, no masked copies, nothing read back to the host -- the body of the reference's optimize_parameters before its optimizer steps
     (models/neural_points_volumetric_model.py:202-214: self.forward(); loss_total.backward(), with compute_losses of
@@ -465,7 +465,9 @@ def train_step(path, aggregator, xyz, emb, conf, pdir, color, raydir, campos, ca
     The reference has TWO frame-weight inputs and so has this call: `frame_weight` is the dataset item's scalar that multiplies loss_total
     (models/base_rendering_model.py:1205; a Python float or a CPU tensor -- converted once, no device read in the step) and
     `frame_weight_nearest` [V] / [1,V] the per-reference-view weights of the image-feature merge under downweight_blurry_feats
-    (models/aggregators/point_aggregators.py:1203), a device tensor that only the forward / backward calls read.
+    (models/aggregators/point_aggregators.py:1203), a device tensor that only the forward / backward calls read.  `device_frame_weight` [1] float32
+    on the device takes the place of `frame_weight` (left None) with no host read: the loss kernels read it, as in CapturedTrainStep --
+    frames.BatchSampler's `frame_weight` output goes here.
 
     emb/conf/pdir/color and the aggregator's parameters are read as they are; with assign_grads their .grad fields are set (or added to,
     as autograd does -- also under TrainPath.reuse_outputs, where a .grad is then a private copy of the step's buffer, never the buffer the next
@@ -474,7 +476,7 @@ def train_step(path, aggregator, xyz, emb, conf, pdir, color, raydir, campos, ca
     cloud = PointCloud(xyz, emb.detach(), conf.detach(), pdir.detach(), color.detach())
     out, S, pg, ag = _queue_step(path, cloud, raydir, campos, camrot, bg_color, near, far, c2w_nearest, campos_nearest, intrinsic_nearest, images_nearest,
                                  gt_image, zero_epsilon, w_color, w_zero_one, frame_weight, tmid, ray_drop, frame_weight_nearest,
-                                 _blur_arg(blur_kernels, patch_num, patch_size, patch_layout), w2c_nearest)
+                                 _blur_arg(blur_kernels, patch_num, patch_size, patch_layout), w2c_nearest, device_frame_weight=device_frame_weight)
     out["_saved"] = S
     if assign_grads:
         _assign_grads(aggregator, emb, conf, pdir, color, pg, ag, accumulate=bool(accumulate_grads), cached=bool(path.reuse_outputs))

@@ -23,7 +23,8 @@
  *              hnr_last_error, hnr_points_bounds, hnr_grid_* (build / destroy / stats / bytes), hnr_march_query, hnr_ray_compact*, hnr_point_records,
  *              hnr_image_features*, hnr_render_forward* (+ workspace sizing), hnr_render_train_forward / _backward / _backward_depth (+ sizing),
  *              hnr_shipped_loss*, hnr_composite, hnr_ray_depth, hnr_ray_march, hnr_voxel_downsample*, hnr_probe_select, hnr_blur_*,
- *              hnr_frame_metrics* (and the HNR_FM_* row layout), hnr_depth_fuse*, hnr_range_crop*, hnr_nearest_view, hnr_point_view_attrs.
+ *              hnr_frame_metrics* (and the HNR_FM_* row layout), hnr_depth_fuse*, hnr_range_crop*, hnr_nearest_view, hnr_point_view_attrs,
+ *              hnr_frame_batch*, hnr_frame_item.
  *   STAGE   -- everything else (hnr_chain_*, hnr_mlp3_*, hnr_merge*, hnr_mixup_stage, hnr_proj_*, hnr_h2*, hnr_linear_*, hnr_gather_*, hnr_ksum*,
  *              hnr_segment_*, hnr_absmax, hnr_div_probe, hnr_image_features_bwd_bbox, ...): the individual stages the two single-call entries are built from.  They are exported so
  *              that tests/ can compare every stage with the oracle and so that tools/ can time them alone; their signatures, workspace layouts and
@@ -875,6 +876,75 @@ int hnr_nearest_view(const float *d_xyz, int64_t N, const float *d_campos, const
  * outputs may be NULL (not all); d_feat / C / Hl / Wl are read only with d_out_feat. */
 int hnr_point_view_attrs(const float *d_xyz, int64_t n, const float *w2c, const float *c2w, const float *cam_pos_cam, const float *K, int H, int W,
                          const float *d_feat, int C, int Hl, int Wl, float *d_out_feat, float *d_out_dir, uint8_t *d_out_mask, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The per-step data path: a device-resident frame bank and the ray batch drawn from it (csrc/frames.hip).  Replaces the dataset item of the
+ * reference, data/scannet_ft_dataset.py:736-976 (data/nerf_synth360_ft_dataset.py:643-800), image decoding aside: per step the reference draws pixel
+ * coordinates with numpy (:892-949), builds raydir with get_dtu_raydir (data/data_utils.py:57-71), gathers gt_image (:957) and uploads the V nearest
+ * frames as float32 (:821-855).  Stream-ordered, nothing is allocated, nothing is read back, at most three launches; every fp32 operation is rounded
+ * on its own in the order given and the random words are Philox4x32-10 (tests/frames_ref.py restates all of it; the GPU tests compare bits).
+ *
+ * hnr_frame_bank -- what stays on the device for one split of a scene:
+ *   d_images [F,H,W,3] uint8 (decoded frames) or float32 (images_f32 = 1: the synthetic set's white-composited images, nerf_synth360_ft_dataset.py:536);
+ *   d_c2w, d_w2c [F,4,4]; d_intrinsic [3,3], or [F,3,3] with intrinsic_per_frame = 1; d_weight [F] = train_weight_list ** weight_exp (:756-759, :834);
+ *   d_angle [F] = vid / total_num_image * 2 pi (:830). */
+typedef struct {
+    const void *d_images;
+    const float *d_c2w, *d_w2c, *d_intrinsic, *d_weight, *d_angle;
+    int images_f32, F, H, W, intrinsic_per_frame;
+} hnr_frame_bank;
+
+/* hnr_frame_batch_params -- how the pixels of a batch are drawn (scannet_ft_dataset.py:892-949; m = margin = opt.edge_filter):
+ *   words w0..w3 = Philox4x32-10(counter = (step low, step high, purpose, index), key = (seed low, seed high));
+ *   randint(u, lo, hi) = lo + (((uint64) u * (uint32)(hi - lo)) >> 32);
+ *   HNR_FRAMES_RANDOM   size^2 rays; purpose 0, index = ray: px = randint(w0, m, W - m), py = randint(w1, m, H - m)                       (:899-907)
+ *   HNR_FRAMES_PATCH    the dilated mode with patch_num = 1, patch_size = size, dilation 1                                               (:893-898)
+ *   HNR_FRAMES_DILATED  (patch_num * patch_size)^2 rays; purpose 1, index = patch pi * patch_num + pj: d = randint(w0, dilation_lo, dilation_hi + 1),
+ *                       x0 = randint(w1, m, W - m - (patch_size - 1) d), y0 = randint(w2, m, H - m - (patch_size - 1) d); pixel (row a, column b) of
+ *                       the patch is (x0 + d b, y0 + d a) at grid position (pi * patch_size + a, pj * patch_size + b), rays row-major       (:917-940)
+ *   bg_random           purpose 2, index 0: white when w0 >= 2^31, else black (:964-969); otherwise bg_color
+ *   ray (get_dtu_raydir) x = ((px + 0.5) - K02) / K00, y = ((py + 0.5) - K12) / K11, dir[c] = (x R[c][0] + y R[c][1]) + R[c][2], R = c2w[:3,:3];
+ *                       dir_norm: dir / (sqrt((dx^2 + dy^2) + dz^2) + 1e-5)
+ *   pixels              gt_image = frame[(int) py][(int) px]; uint8 v -> (float) v / 255.0f (a division, as ToTensor); float32 banks are copied
+ *   downweight_blurry_feats: frame_weight_nearest = the reference bank's weights (:832-834), ones otherwise. */
+#define HNR_FRAMES_RANDOM  0
+#define HNR_FRAMES_PATCH   1
+#define HNR_FRAMES_DILATED 2
+typedef struct {
+    int mode, size, patch_num, patch_size, dilation_lo, dilation_hi, margin, dir_norm, bg_random, downweight_blurry_feats;
+    float bg_color[3];
+    uint64_t seed;
+} hnr_frame_batch_params;
+
+/* hnr_frame_batch_out -- the item's tensors; a NULL pointer is an output that is not wanted (nothing is written for it):
+ *   per ray       d_raydir [R,3], d_pixel_idx [R,2] (x, y) float32, d_gt_image [R,3]
+ *   camera        d_campos [3], d_camrot [3,3], d_c2w [4,4], d_intrinsic [3,3]
+ *   views         d_c2w_nearest, d_w2c_nearest [V,4,4], d_campos_nearest [V,3], d_intrinsic_nearest [3,3] (of the first view), d_images_nearest [V,H,W,3]
+ *                 float32 (16-byte aligned), d_frame_weight_nearest [V], d_vid_angle_nearest [V]
+ *   scalars       d_frame_weight [1], d_bg_color [3], d_frame_row [1] int32, d_patch_table [patch_num^2,3] int32 (d, x0, y0; patch / dilated) */
+typedef struct {
+    float *d_raydir, *d_pixel_idx, *d_gt_image, *d_campos, *d_camrot, *d_c2w, *d_intrinsic, *d_c2w_nearest, *d_w2c_nearest, *d_campos_nearest,
+          *d_intrinsic_nearest, *d_images_nearest, *d_frame_weight_nearest, *d_vid_angle_nearest, *d_frame_weight, *d_bg_color;
+    int32_t *d_frame_row, *d_patch_table;
+} hnr_frame_batch_out;
+
+/* hnr_frame_batch -- the batch of step d_step[0]: the frame is row d_schedule[d_step[0] % n_schedule] of `target`, its V reference views are rows
+ * d_nearest[row * V ..] of `reference` (the same bank, or a test split's train bank; same H, W), and d_step[0] (uint64) advances by one, exactly once.
+ * The frame number and the counter are read on the device: the call can be captured in a hipGraph on one stream and replayed.
+ * d_scratch: hnr_frame_batch_scratch_bytes(mode, patch_num) bytes (negative: bad arguments), private to the call sequence of one sampler.
+ * Ranges that are empty for the frame size (margin, patch reach) and rows outside a bank are HNR_ERR_BADARG / the caller's to validate
+ * (the kernels clamp a bad row to 0 rather than read outside the bank). */
+int64_t hnr_frame_batch_scratch_bytes(int mode, int patch_num);
+int hnr_frame_batch(const hnr_frame_bank *target, const hnr_frame_bank *reference, const int32_t *d_nearest, int V, const hnr_frame_batch_params *p,
+                    const int32_t *d_schedule, int n_schedule, uint64_t *d_step, const hnr_frame_batch_out *out, void *d_scratch, int64_t scratch_bytes,
+                    void *stream);
+
+/* hnr_frame_item -- the same item for an explicit frame `row` (a host int), no counter, no random words: with d_pixels [n_rays,2] float32 (x, y)
+ * those pixels (fractional ones truncate for gt_image, as :957; a pixel outside the frame gets gt_image = 0), with d_pixels = NULL every pixel minus
+ * `margin` in scan-line order, n_rays = (W - 2 margin)(H - 2 margin) (`no_crop`, :946-949).  bg_color: 3 host floats.  d_scratch: 16 bytes. */
+int hnr_frame_item(const hnr_frame_bank *target, const hnr_frame_bank *reference, const int32_t *d_nearest, int V, int row, const float *d_pixels,
+                   int64_t n_rays, int margin, int dir_norm, const float *bg_color, int downweight_blurry_feats, const hnr_frame_batch_out *out,
+                   void *d_scratch, int64_t scratch_bytes, void *stream);
 
 #ifdef __cplusplus
 }
