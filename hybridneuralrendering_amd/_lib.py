@@ -196,6 +196,8 @@ SIGNATURES = {
                              ctypes.POINTER(FrameBatchOut), _P, ctypes.c_int64, _P]),
     "hnr_frame_item": (_I, [ctypes.POINTER(FrameBankC), ctypes.POINTER(FrameBankC), _P, _I, _I, _P, ctypes.c_int64, _I, _I, ctypes.POINTER(_F), _I,
                             ctypes.POINTER(FrameBatchOut), _P, ctypes.c_int64, _P]),
+    # growth schedule: ray-miss loss + the table of the worst frames, one launch per step (csrc/rank.hip)
+    "hnr_ray_miss_rank": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _P, _P]),
     "hnr_blur_gray_patches": (_I, [_P, _P, _I, _I, _P, _P]),
     "hnr_blur_gray_patches_bwd": (_I, [_P, _I, _I, _P, _P]),
     "hnr_blur_apply": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),

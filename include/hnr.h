@@ -24,7 +24,7 @@
  *              hnr_image_features*, hnr_render_forward* (+ workspace sizing), hnr_render_train_forward / _backward / _backward_depth (+ sizing),
  *              hnr_shipped_loss*, hnr_composite, hnr_ray_depth, hnr_ray_march, hnr_voxel_downsample*, hnr_probe_select, hnr_blur_*,
  *              hnr_frame_metrics* (and the HNR_FM_* row layout), hnr_depth_fuse*, hnr_range_crop*, hnr_nearest_view, hnr_point_view_attrs,
- *              hnr_frame_batch*, hnr_frame_item.
+ *              hnr_frame_batch*, hnr_frame_item, hnr_ray_miss_rank.
  *   STAGE   -- everything else (hnr_chain_*, hnr_mlp3_*, hnr_merge*, hnr_mixup_stage, hnr_proj_*, hnr_h2*, hnr_linear_*, hnr_gather_*, hnr_ksum*,
  *              hnr_segment_*, hnr_absmax, hnr_div_probe, hnr_image_features_bwd_bbox, ...): the individual stages the two single-call entries are built from.  They are exported so
  *              that tests/ can compare every stage with the oracle and so that tools/ can time them alone; their signatures, workspace layouts and
@@ -945,6 +945,29 @@ int hnr_frame_batch(const hnr_frame_bank *target, const hnr_frame_bank *referenc
 int hnr_frame_item(const hnr_frame_bank *target, const hnr_frame_bank *reference, const int32_t *d_nearest, int V, int row, const float *d_pixels,
                    int64_t n_rays, int margin, int dir_norm, const float *bg_color, int downweight_blurry_feats, const hnr_frame_batch_out *out,
                    void *d_scratch, int64_t scratch_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Growth schedule, the per-step part: the step's ray-miss loss and the table of the worst frames (prob_mode 0), ONE launch of one workgroup.
+ * Replaces the `ray_miss_coarse_raycolor` item of compute_losses (models/base_rendering_model.py:1147-1159) and rank_ray_miss /
+ * update_rank_ray_miss (models/mvs_points_volumetric_model.py:154-172), which cost two host synchronisations per step.
+ *
+ *   L = (sum over the rays with ray_mask == 0, over 3 channels, of (color - gt)^2) / 3   -- l2loss(masked_output, masked_gt) * masked_gt.shape[1];
+ *       0 when no ray missed (and for R == 0).  Every difference and square is one rounded fp32 operation; the sums are fp64 in a fixed order
+ *       (lane t of 256 takes rays t, t + 256, ...; a butterfly within each wave; the four waves in order); the division by 3 is fp64, rounded
+ *       once to fp32.  d_color is the colour the loss kernels were given (the blur module's output when it ran, else coarse_raycolor); the rows
+ *       of coarse_raycolor at rays with ray_mask == 0 hold bg_color (composite_kernel, csrc/aggregate.hip, writes it there), so L measures how
+ *       far the ground truth of the missed rays is from the background.
+ *   n >= 2: d_ids [n] / d_losses [n] are the table (top_ray_miss_ids / top_ray_miss_loss).  If a slot holds d_frame_id[0] its loss becomes
+ *       max(L, old); otherwise slot n - 1 is overwritten with (d_frame_id[0], L) -- also when L == 0 or smaller than every entry, as the
+ *       reference does.  Then the table is sorted by loss, descending and STABLE (equal losses keep their slot order; torch.sort leaves it open).
+ *   n == 1 (prob_num_step == 1): d_losses[0] = max(L, d_losses[0]); d_ids is not touched and may be NULL.
+ *   A non-finite L is written to d_miss_out and leaves the table as it was (the reference would carry the NaN into the table).
+ *   d_miss_out [2] (may be NULL) = {L, number of missed rays}.  d_frame_id [1] is read on the device (frames.BatchSampler's frame_row).
+ * Allocates nothing, reads nothing back, capturable.  HNR_ERR_BADARG, nothing written: n < 1, n > 1024, R < 0, R > 2^24, a NULL pointer other
+ * than d_miss_out (and d_ids when n == 1). */
+int hnr_ray_miss_rank(const float *d_color /*[R,3]*/, const float *d_gt /*[R,3]*/, const int8_t *d_ray_mask /*[R]*/, int R,
+                      const int32_t *d_frame_id /*[1], device*/, int32_t *d_ids /*[n]*/, float *d_losses /*[n]*/, int n,
+                      float *d_miss_out /*[2] or NULL: loss, number of missed rays*/, void *stream);
 
 #ifdef __cplusplus
 }
