@@ -6,6 +6,7 @@
 //
 // Row order everywhere is the reference's boolean-mask order: (ray, slot, k) ascending.
 #include "hnr_common.h"
+#include "hnr_launch.h"
 
 namespace hnr {
 
@@ -1050,8 +1051,7 @@ extern "C" int hnr_image_features(const float *d_img, int V, int H, int W, const
     float *s1a = d_scratch, *s1 = s1a + (size_t)V * 6 * H1 * W1;
     float *s2a = s1 + (size_t)V * 6 * H1 * W1, *s2 = s2a + (size_t)V * 12 * H2 * W2;
     float *s3a = s2 + (size_t)V * 12 * H2 * W2, *s3 = s3a + (size_t)V * 24 * H3 * W3;
-    static int old_conv = -1;                                              // HNR_CONV_OLD=1: the one-thread-per-output-element kernel (A/B, tests)
-    if (old_conv < 0) { const char *e = getenv("HNR_CONV_OLD"); old_conv = e ? atoi(e) : 0; }
+    static const int old_conv = knob("HNR_CONV_OLD", 0);                  // 1: the one-thread-per-output-element kernel (A/B, tests)
     auto conv = [&](const float *in, int Cin, int Hin, int Win, int cl, int cstride, int li, int Cout, int stride, int Hout, int Wout, float *out) {
         const int64_t total = (int64_t)V * Cout * Hout * Wout, pixels = (int64_t)V * Hout * Wout;
 #define HNR_CONV_TILE(CIN_, CT_, CL_) \

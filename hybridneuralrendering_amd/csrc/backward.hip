@@ -18,6 +18,7 @@
 #include <utility>
 
 #include "hnr_common.h"
+#include "hnr_launch.h"
 #include "train_internal.h"
 
 namespace hnr {
@@ -699,13 +700,8 @@ static int conv3x3_bwd_tile_launch(ConvTileArgs a, hipStream_t st)
     constexpr int UNITS = (COUT / 3) * CIN, SLICES = 256 / UNITS;
     constexpr size_t lds = sizeof(float) * ((size_t)COUT * DSTR + (size_t)CIN * ISTR + (DGRAD ? 9 * COUT * CIN : 0) + (SLICES > 1 ? (size_t)SLICES * COUT * CIN * 9 : 0));
     static_assert(lds <= 160 * 1024, "tile does not fit the LDS");
-    auto kern = conv3x3_bwd_tile_kernel<CIN, COUT, S, TO, DGRAD, IN_CL>;
-    static PerDeviceOnce attr;
-    if (attr.first()) HNR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     a.tiles_x = (a.Wout + TO - 1) / TO; a.tiles_y = (a.Hout + TO - 1) / TO;
-    kern<<<a.tiles_x * a.tiles_y * a.V, 256, lds, st>>>(a);
-    HNR_LAUNCH_CHECK();
-    return HNR_OK;
+    return launch_lds<conv3x3_bwd_tile_kernel<CIN, COUT, S, TO, DGRAD, IN_CL>>(a.tiles_x * a.tiles_y * a.V, 256, (int)lds, st, a);
 }
 
 // ------------------------------------------------------------------------------------------------ gather

@@ -34,6 +34,7 @@
 #include <stdlib.h>
 
 #include "chain_defs.h"
+#include "hnr_launch.h"
 
 namespace hnr {
 
@@ -694,7 +695,13 @@ __global__ __launch_bounds__(1024) void chain_plan_scan_kernel(const int32_t *__
 
 using namespace hnr;
 
-static int chain_num_cus() { return device_num_cus(); }
+// HNR_CHAIN_RT = 4: the compiler-scheduled one-workgroup-per-CU kernel of this file (the training forward runs its activation-keeping form);
+// anything else: the weight-stationary pipelined kernel (csrc/chain_ws.hip), the default
+static bool chain_ws_selected()
+{
+    static const bool ws = knob("HNR_CHAIN_RT", 16) != 4;
+    return ws;
+}
 
 extern "C" int64_t hnr_chain_packed_bytes(void) { return (int64_t)CH_WBYTES + CH_META_FLOATS * 4; }
 
@@ -733,14 +740,8 @@ extern "C" int hnr_chain_pack(const float *d_w_b1_0_dist, int ldw0, const float 
 extern "C" int hnr_chain_classes(void)
 {
     // the 4- and 2-slot classes need the weight-stationary kernel (the default); HNR_CHAIN_CLASSES = 0 / 1 limits them
-    static int on = -1;
-    if (on < 0) {
-        const char *e = getenv("HNR_CHAIN_RT"), *c = getenv("HNR_CHAIN_CLASSES");
-        const bool ws = !e || atoi(e) != 4;
-        const int want = c ? atoi(c) : 2;
-        on = ws ? (want < 0 ? 0 : want > 2 ? 2 : want) : 0;
-    }
-    return on;
+    static const int want = knob("HNR_CHAIN_CLASSES", 2, 0, 2);
+    return chain_ws_selected() ? want : 0;
 }
 
 extern "C" int hnr_chain_plan(const int32_t *d_work, const int32_t *d_sample_pidx, int64_t *d_counts, int K, int max_items, int classes,
@@ -856,31 +857,19 @@ extern "C" int hnr_chain_forward(const void *d_workspace, const float *d_point_t
     a.xp = (const char *)d_workspace; a.aux = (const char *)d_workspace + (size_t)blocks * 4 * CH_XP_GROUP;
     a.dsig = reinterpret_cast<float *>((char *)d_workspace + (size_t)blocks * 4 * (CH_XP_GROUP + CH_AUX_GROUP));
     a.ptab = d_point_table; a.ldt = ldt; a.wimg = (const char *)d_packed;
-    { static int tab0 = -1; if (tab0 < 0) { const char *e = getenv("HNR_CHAIN_PROBE_TAB0"); tab0 = e ? atoi(e) : 0; } if (tab0) a.ldt = 0; }      // probe: every row reads table row 0 (what the gather's latency costs; results are garbage)
+    { static const int tab0 = knob("HNR_CHAIN_PROBE_TAB0", 0); if (tab0) a.ldt = 0; }      // probe: every row reads table row 0 (what the gather's latency costs; results are garbage)
     a.counts = reinterpret_cast<const unsigned long long *>(d_counts);
     a.X5 = d_X5; a.ld5 = ld5; a.sigma = d_sigma; a.slope = slope; a.cap_samples = cap_samples; a.dbg = d_dbg; a.dbg_layer = dbg_layer;
-    const int n_cu = chain_num_cus();
+    const int n_cu = device_num_cus();
     hipStream_t st = (hipStream_t)stream;
-    // HNR_CHAIN_RT = 4: the compiler-scheduled one-workgroup-per-CU kernel of this file (the training forward runs its activation-keeping form);
-    // default: the weight-stationary pipelined kernel (csrc/chain_ws.hip)
-    static int rt_mode = 0;
-    if (rt_mode == 0) { const char *e = getenv("HNR_CHAIN_RT"); rt_mode = (e && atoi(e) == 4) ? 4 : 16; }
     a.skew = 0; a.uidx = nullptr; a.hmax = nullptr; a.x5max = nullptr; a.row_u = nullptr; a.ucap = 0; a.hbits = nullptr; a.hbits_stride = 0;
     for (int l = 0; l < 4; ++l) { a.H[l] = nullptr; a.ldh[l] = 0; }
-    static PerDeviceOnce attr_once;
-    if (attr_once.first()) {
-        HNR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(chain_kernel<4, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, ch_lds_bytes(4)));
-        HNR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(chain_kernel<4, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, ch_lds_bytes(4)));
-        HNR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(chain_kernel<4, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, ch_lds_bytes(4)));
-    }
     const int tiles = cdiv(cap_samples, 16), grid = tiles < n_cu ? tiles : n_cu;
-    if (rt_mode == 16)                                                      // weight-stationary pipelined kernel (csrc/chain_ws.hip)
+    if (chain_ws_selected())
         return launch_chain_ws(a, grid, st, (d_dbg && dbg_layer <= -3 && dbg_layer >= -7) ? -dbg_layer : (d_dbg && dbg_layer < 0) ? 2 : d_dbg ? 1 : 0);
-    if (d_dbg && dbg_layer < 0) chain_kernel<4, 2><<<grid, 256, ch_lds_bytes(4), st>>>(a);      // probe: per-phase cycle counts of block 0
-    else if (d_dbg) chain_kernel<4, 1><<<grid, 256, ch_lds_bytes(4), st>>>(a);
-    else chain_kernel<4, 0><<<grid, 256, ch_lds_bytes(4), st>>>(a);
-    HNR_LAUNCH_CHECK();
-    return HNR_OK;
+    if (!d_dbg) return launch_lds<chain_kernel<4, 0>>(grid, 256, ch_lds_bytes(4), st, a);
+    if (dbg_layer >= 0) return launch_lds<chain_kernel<4, 1>>(grid, 256, ch_lds_bytes(4), st, a);
+    return launch_lds<chain_kernel<4, 2>>(grid, 256, ch_lds_bytes(4), st, a);                                   // probe: per-phase cycle counts of block 0
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -910,19 +899,15 @@ int chain_forward_train(const void *d_workspace, const float *d_point_table, int
     a.X5 = d_X5; a.ld5 = ld5; a.sigma = d_sigma; a.slope = slope; a.cap_samples = cap_samples; a.dbg = nullptr; a.dbg_layer = 0; a.skew = 0;
     for (int l = 0; l < 4; ++l) { a.H[l] = d_H[l]; a.ldh[l] = ldh[l]; }
     a.uidx = d_uidx; a.hmax = d_hmax; a.x5max = d_x5max; a.row_u = d_row_u; a.ucap = ucap; a.hbits = d_hbits; a.hbits_stride = hbits_stride;
-    const int n_cu = chain_num_cus();
+    const int n_cu = device_num_cus();
     const int tiles = cdiv(cap_samples, 16), grid = tiles < n_cu ? tiles : n_cu;
     // The weight-stationary pipelined kernel in its activation-keeping form (csrc/chain_ws.hip, chain_ws_kernel<8>: the render path's kernel + eight
     // 16-B stores per pass and lane; same arithmetic, same results bit for bit) when the row -> table-row map is there and every kept buffer's byte
     // offsets fit 31 bits; HNR_TRAIN_CHAIN_WS=0: the layer-by-layer kernel below
-    static int use_ws = -1;
-    if (use_ws < 0) { const char *e = getenv("HNR_TRAIN_CHAIN_WS"); use_ws = e ? atoi(e) : 1; }
+    static const int use_ws = knob("HNR_TRAIN_CHAIN_WS", 1);
     bool fits = d_row_u != nullptr && d_hmax != nullptr;
     for (int l = 0; l < 4; ++l) fits = fits && d_H[l] != nullptr && (long long)blocks * 128 * ldh[l] * 4 < 0x7fffffffLL && (ldh[l] & 3) == 0;
     if (use_ws && fits) return launch_chain_ws(a, grid, (hipStream_t)stream, 8);
-    HNR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(chain_kernel<4, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, ch_lds_bytes(4)));
-    chain_kernel<4, 3><<<grid, 256, ch_lds_bytes(4), (hipStream_t)stream>>>(a);
-    HNR_LAUNCH_CHECK();
-    return HNR_OK;
+    return launch_lds<chain_kernel<4, 3>>(grid, 256, ch_lds_bytes(4), (hipStream_t)stream, a);
 }
 }  // namespace hnr

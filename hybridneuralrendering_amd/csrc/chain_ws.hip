@@ -29,6 +29,7 @@
 #include <utility>
 
 #include "chain_defs.h"
+#include "hnr_launch.h"
 
 namespace hnr {
 
@@ -818,33 +819,23 @@ __global__ __launch_bounds__(128) void chain_sigma_kernel(ChainArgs a)
 
 int launch_chain_ws(const ChainArgs &a, int grid, hipStream_t st, int mode)
 {
-    static PerDeviceOnce attr_once;
-    if (attr_once.first()) {
-        HNR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(chain_ws_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, cw_lds_bytes()));
-        HNR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(chain_ws_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, cw_lds_bytes()));
-        HNR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(chain_ws_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, cw_lds_bytes()));
-        HNR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(chain_ws_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, cw_lds_bytes()));
-#ifdef HNR_CHAIN_WS_PROBES
-        HNR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(chain_ws_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, cw_lds_bytes()));
-        HNR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(chain_ws_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, cw_lds_bytes()));
-        HNR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(chain_ws_kernel<5>), hipFuncAttributeMaxDynamicSharedMemorySize, cw_lds_bytes()));
-        HNR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(chain_ws_kernel<6>), hipFuncAttributeMaxDynamicSharedMemorySize, cw_lds_bytes()));
-        HNR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(chain_ws_kernel<7>), hipFuncAttributeMaxDynamicSharedMemorySize, cw_lds_bytes()));
+    int rc;
+#define HNR_CHAIN_WS_MODE(M_) launch_lds<chain_ws_kernel<M_>>(grid, 256, cw_lds_bytes(), st, a)
+    switch (mode) {
+    default: rc = HNR_CHAIN_WS_MODE(0); break;
+    case 1: rc = HNR_CHAIN_WS_MODE(1); break;
+    case 2: rc = HNR_CHAIN_WS_MODE(2); break;
+    case 8: rc = HNR_CHAIN_WS_MODE(8); break;
+#ifdef HNR_CHAIN_WS_PROBES                                       // timing probes (results are garbage): make EXTRA=-DHNR_CHAIN_WS_PROBES
+    case 3: rc = HNR_CHAIN_WS_MODE(3); break;                    // no epilogue
+    case 4: rc = HNR_CHAIN_WS_MODE(4); break;                    // no MFMAs
+    case 5: rc = HNR_CHAIN_WS_MODE(5); break;                    // epilogue without its LDS reads
+    case 6: rc = HNR_CHAIN_WS_MODE(6); break;                    // epilogue without its LDS writes
+    case 7: rc = HNR_CHAIN_WS_MODE(7); break;                    // neither
 #endif
     }
-#ifdef HNR_CHAIN_WS_PROBES                                                       // timing probes (results are garbage): make EXTRA=-DHNR_CHAIN_WS_PROBES
-    if (mode == 5) chain_ws_kernel<5><<<grid, 256, cw_lds_bytes(), st>>>(a);           // epilogue without its LDS reads
-    else if (mode == 6) chain_ws_kernel<6><<<grid, 256, cw_lds_bytes(), st>>>(a);      // epilogue without its LDS writes
-    else if (mode == 7) chain_ws_kernel<7><<<grid, 256, cw_lds_bytes(), st>>>(a);      // neither
-    else if (mode == 3) chain_ws_kernel<3><<<grid, 256, cw_lds_bytes(), st>>>(a);      // no epilogue
-    else if (mode == 4) chain_ws_kernel<4><<<grid, 256, cw_lds_bytes(), st>>>(a);      // no MFMAs
-    else
-#endif
-    if (mode == 8) chain_ws_kernel<8><<<grid, 256, cw_lds_bytes(), st>>>(a);
-    else if (mode == 2) chain_ws_kernel<2><<<grid, 256, cw_lds_bytes(), st>>>(a);
-    else if (mode == 1) chain_ws_kernel<1><<<grid, 256, cw_lds_bytes(), st>>>(a);
-    else chain_ws_kernel<0><<<grid, 256, cw_lds_bytes(), st>>>(a);
-    HNR_LAUNCH_CHECK();
+#undef HNR_CHAIN_WS_MODE
+    if (rc != HNR_OK) return rc;
     const int tiles = (a.cap_samples + 15) / 16 + 2;                        // capacity (each slot class may end in a partial tile): the kernel reads the real tile count from the device counters
     chain_sigma_kernel<<<tiles, 128, 0, st>>>(a);
     HNR_LAUNCH_CHECK();

@@ -14,6 +14,7 @@
 // Philox4x32-10: tests/frames_ref.py restates all of it in NumPy and the GPU tests compare bits.  Nothing is allocated, nothing is read back; three
 // launches on the caller's stream.
 #include "hnr_common.h"
+#include "hnr_launch.h"
 
 namespace hnr {
 

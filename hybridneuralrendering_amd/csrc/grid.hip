@@ -22,6 +22,7 @@
 #include <utility>
 
 #include "hnr_common.h"
+#include "hnr_launch.h"
 
 namespace hnr {
 
@@ -476,8 +477,7 @@ static int build_impl(hnr_grid *g, const float *d_xyz, int n, hipStream_t st)
     DevBuf<uint4> rec;
     DevBuf<uint32_t> cell_total;
     // slack behind the compact tables (HNR_GRID_SLACK percent, default 25): room for hnr_grid_grow to append lists / runs without reallocating
-    int slack_pct = 25;
-    if (const char *es = getenv("HNR_GRID_SLACK")) { slack_pct = atoi(es); if (slack_pct < 0) slack_pct = 0; if (slack_pct > 400) slack_pct = 400; }
+    const int slack_pct = knob_now("HNR_GRID_SLACK", 25, 0, 400);
     auto with_slack = [&](uint64_t n_items, uint64_t floor_items) -> uint64_t { return n_items + (n_items * (uint64_t)slack_pct) / 100 + (slack_pct ? floor_items : 0); };
     const uint64_t occ_cap = with_slack(n_occ, 1024), pts_cap = with_slack((uint64_t)n_listed, 4096);
     GB_CHECK(start.alloc(n_occ)); GB_CHECK(end.alloc(n_occ));
@@ -512,7 +512,7 @@ static int build_impl(hnr_grid *g, const float *d_xyz, int n, hipStream_t st)
     // ---- brick-level "anything near" mask for the march's coarse level (GridView::brick_near).  Only with HNR_MARCH_TWO_LEVEL=1: the two-level march
     //      returns the same samples (tests/test_query_gpu.py runs it) and is NOT faster on the bench frame (0.242 vs 0.233 ms: a coarse probe costs what
     //      a fine one does -- the three exact divisions -- and too many groups of a cluttered room lie within two bricks of the mask)
-    if (const char *e2 = getenv("HNR_MARCH_TWO_LEVEL"); e2 && atoi(e2) != 0) {
+    if (knob_now("HNR_MARCH_TWO_LEVEL", 0) != 0) {
         DevBuf<uint8_t> nearb;
         GB_CHECK(nearb.alloc(n_words));
         const GridView v1 = g->view();
@@ -524,9 +524,8 @@ static int build_impl(hnr_grid *g, const float *d_xyz, int n, hipStream_t st)
     //      fit 32-bit indices; HNR_NB_LISTS=0 skips them (the k-NN then walks the 27 cells itself: knn3_kernel).
     int64_t nb_bytes = 0;
     {
-        const char *e = getenv("HNR_NB_LISTS");
         const int64_t n_dil = (int64_t)h_scal[2];
-        if (!(e && atoi(e) == 0) && p->P <= 63 && n_dil > 0 && n_listed > 0 && 27ll * n_listed + 8ll * n_dil < (1ll << 31)) {
+        if (knob_now("HNR_NB_LISTS", 1) != 0 && p->P <= 63 && n_dil > 0 && n_listed > 0 && 27ll * n_listed + 8ll * n_dil < (1ll << 31)) {
             DevBuf<uint32_t> dcnt, dprefix, nb_cnt, nb_start;
             DevBuf<uint4> drec;
             DevBuf<uint2> nbr;

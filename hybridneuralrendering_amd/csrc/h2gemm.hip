@@ -19,6 +19,7 @@
 #include <type_traits>
 
 #include "chain_defs.h"
+#include "hnr_launch.h"
 
 namespace hnr {
 
@@ -348,11 +349,9 @@ __device__ __forceinline__ f16x8 h2_tr_frag(const char *plane, int rs, int col0,
 // the next stage: the conversion VALU work and the LDS writes ride under the wave's own MFMAs, the HBM latency under a whole iteration.
 // The loop body is STRAIGHT-LINE code: every predicate is folded into an address or a select (a load or an MFMA inside a branch makes the
 // compiler's wait-count pass wait for vmcnt(0), i.e. for the loads it has just issued: no lookahead, 1.9 TB/s).
-// BIASV (K = 256: no spare column in 8 tiles, and a ninth tile costs 16 more accumulator registers per wave than the file has): the bias gradient
-// is summed on the side in fp32 from the dZ rows as they pass through the staging registers.
 // DEPTH = 1 (NT = 8, KT = 9: the largest accumulator set leaves no room for a second register set): one set, loaded at the top of the iteration
 // for block i + 1 and converted in the iteration's last rounds.
-template <int NT, int KT, int WK, int BIASV = 0, int DEPTH = 2>
+template <int NT, int KT, int WK, int DEPTH = 2>
 __global__ __launch_bounds__(512, 1) void h2wgrad_kernel(H2WgradArgs a)
 {
     constexpr int WN = NT;
@@ -382,18 +381,12 @@ __global__ __launch_bounds__(512, 1) void h2wgrad_kernel(H2WgradArgs a)
     // staging slots of this thread: slot it = float4 (row, columns c .. c + 3) of the dZ tile or of the X tile of a block; (row, c, tile) do not
     // depend on the block.  Per slot: the element offset inside a block's rows, the LDS offset of its planes, the masks of its four values.
     float4 stg[DEPTH][NLD];
-    constexpr int NZS = BIASV ? (RB * Z4) / 512 : 0;                           // BIASV: the first NZS slots of every thread are dZ slots
-    static_assert(!BIASV || (RB * Z4) % 512 == 0, "BIASV needs whole dZ slots");
-    float bsum[NZS > 0 ? NZS : 1][4];
-#pragma unroll
-    for (int i = 0; i < (NZS > 0 ? NZS : 1); ++i) bsum[i][0] = bsum[i][1] = bsum[i][2] = bsum[i][3] = 0.f;
     int s_rc[NLD], s_lds[NLD];                                                 // row << 16 | first column read; LDS offset of the high plane
     unsigned s_keep[NLD];                                                      // bit e: value e is a real column (< N or < K); bit 4: the X tile; bit 8 + e: value e is the bias column
     const long long seg_extra = a.n_seg > 1 ? a.seg_stride - n_unit : 0;       // physical row = m + (segment of m) * seg_extra
 #pragma unroll
     for (int it = 0; it < NLD; ++it) {
         const int idx = (tid + 512 * it < RB * (Z4 + X4)) ? tid + 512 * it : tid + 512 * (it - 1);      // no slot left: this thread repeats its previous one
-        const bool has = true;
         const bool isx = idx >= RB * Z4;
         const int id2 = isx ? idx - RB * Z4 : idx, per = isx ? X4 : Z4;
         const int row = id2 / per, c = 4 * (id2 - row * per);
@@ -402,8 +395,8 @@ __global__ __launch_bounds__(512, 1) void h2wgrad_kernel(H2WgradArgs a)
         s_rc[it] = (row << 16) | (inrow ? c : 0);
         unsigned keep = 0;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) keep |= (has && inrow && c + e < lim) ? (1u << e) : 0u;
-        if (isx) { keep |= 16u; if (!BIASV && has && (a.K >> 2) == (c >> 2)) keep |= 256u << (a.K & 3); }
+        for (int e = 0; e < 4; ++e) keep |= (inrow && c + e < lim) ? (1u << e) : 0u;
+        if (isx) { keep |= 16u; if ((a.K >> 2) == (c >> 2)) keep |= 256u << (a.K & 3); }
         s_keep[it] = keep;
         s_lds[it] = (isx ? 2 * PZ : 0) + row * (isx ? RSX : RSZ) + c * 2;
     }
@@ -421,10 +414,6 @@ __global__ __launch_bounds__(512, 1) void h2wgrad_kernel(H2WgradArgs a)
     auto store_slot = [&](char *base, long long blk, int it, const float4 &v) {
         const unsigned keep = (blk * RB + (s_rc[it] >> 16) < M) ? s_keep[it] : (s_keep[it] & ~15u);
         const float sc = (keep & 16u) ? sx : sz;
-        if (BIASV && it < NZS) {
-            bsum[it < NZS ? it : 0][0] += (keep & 1u) ? v.x : 0.f; bsum[it < NZS ? it : 0][1] += (keep & 2u) ? v.y : 0.f;
-            bsum[it < NZS ? it : 0][2] += (keep & 4u) ? v.z : 0.f; bsum[it < NZS ? it : 0][3] += (keep & 8u) ? v.w : 0.f;
-        }
         unsigned ph0, pm0, ph1, pm1;
         split2h((keep & 1u) ? __fmul_rn(v.x, sc) : 0.f, (keep & 2u) ? __fmul_rn(v.y, sc) : 0.f, ph0, pm0);
         split2h((keep & 4u) ? __fmul_rn(v.z, sc) : 0.f, (keep & 8u) ? __fmul_rn(v.w, sc) : 0.f, ph1, pm1);
@@ -497,25 +486,9 @@ __global__ __launch_bounds__(512, 1) void h2wgrad_kernel(H2WgradArgs a)
         __syncthreads();
     }
     // ---- this workgroup's partial: [NP = 32 NT][KP], true units (scales removed); accumulator (reg r, lane): row n = (r & 3) + 8 (r >> 2) + 4 (lane >> 5), column lane & 31
-    constexpr int NP = 32 * NT, KP = 32 * KT, LDP = KP + (BIASV ? 32 : 0);
+    constexpr int NP = 32 * NT, KP = 32 * KT, LDP = KP;
     float *out = a.partial + (size_t)blockIdx.x * NP * LDP;
     const float dsz = pow2f(-kz), dsx = pow2f(-kx);
-    if (BIASV) {
-        // column sums of dZ: a thread's slot it covers row (tid + 512 it) / Z4 and columns 4 ((tid + 512 it) % Z4) .. + 3, the same columns in every block
-        float *sb = reinterpret_cast<float *>(lds);                            // [RB rows][WZ columns] (the stages are free: the loop's last barrier is behind)
-#pragma unroll
-        for (int it = 0; it < NZS; ++it) {
-            const int idx = tid + 512 * it, row = idx / Z4, c = 4 * (idx - row * Z4);
-            *reinterpret_cast<float4 *>(sb + row * WZ + c) = make_float4(bsum[it][0], bsum[it][1], bsum[it][2], bsum[it][3]);
-        }
-        __syncthreads();
-        if (tid < WZ) {
-            float t = 0.f;
-#pragma unroll
-            for (int r = 0; r < RB; ++r) t += sb[r * WZ + tid];
-            out[(size_t)tid * LDP + a.K] = t;                                   // (K = KP here)
-        }
-    }
 #pragma unroll
     for (int u = 0; u < KTW; ++u) {
         const int kt = wk * KTW + u;
@@ -530,7 +503,7 @@ __global__ __launch_bounds__(512, 1) void h2wgrad_kernel(H2WgradArgs a)
     }
 }
 
-// The 256-wide weight gradient (NT = 8, KT = 9) with the fp32 rows staged through LDS by DMA.  h2wgrad_kernel<8, 9, 1, 0, 1> has room for ONE register
+// The 256-wide weight gradient (NT = 8, KT = 9) with the fp32 rows staged through LDS by DMA.  h2wgrad_kernel<8, 9, 1, 1> has room for ONE register
 // set of staged rows beside its 144 accumulator registers, so a block's loads have one iteration of MFMAs (864 cycles) to arrive and the kernel ran at
 // the latency of its loads: 3.2 us per 16-row block, 2.3 - 2.5 TB/s (32 KiB in flight per CU).  Here the rows of block i + 2 go global -> LDS (raw fp32,
 // `global_load_lds_dwordx4`: no registers) while block i is multiplied, and block i + 1 is converted to its fp16 planes AFTER the MFMAs of the iteration:
@@ -925,8 +898,6 @@ __global__ __launch_bounds__(256) void h2wgrad_reduce_kernel(const float *__rest
 
 using namespace hnr;
 
-static int h2_num_cus() { return device_num_cus(); }
-
 extern "C" int64_t hnr_h2lin_packed_bytes(int K)
 {
     if (K <= 0 || K > 288) return -1;
@@ -966,8 +937,7 @@ int h2lin_dgrad_bits(const float *d_dZ, int ldz, int64_t M_cap, const int64_t *d
 {
     if (!d_side_bits || N != 256 || (M_cap & 31)) { set_error("h2lin_dgrad_bits: needs the bit words, N = 256 and whole 32-row tiles"); return HNR_ERR_BADARG; }
     // K = 256: the weight-stationary kernel (csrc/h2lin_ws.hip; bit-identical results).  HNR_H2LIN_WS=0: the streaming kernel below (A/B timing)
-    static int use_ws = -1;
-    if (use_ws < 0) { const char *e = getenv("HNR_H2LIN_WS"); use_ws = e ? atoi(e) : 1; }
+    static const int use_ws = knob("HNR_H2LIN_WS", 1);
     if (use_ws && K == 256 && d_dZ && d_packed && d_C && ldz >= 256 && !(ldz & 3) && ldc >= 256 && !(ldc & 3) && !((uintptr_t)d_dZ & 15) && !((uintptr_t)d_C & 15) &&
         !((uintptr_t)d_packed & 15) && slope > 0.f && slope < 1.f && (long long)M_cap * ldc * 4 < 0x7fffffffLL)
         return launch_h2lin_ws(d_dZ, ldz, M_cap, d_m, d_packed, slope, d_side_bits, d_C, ldc, d_absmax, stream);
@@ -1002,21 +972,13 @@ int hnr::h2lin_launch(const float *d_A, int lda, int64_t M_cap, const int64_t *d
     a.A = d_A; a.lda = lda; a.d_m = reinterpret_cast<const long long *>(d_m); a.M_cap = M_cap; a.n_seg = n_seg; a.seg_stride = seg_stride;
     a.wimg = (const char *)d_packed; a.N = N; a.K = K;
     a.mode = mode; a.act = act; a.slope = slope; a.side = d_side; a.lds_ = ld_side; a.side_bits = d_side_bits; a.C = d_C; a.ldc = ldc; a.absmax = d_absmax;
-    static int spread = -1;
-    if (spread < 0) { const char *e = getenv("HNR_H2LIN_SPREAD"); spread = e ? atoi(e) : 1; }
+    static const int spread = knob("HNR_H2LIN_SPREAD", 1);
     a.spread = spread;
     const int S = (K + 15) / 16;
     const int64_t tiles = (M_cap * n_seg + 63) / 64;
-    const int wgs = 2 * h2_num_cus(), grid = (int)(tiles < wgs ? tiles : wgs);
+    const int wgs = 2 * device_num_cus(), grid = (int)(tiles < wgs ? tiles : wgs);
     hipStream_t st = (hipStream_t)stream;
-#define HNR_H2LIN_CASE(S_)                                                                                                              \
-    if (S == S_) {                                                                                                                      \
-        constexpr int ldsb = S_ * (4096 + 32) + 64 * 4;                                                                                        \
-        HNR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(h2lin_kernel<S_>), hipFuncAttributeMaxDynamicSharedMemorySize, ldsb)); \
-        h2lin_kernel<S_><<<grid, 256, ldsb, st>>>(a);                                                                                   \
-        HNR_LAUNCH_CHECK();                                                                                                             \
-        return HNR_OK;                                                                                                                  \
-    }
+#define HNR_H2LIN_CASE(S_) if (S == S_) return launch_lds<h2lin_kernel<S_>>(grid, 256, S_ * (4096 + 32) + 64 * 4, st, a);
     HNR_H2LIN_CASE(3) HNR_H2LIN_CASE(4) HNR_H2LIN_CASE(8) HNR_H2LIN_CASE(14) HNR_H2LIN_CASE(16)
 #undef HNR_H2LIN_CASE
     set_error("hnr_h2lin: no kernel for K = %d (%d k steps); built: 3, 4, 8, 14, 16 k steps of 16", K, S);
@@ -1050,7 +1012,7 @@ extern "C" int64_t hnr_h2wgrad_scratch_bytes(int N, int K)
     if (N <= 0 || N > 256 || K <= 0 || K > 287) return -1;
     int NT, KT;
     h2wgrad_cfg(N, K, &NT, &KT);
-    return (int64_t)h2_num_cus() * (32 * NT) * (32 * KT + 32) * 4;
+    return (int64_t)device_num_cus() * (32 * NT) * (32 * KT + 32) * 4;
 }
 
 extern "C" int hnr_h2wgrad(const float *d_dZ, int ldz, const float *d_X, int ldx, int64_t M_cap, const int64_t *d_m, int n_seg, int64_t seg_stride, int N, int K,
@@ -1069,45 +1031,34 @@ extern "C" int hnr_h2wgrad(const float *d_dZ, int ldz, const float *d_X, int ldx
     a.N = N; a.K = K;
     a.zmax = d_absmax_z; a.xmax = d_absmax_x; a.partial = (float *)d_scratch; a.dbg = 0;
 #ifdef HNR_WG_DBG
-    { const char *e = getenv("HNR_WG_DBG"); a.dbg = e ? atoi(e) : 0; }
+    a.dbg = knob_now("HNR_WG_DBG", 0);
 #endif
     const int64_t blocks = (M_cap * n_seg + 15) / 16;
-    const int n_cu = h2_num_cus();
+    const int n_cu = device_num_cus();
     int grid = (int)((blocks + 15) / 16 < n_cu ? (blocks + 15) / 16 : n_cu);           // at least 8 row blocks per workgroup: every workgroup writes (and the reduction reads) a whole partial
     if (grid < 1) grid = 1;
     hipStream_t st = (hipStream_t)stream;
+    int rc = HNR_OK;
 #define HNR_H2WG_CASE(NT_, KT_)                                                                                                         \
-    if (NT == NT_ && KT == KT_ && !biasv && !(NT_ == 8 && KT_ == 9)) {                                                                                                       \
+    if (NT == NT_ && KT == KT_) {                                                                                                       \
         constexpr int rsz = ((32 * NT_ * 2 - 64 + 255) & ~255) + 64, rsx = ((32 * KT_ * 2 - 64 + 255) & ~255) + 64;                     \
-        constexpr int ldsb = 3 * (2 * 16 * rsz + 2 * 16 * rsx);                                                                    \
-        static PerDeviceOnce once_;                                                                                                     \
-        if (once_.first()) HNR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(h2wgrad_kernel<NT_, KT_, 8 / NT_>), hipFuncAttributeMaxDynamicSharedMemorySize, ldsb)); \
-        h2wgrad_kernel<NT_, KT_, 8 / NT_><<<grid, 512, ldsb, st>>>(a);                                                                  \
+        rc = launch_lds<h2wgrad_kernel<NT_, KT_, 8 / NT_>>(grid, 512, 3 * (2 * 16 * rsz + 2 * 16 * rsx), st, a);                        \
     }
-    const bool biasv = false;
     if (NT == 8 && KT == 9) {
         constexpr int rsz = ((32 * 8 * 2 - 64 + 255) & ~255) + 64, rsx = ((32 * 9 * 2 - 64 + 255) & ~255) + 64, ldsb = 3 * (2 * 16 * rsz + 2 * 16 * rsx);
         constexpr int lds_dma = 2 * (2 * 16 * rsz + 2 * 16 * rsx) + 2 * 16 * (256 + 288) * 4;     // two plane stages + two raw blocks
-        static int use_dma = -1;
-        if (use_dma < 0) { const char *e = getenv("HNR_WGRAD_DMA"); use_dma = e ? atoi(e) : 1; }   // 0: the register-staged kernel (A/B timing)
-        static PerDeviceOnce once89;
-        if (once89.first()) {
-            HNR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(h2wgrad_kernel<8, 9, 1, 0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, ldsb));
-            HNR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(h2wgrad_dma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_dma));
-            HNR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(h2wgrad_dma256_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_dma));
-            HNR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(h2wgrad_dma256_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_dma));
-        }
+        static const int use_dma = knob("HNR_WGRAD_DMA", 1);                                      // 0: the register-staged kernel (A/B timing)
         // N = 256, plain rows: the kernel specialised for the training step's 256-wide layers (HNR_WGRAD_DMA=2: the general DMA kernel instead, A/B timing)
         const bool fast = use_dma == 1 && N == 256 && n_seg == 1 && ldz >= 256 && ldx >= 256 && M_cap < 0x7ffff000LL;
-        if (fast && K == 256) h2wgrad_dma256_kernel<false><<<grid, 512, lds_dma, st>>>(a);
-        else if (fast) h2wgrad_dma256_kernel<true><<<grid, 512, lds_dma, st>>>(a);
-        else if (use_dma) h2wgrad_dma_kernel<<<grid, 512, lds_dma, st>>>(a);
-        else h2wgrad_kernel<8, 9, 1, 0, 1><<<grid, 512, ldsb, st>>>(a);
+        if (!use_dma) rc = launch_lds<h2wgrad_kernel<8, 9, 1, 1>>(grid, 512, ldsb, st, a);
+        else if (!fast) rc = launch_lds<h2wgrad_dma_kernel>(grid, 512, lds_dma, st, a);
+        else if (K == 256) rc = launch_lds<h2wgrad_dma256_kernel<false>>(grid, 512, lds_dma, st, a);
+        else rc = launch_lds<h2wgrad_dma256_kernel<true>>(grid, 512, lds_dma, st, a);
     }
-    HNR_H2WG_CASE(8, 9) HNR_H2WG_CASE(8, 8) HNR_H2WG_CASE(8, 2) HNR_H2WG_CASE(4, 9) HNR_H2WG_CASE(4, 5) HNR_H2WG_CASE(2, 9) HNR_H2WG_CASE(2, 5) HNR_H2WG_CASE(2, 3) HNR_H2WG_CASE(2, 2)
+    HNR_H2WG_CASE(8, 8) HNR_H2WG_CASE(8, 2) HNR_H2WG_CASE(4, 9) HNR_H2WG_CASE(4, 5) HNR_H2WG_CASE(2, 9) HNR_H2WG_CASE(2, 5) HNR_H2WG_CASE(2, 3) HNR_H2WG_CASE(2, 2)
 #undef HNR_H2WG_CASE
-    HNR_LAUNCH_CHECK();
-    const int NP = 32 * NT, LDP = 32 * KT + (biasv ? 32 : 0);
+    if (rc != HNR_OK) return rc;
+    const int NP = 32 * NT, LDP = 32 * KT;
     const int total = N * (K + 1);
     h2wgrad_reduce_kernel<<<(total + 63) / 64, 256, 0, st>>>((const float *)d_scratch, grid, reinterpret_cast<const long long *>(d_m), M_cap, NP, LDP, N, K,
                                                               d_dW, lddw, d_db, accumulate, n_seg, seg_stride);

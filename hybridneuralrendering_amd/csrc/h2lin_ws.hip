@@ -16,6 +16,7 @@
 #include <utility>
 
 #include "chain_defs.h"
+#include "hnr_launch.h"
 
 namespace hnr {
 
@@ -332,14 +333,12 @@ int launch_h2lin_ws(const float *d_dZ, int ldz, int64_t M_cap, const int64_t *d_
     H2LinWsArgs a;
     a.A = d_dZ; a.lda = ldz; a.d_m = reinterpret_cast<const long long *>(d_m); a.M_cap = M_cap; a.wimg = (const char *)d_packed; a.slope = slope;
     a.side_bits = d_side_bits; a.C = d_C; a.ldc = ldc; a.absmax = d_absmax;
-    static PerDeviceOnce once;
-    if (once.first()) HNR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(h2lin_ws_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, HW_LDS));
     const int64_t tiles = (M_cap + 31) / 32;
     const int n_cu = device_num_cus(), grid = (int)(tiles < n_cu ? tiles : n_cu);
-    h2lin_ws_kernel<<<grid, 256, HW_LDS, (hipStream_t)stream>>>(a);
-    HNR_LAUNCH_CHECK();
+    const int rc = launch_lds<h2lin_ws_kernel>(grid, 256, HW_LDS, (hipStream_t)stream, a);
+    if (rc != HNR_OK) return rc;
 #ifdef HNR_WS_PROBE
-    if (getenv("HNR_WS_PROBE_PRINT")) {
+    if (knob_now("HNR_WS_PROBE_PRINT", 0)) {
         long long hp[40];
         if (hipDeviceSynchronize() == hipSuccess && hipMemcpyFromSymbol(hp, HIP_SYMBOL(g_hw_probe), sizeof(hp)) == hipSuccess && hp[17] > 0) {
             fprintf(stderr, "h2lin_ws probe: %lld iterations; cycles per k step:", hp[17]);

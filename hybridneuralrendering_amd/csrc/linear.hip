@@ -17,6 +17,7 @@
 #include <stdlib.h>
 
 #include "hnr_common.h"
+#include "hnr_launch.h"
 
 namespace hnr {
 
@@ -715,11 +716,9 @@ static int linear_launch(const float *d_A, int lda, const float *d_Wp, const flo
     // persistent workgroups: 2 per CU fit (registers + 2 x LDS double buffers); they stride over the M tiles
     const int n_cu = device_num_cus();
     const int n_mtiles = cdiv(M, 128);
-    static int dbg = -1;
-    if (dbg < 0) { const char *e = getenv("HNR_LINEAR_DBG"); dbg = e ? atoi(e) : 0; }
+    static const int dbg = knob("HNR_LINEAR_DBG", 0);
     // column pairing (8-B epilogue accesses) needs even strides / column counts and 8-B aligned bases
-    static int pair_env = -1;
-    if (pair_env < 0) { const char *e = getenv("HNR_LINEAR_PAIR"); pair_env = e ? atoi(e) : 1; }
+    static const int pair_env = knob("HNR_LINEAR_PAIR", 1);
     const bool pair = pair_env && N >= 128 && !(N & 1) && !(ldc & 1) && !((uintptr_t)d_C & 7) &&
                       (!d_R || (!(ldr & 1) && !(r_cols & 1) && !((uintptr_t)d_R & 7)));
     const int r_mode_x = r_mode;

@@ -10,6 +10,7 @@
 #include <stdlib.h>
 
 #include "hnr_h2.h"
+#include "hnr_launch.h"
 
 namespace hnr {
 
@@ -1102,7 +1103,7 @@ extern "C" int hnr_mlp3_pack(int n_layers, const float *const *d_W, const int *l
 static void mlp3_probe_print(hipStream_t st, int n_layers, int K0)
 {
 #ifdef HNR_MLP_PROBE
-    if (getenv("HNR_MLP_PROBE_PRINT")) {
+    if (knob_now("HNR_MLP_PROBE_PRINT", 0)) {
         (void)hipStreamSynchronize(st);
         long long h[24];
         if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_mlp_probe), sizeof(h)) == hipSuccess && h[20] > 0) {
@@ -1186,12 +1187,9 @@ static int mlp3_forward_impl(const float *d_A, int lda, int64_t M_cap, const int
         constexpr int ldsb = smax * (RT_ * 2048 + ML_PAD) + 32 * RT_ * 4 * 4 + 32 * RT_ * 4;                                                       \
         const int64_t tiles = (M_cap + 32 * RT_ - 1) / (32 * RT_);                                                                      \
         const int wgs = mlp3_wgs_per_cu(S0_, RT_, 0) * n_cu, grid = (int)(tiles < wgs ? tiles : wgs);                                              \
-        static PerDeviceOnce attr;                                                                                                      \
-        if (attr.first()) HNR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(mlp3_kernel<S0_, S1_, S2_, S3_, 0, RT_>), hipFuncAttributeMaxDynamicSharedMemorySize, ldsb)); \
-        mlp3_kernel<S0_, S1_, S2_, S3_, 0, RT_><<<grid, 256, ldsb, st>>>(a);                                                             \
+        const int rc = launch_lds<mlp3_kernel<S0_, S1_, S2_, S3_, 0, RT_>>(grid, 256, ldsb, st, a);                                        \
         mlp3_probe_print(st, n_layers, K[0]);                                                                                          \
-        HNR_LAUNCH_CHECK();                                                                                                             \
-        return HNR_OK;                                                                                                                  \
+        return rc;                                                                                                                      \
     }
     HNR_MLP3_CASE(18, 8, 8, 0, 2)     // color_feature_branch: 280 -> 128 -> 128 -> 128 (32-row tiles with 3 or 4 workgroups per CU: 2.63 / 2.61 vs 2.45 ms)
     HNR_MLP3_CASE(18, 8, 8, 8, 2)     // the same + tail 128 -> 64: the colour-feature columns of aux_merge_weight_block.0, once per sample
@@ -1234,34 +1232,24 @@ extern "C" int hnr_merge_stage(const float *d_sample_loc_w, const int32_t *d_vs_
     const int n_cu = device_num_cus();
     // 64-row tiles (16 samples x 4 views), four workgroups per CU: the stage is a chain of dependent memory round trips (sample -> projection ->
     // pixel -> feature rows) and barriers, so it is the number of co-resident workgroups that keeps a CU busy (128-row tiles, two per CU: HNR_MERGE_RT=4)
-    static int rt_sel = 0;
-    if (rt_sel == 0) { const char *e = getenv("HNR_MERGE_RT"); rt_sel = e ? atoi(e) : 1; if (rt_sel != 4 && rt_sel != 2) rt_sel = 1; }
+    static const int rt_env = knob("HNR_MERGE_RT", 1);
+    const int rt_sel = rt_env == 4 || rt_env == 2 ? rt_env : 1;
     // (the wave-per-tile kernel moves the colour-feature and mix-up rows as 16-B chunks, and writes the two padding columns 90, 91 of the mix-up rows)
     const bool wp_ok = ldcf >= 48 && !(ldcf & 3) && !((uintptr_t)d_CF & 15) && ld7 >= 92 && !(ld7 & 3) && !((uintptr_t)d_X7 & 15);
     if (rt_sel == 1 && wp_ok) {
         const int64_t wtiles = ((int64_t)cap_samples + 7) / 8, wg_tiles = (wtiles + MW_WAVES - 1) / MW_WAVES;
         const int g = (int)(wg_tiles < (int64_t)n_cu ? wg_tiles : (int64_t)n_cu);
-        static PerDeviceOnce attr_wp;
-        if (attr_wp.first()) HNR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(merge_wp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, MW_LDS));
-        merge_wp_kernel<<<g, 64 * MW_WAVES, MW_LDS, (hipStream_t)stream>>>(a);
-        HNR_LAUNCH_CHECK();
-        return HNR_OK;
+        return launch_lds<merge_wp_kernel>(g, 64 * MW_WAVES, MW_LDS, (hipStream_t)stream, a);
     }
     const int rt_k = rt_sel == 4 ? 4 : 2;
     const int rows = 32 * rt_k, wgs = mlp3_wgs_per_cu(3, rt_k, 1);
     const int64_t tiles = ((int64_t)cap_samples * 4 + rows - 1) / rows;
     const int grid = (int)(tiles < (int64_t)wgs * n_cu ? tiles : (int64_t)wgs * n_cu);
     const int ldsb = 4 * (rt_k * 2048 + ML_PAD) + rows * 4 * 4 + rows * 4 + rows * 48 * 4 + 3 * rows * 4 + 128 * 4;
-    static PerDeviceOnce attr;
-    if (attr.first()) {
-        HNR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(mlp3_kernel<3, 4, 4, 0, 1, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * ML_SLOT + 128 * 4 * 4 + 128 * 4 + 128 * 48 * 4 + 3 * 128 * 4 + 128 * 4));
-        HNR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(mlp3_kernel<3, 4, 4, 0, 1, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (2 * 2048 + ML_PAD) + 64 * 4 * 4 + 64 * 4 + 64 * 48 * 4 + 3 * 64 * 4 + 128 * 4));
-    }
-    if (rt_k == 4) mlp3_kernel<3, 4, 4, 0, 1, 4><<<grid, 256, ldsb, (hipStream_t)stream>>>(a);
-    else mlp3_kernel<3, 4, 4, 0, 1, 2><<<grid, 256, ldsb, (hipStream_t)stream>>>(a);
+    const int rc = rt_k == 4 ? launch_lds<mlp3_kernel<3, 4, 4, 0, 1, 4>>(grid, 256, ldsb, (hipStream_t)stream, a)
+                             : launch_lds<mlp3_kernel<3, 4, 4, 0, 1, 2>>(grid, 256, ldsb, (hipStream_t)stream, a);
     mlp3_probe_print((hipStream_t)stream, 3, 48);
-    HNR_LAUNCH_CHECK();
-    return HNR_OK;
+    return rc;
 }
 
 extern "C" int hnr_mixup_stage(const float *d_X7, int ld7, const void *d_mlp_mx, const float *d_CF, int ldcf, const float *d_w_fin, const float *d_b_fin,
@@ -1283,9 +1271,5 @@ extern "C" int hnr_mixup_stage(const float *d_X7, int ld7, const void *d_mlp_mx,
     const int n_cu = device_num_cus();
     const int64_t tiles = ((int64_t)cap_samples + 31) / 32, wg_tiles = (tiles + MX_WAVES - 1) / MX_WAVES;
     const int g = (int)(wg_tiles < (int64_t)n_cu ? wg_tiles : (int64_t)n_cu);
-    static PerDeviceOnce attr;
-    if (attr.first()) HNR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(mixfinal_wp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, MX_LDS));
-    mixfinal_wp_kernel<<<g, 64 * MX_WAVES, MX_LDS, (hipStream_t)stream>>>(a);
-    HNR_LAUNCH_CHECK();
-    return HNR_OK;
+    return launch_lds<mixfinal_wp_kernel>(g, 64 * MX_WAVES, MX_LDS, (hipStream_t)stream, a);
 }

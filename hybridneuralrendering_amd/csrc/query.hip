@@ -10,11 +10,13 @@
 //
 // Results are bit-identical to oracle/query_oracle.c (same visiting order, same strict-< replacement
 // and first-max scan), so sample_pidx matches slot for slot.
+#include <limits.h>
 #include <stdlib.h>
 
 #include <type_traits>
 
 #include "hnr_common.h"
+#include "hnr_launch.h"
 
 namespace hnr {
 
@@ -1218,12 +1220,10 @@ extern "C" int hnr_march_query(const hnr_grid *g, const float *d_campos, const f
     if (q->R == 0) return HNR_OK;
     const GridView v = g->view();
     unsigned long long *cnt = reinterpret_cast<unsigned long long *>(d_counts);
-    static int march_probe = -1;                                 // HNR_MARCH_PROBE=1: time the march kernel's fixed part alone (tools; results are empty)
-    if (march_probe < 0) { const char *e = getenv("HNR_MARCH_PROBE"); march_probe = e ? atoi(e) : 0; }
+    static const int march_probe = knob("HNR_MARCH_PROBE", 0);  // 1: time the march kernel's fixed part alone (tools; results are empty)
     // a wave works through ~8 rays (wave launches, not instructions, bounded the one-ray-per-wave form: 0.63 waves per cycle over the whole chip); enough
     // workgroups that the last, partial round of residency is a few per cent of the launch (ONE workgroup per resident slot left a third of the CUs idle in a second round)
-    static int rays_per_wave = -1;
-    if (rays_per_wave < 0) { const char *e = getenv("HNR_MARCH_RAYS_PER_WAVE"); rays_per_wave = e ? atoi(e) : 8; if (rays_per_wave < 1) rays_per_wave = 1; }
+    static const int rays_per_wave = knob("HNR_MARCH_RAYS_PER_WAVE", 8, 1, INT_MAX);
     // (small batches: one ray per wave until there are ~32 waves per CU)
     int rpw = q->R / (device_num_cus() * 32);
     rpw = rpw < 1 ? 1 : (rpw > rays_per_wave ? rays_per_wave : rpw);
@@ -1244,8 +1244,7 @@ extern "C" int hnr_march_query(const hnr_grid *g, const float *d_campos, const f
     worklist_kernel<<<nb, 1024, 0, st>>>(d_ray_nsamp, q->R, q->SR, block_sums, nb, d_work, cnt);
     HNR_LAUNCH_CHECK();
     // K = 8 with a 3x3x3 neighbourhood (every shipped config): the pipelined kernel (HNR_KNN=1: the generic one-cell-at-a-time kernel)
-    static int knn_sel = -1;
-    if (knn_sel < 0) { const char *e = getenv("HNR_KNN"); knn_sel = e ? atoi(e) : 8; }
+    static const int knn_sel = knob("HNR_KNN", 8);
     if (q->knn_order == 1 && !(q->K == 8 && layers <= 2)) {
         set_error("hnr_march_query: knn_order = 1 (canonical neighbour order) is built for K = 8 with a 3x3x3 neighbourhood (K=%d)", q->K);
         return HNR_ERR_BADARG;
@@ -1265,8 +1264,7 @@ extern "C" int hnr_march_query(const hnr_grid *g, const float *d_campos, const f
         const int bin = knn_sel == 5 ? 0 : (knn_sel == 8 ? 2 : (knn_sel == 10 ? 3 : 1));
         {   // workgroups per CU of the persistent k-NN kernels (HNR_KNN_WG_PER_CU; 8 = what knn_blocks caps at).  Measured for the quad kernel: 6 (what its
             // 26 KB of LDS let a CU hold at once) 0.423 ms, 8 0.35 ms -- the workgroups that wait for a slot fill the tail of the first ones
-            static int wg_per_cu = -1;
-            if (wg_per_cu < 0) { const char *e = getenv("HNR_KNN_WG_PER_CU"); wg_per_cu = e ? atoi(e) : 8; if (wg_per_cu < 1) wg_per_cu = 1; }
+            static const int wg_per_cu = knob("HNR_KNN_WG_PER_CU", 8, 1, INT_MAX);
             const int cap = device_num_cus() * wg_per_cu;
             if (knn_sel != 5) blocks = cdiv(max_items, 256) < cap ? cdiv(max_items, 256) : cap;
             if (blocks > knn_blocks(max_items)) blocks = knn_blocks(max_items);          // (the per-workgroup counters' scratch is sized for that many)
@@ -1292,8 +1290,7 @@ extern "C" int hnr_march_query(const hnr_grid *g, const float *d_campos, const f
     }
     if (q->K == 8 && layers <= 2 && packable && (knn_sel != 1 || q->knn_order == 1)) {
         const int blocks = knn_blocks(max_items);
-        static int probe_pass1 = -1;                             // HNR_KNN_PROBE_PASS1=1: time the cell lookups alone (tools/probe_query.py; results are empty)
-        if (probe_pass1 < 0) { const char *e = getenv("HNR_KNN_PROBE_PASS1"); probe_pass1 = e ? atoi(e) : 0; }
+        static const int probe_pass1 = knob("HNR_KNN_PROBE_PASS1", 0);   // 1: time the cell lookups alone (tools/probe_query.py; results are empty)
         if (q->knn_order == 1)
             knn3_kernel<8, 1><<<blocks, 256, 0, st>>>(v, d_work, d_sample_loc_w, q->SR, q->radius2, probe_pass1 ? 0 : layers, d_sample_pidx, d_ray_mask, cnt, block_stats);
         else

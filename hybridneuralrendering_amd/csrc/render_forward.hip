@@ -8,23 +8,11 @@
 // that capacity is reported in *d_status (device) instead of being discovered on the host.  No host read, no allocation.
 #include <limits.h>
 
-#include "hnr_common.h"
+#include "render_internal.h"
 
 using namespace hnr;
 
 namespace {
-
-struct Carver {
-    char *base; size_t off, cap; bool ok;
-    template <class T> T *take(size_t n)
-    {
-        off = (off + 255) & ~(size_t)255;
-        T *p = reinterpret_cast<T *>(base + off);
-        off += n * sizeof(T);
-        if (base && off > cap) ok = false;
-        return base ? p : nullptr;
-    }
-};
 
 struct Layout {
     int32_t *work, *vs_item, *vs_off, *vs_cnt, *scratch, *row_s;
@@ -88,18 +76,12 @@ extern "C" int hnr_render_forward(const hnr_grid *grid, const hnr_render_params 
     if (!ok) { set_error("hnr_render_forward: workspace too small (%lld bytes, need %lld)", (long long)workspace_bytes, (long long)hnr_render_workspace_bytes(p)); return HNR_ERR_BADARG; }
     hipStream_t st = (hipStream_t)stream;
     const int R = p->R, SR = p->SR, K = p->K, cap = p->cap_samples, V = p->V;
-    int rc, stage = 0;
-    auto mark = [&]() -> int {
-        if (o->stage_events && o->stage_events[stage]) { if (hipEventRecord((hipEvent_t)o->stage_events[stage], st) != hipSuccess) return 1; }
-        ++stage;
-        return 0;
-    };
-#define HNR_MARK() do { if (mark()) { set_error("hnr_render_forward: hipEventRecord failed"); return HNR_ERR_HIP; } } while (0)
+    int rc;
+    StageMarker mark{"hnr_render_forward: hipEventRecord failed", o->stage_events, st};
+#define HNR_MARK() do { if ((rc = mark()) != HNR_OK) return rc; } while (0)
     HNR_MARK();
     // ---- query (march + first-SR compaction + k-NN), un-padded outputs
-    hnr_query_params q;
-    q.R = R; q.D = p->D; q.SR = SR; q.K = K; q.radius2 = p->radius2; q.tmid_stride = p->tmid_stride; q.pad_outputs = 0; q.knn_order = p->knn_order;
-    for (int i = 0; i < 3; ++i) q.kernel_size[i] = p->kernel_size[i];
+    const hnr_query_params q = query_params(*p, 0);
     if ((rc = hnr_march_query(grid, cam->d_campos, cam->d_raydir, cam->d_tmid, &q, o->d_sample_pidx, o->d_sample_loc_w, o->d_ray_nsamp, o->d_ray_mask,
                               L.work, o->d_counts, stream)) != HNR_OK) return rc;
     HNR_MARK();
@@ -120,8 +102,7 @@ extern "C" int hnr_render_forward(const hnr_grid *grid, const hnr_render_params 
     HNR_MARK();
     // ---- per-sample MLPs
     // colour feature 280 -> 128 -> 128 -> 128, and on its tail the colour-feature columns of aux_merge_weight_block.0 (128 -> 64, once per sample)
-    const int cfN[4] = {128, 128, 128, 64}, cfK[4] = {280, 128, 128, 128}, act1110[4] = {1, 1, 1, 0}, act111[3] = {1, 1, 1};
-    if ((rc = hnr_mlp3_forward(L.X5, 280, cap, o->d_counts, HNR_CNT_SAMPLES_VALID, 1, 0, w->d_mlp_cf, V > 0 ? 4 : 3, cfN, cfK, act1110, w->slope, nullptr, nullptr, 0,
+    if ((rc = hnr_mlp3_forward(L.X5, 280, cap, o->d_counts, HNR_CNT_SAMPLES_VALID, 1, 0, w->d_mlp_cf, V > 0 ? 4 : 3, CF_N, CF_K, CF_ACT, w->slope, nullptr, nullptr, 0,
                                L.CF, 128, L.pre, 64, stream)) != HNR_OK) return rc;
     HNR_MARK();
     if (V > 0 && vw->featmap_ready) HNR_HIP_CHECK(hipStreamWaitEvent(st, (hipEvent_t)vw->featmap_ready, 0));      // the feature map may have been built on another stream
@@ -136,8 +117,7 @@ extern "C" int hnr_render_forward(const hnr_grid *grid, const hnr_render_params 
         if ((rc = hnr_proj_rows(o->d_sample_loc_w, L.vs_item, o->d_counts, vw->d_w2c, vw->d_intrinsic, cam->d_campos, vw->d_campos_nearest, vw->d_featmap,
                                 V, vw->H, vw->W, L.CF, 128, cap, L.X6, 48, L.vmask, L.row_s, stream)) != HNR_OK) return rc;
         HNR_MARK();
-        const int mwN[3] = {64, 64, 64}, mwK[3] = {48, 64, 64};
-        if ((rc = hnr_mlp3_forward(L.X6, 48, (int64_t)V * cap, o->d_counts, HNR_CNT_SAMPLES_VALID, V, cap, w->d_mlp_mw, 3, mwN, mwK, act111, w->slope, L.pre, L.row_s, 64,
+        if ((rc = hnr_mlp3_forward(L.X6, 48, (int64_t)V * cap, o->d_counts, HNR_CNT_SAMPLES_VALID, V, cap, w->d_mlp_mw, 3, MW_N, MW_K, MW_ACT, w->slope, L.pre, L.row_s, 64,
                                    L.M1, 64, nullptr, 0, stream)) != HNR_OK) return rc;
         HNR_MARK();
         if ((rc = hnr_merge(L.X6, 48, L.M1, 64, w->d_mw_last_w, w->d_mw_last_b, L.vmask, vw->d_frame_w, L.CF, 128, o->d_counts, V, cap, L.X7, 92,

@@ -19,6 +19,8 @@
 #include "chain_defs.h"
 #include <stdlib.h>
 
+#include "hnr_launch.h"
+#include "render_internal.h"
 #include "train_internal.h"
 
 using namespace hnr;
@@ -26,18 +28,6 @@ using namespace hnr;
 namespace {
 
 // ---------------------------------------------------------------------------------------------------------------- workspace
-struct Carver {
-    char *base; size_t off, cap; bool ok;
-    template <class T> T *take(size_t n)
-    {
-        off = (off + 255) & ~(size_t)255;
-        T *p = reinterpret_cast<T *>(base + off);
-        off += n * sizeof(T);
-        if (base && off > cap) ok = false;
-        return base ? p : nullptr;
-    }
-};
-
 enum {  // slots of the abs-max table (uint32 bit patterns): scales of the weight-gradient GEMMs
     AM_H1 = 0, AM_X3, AM_H3, AM_H4, AM_ONE, AM_T1, AM_T2, AM_CF, AM_M1, AM_M2, AM_M3, AM_Y1, AM_Y2, AM_Y3, AM_X5, AM_X6, AM_X7, AM_E,
     AM_gY3, AM_dY2, AM_dY1, AM_gZ3m, AM_dM2, AM_dM1, AM_gpre, AM_gCF, AM_dT2, AM_dT1, AM_gZ4, AM_dZ3, AM_dZ2, AM_dZ1, AM_gTu, AM_N
@@ -88,10 +78,9 @@ Layout carve(void *ws, size_t ws_bytes, const hnr_train_params *p, bool *ok)
     L.amax = c.take<uint32_t>(AM_N);
     L.chain_ws = c.take<char>((size_t)hnr_chain_workspace_bytes(p->cap_samples));
     L.img_chain = c.take<char>((size_t)hnr_chain_packed_bytes());
-    const int cfK[4] = {280, 128, 128, 128}, mwK[3] = {48, 64, 64}, mxK[3] = {90, 45, 45};
-    L.img_cf = c.take<char>((size_t)hnr_mlp3_packed_bytes(4, cfK));
-    L.img_mw = c.take<char>((size_t)hnr_mlp3_packed_bytes(3, mwK));
-    L.img_mx = c.take<char>((size_t)hnr_mlp3_packed_bytes(3, mxK));
+    L.img_cf = c.take<char>((size_t)hnr_mlp3_packed_bytes(4, CF_K));
+    L.img_mw = c.take<char>((size_t)hnr_mlp3_packed_bytes(3, MW_K));
+    L.img_mx = c.take<char>((size_t)hnr_mlp3_packed_bytes(3, MX_K));
     for (int i = 0; i < IM_N; ++i) L.img[i] = c.take<char>((size_t)hnr_h2lin_packed_bytes(IM_K[i]));
     L.W0fd = c.take<float>(64 * 48);
     L.Xd = c.take<float>(rows * 64);
@@ -450,8 +439,8 @@ TrainSide &train_side()
     std::lock_guard<std::mutex> lock(mu);
     TrainSide &t = per_dev[dev];
     if (t.on < 0) {
-        const char *e = getenv("HNR_TRAIN_SIDE");
-        t.on = e ? atoi(e) : 63;                                         // see the bit list above
+        static const int side_env = knob("HNR_TRAIN_SIDE", 63);          // see the bit list above
+        t.on = side_env;
         if (t.on && (hipStreamCreateWithFlags(&t.stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&t.fork_f, hipEventDisableTiming) != hipSuccess ||
                      hipEventCreateWithFlags(&t.join_f, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&t.fork_b, hipEventDisableTiming) != hipSuccess ||
                      hipEventCreateWithFlags(&t.join_b, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&t.fork_z, hipEventDisableTiming) != hipSuccess ||
@@ -470,9 +459,10 @@ static int pack_transposed_images(const Layout &L, const hnr_train_weights *w, i
                                 w->mx_w[2], w->mx_w[1], w->mx_w[0]};
     //                         IM_TABT [224 <- 256]  B32T  B30T [256 <- 256: the H2 columns]  B12T  CF2T  CF1T  CF0T [256 <- 128]  MW2T  MW1T  MW0FDT [48 <- 64]  MW0CFT [128 <- 64]  MX2T  MX1T  MX0T [90 <- 45]
     const int64_t rs[IM_N - 1] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
-    const int64_t cs[IM_N - 1] = {284, 256, 263, 256, 128, 128, 280, 64, 64, 48, 176, 45, 45, 90};
-    const int Nn[IM_N - 1] = {224, 256, 256, 256, 128, 128, 256, 64, 64, 48, 128, 45, 45, 90};
-    const int Kk[IM_N - 1] = {256, 256, 256, 256, 128, 128, 128, 64, 64, 64, 64, 45, 45, 45};
+    // (transposed: an image's N is its layer's K and the other way round, its column stride the layer's row stride; CF0T covers X5's 256 feature columns only)
+    const int64_t cs[IM_N - 1] = {284, 256, 263, 256, CF_LD[2], CF_LD[1], CF_LD[0], MW_LD[2], MW_LD[1], MW_LD[0], CF_LD[3], MX_LD[2], MX_LD[1], MX_LD[0]};
+    const int Nn[IM_N - 1] = {224, 256, 256, 256, CF_K[2], CF_K[1], 256, MW_K[2], MW_K[1], MW_K[0], CF_K[3], MX_K[2], MX_K[1], MX_K[0]};
+    const int Kk[IM_N - 1] = {256, 256, 256, 256, CF_N[2], CF_N[1], CF_N[0], MW_N[2], MW_N[1], MW_N[0], CF_N[3], MX_N[2], MX_N[1], MX_N[0]};
     void *out[IM_N - 1];
     for (int i = 1; i < IM_N; ++i) out[i - 1] = L.img[i];
     if (V > 0) TR(hnr_h2lin_pack(IM_N - 1, W, rs, cs, Nn, Kk, nullptr, out, stream));
@@ -546,12 +536,7 @@ extern "C" int hnr_render_train_forward(const hnr_grid *grid, const hnr_train_pa
     const float sl = p->slope;
     const int64_t *dS = reinterpret_cast<const int64_t *>(L.tc + TC_S), *dU = reinterpret_cast<const int64_t *>(L.tc + TC_U);
     unsigned long long *cnt = reinterpret_cast<unsigned long long *>(o->d_counts);
-    int stage = 0;
-    auto mark = [&]() -> int {      // optional HIP events at the stage boundaries (profiling hook, as in hnr_render_forward)
-        if (o->stage_events && o->stage_events[stage]) { if (hipEventRecord((hipEvent_t)o->stage_events[stage], st) != hipSuccess) { set_error("hipEventRecord failed"); return HNR_ERR_HIP; } }
-        ++stage;
-        return HNR_OK;
-    };
+    StageMarker mark{"hipEventRecord failed", o->stage_events, st};
     TR(mark());
     // the reference-view feature pyramid needs the images and the conv weights only and is first read by the merge stage: side stream, from here
     TrainSide &side = train_side();
@@ -580,21 +565,18 @@ extern "C" int hnr_render_train_forward(const hnr_grid *grid, const hnr_train_pa
     }
     TR(hnr_chain_pack(w->block1_0_w + 224, 284, w->block1_0_b, w->block1_2_w, w->block1_2_b, w->block3_0_w, w->block3_0_b, w->block3_2_w, w->block3_2_b,
                       w->alpha_w, w->alpha_b, L.img_chain, sp));
-    const int cfN[4] = {128, 128, 128, 64}, cfK[4] = {280, 128, 128, 128}, cfld[4] = {280, 128, 128, 176};
     {
         const float *W[4] = {w->cf_w[0], w->cf_w[1], w->cf_w[2], V > 0 ? w->mw_w[0] + 45 : nullptr}, *B[4] = {w->cf_b[0], w->cf_b[1], w->cf_b[2], V > 0 ? w->mw_b[0] : nullptr};
-        TR(hnr_mlp3_pack(V > 0 ? 4 : 3, W, cfld, cfN, cfK, B, L.img_cf, sp));
+        TR(hnr_mlp3_pack(V > 0 ? 4 : 3, W, CF_LD, CF_N, CF_K, B, L.img_cf, sp));
     }
-    const int mwN[3] = {64, 64, 64}, mwK[3] = {48, 64, 64}, mwld[3] = {48, 64, 64};
     if (V > 0) {
         train_w0fd_kernel<<<(64 * 48 + 255) / 256, 256, 0, (hipStream_t)sp>>>(w->mw_w[0], L.W0fd);
         const float *W[3] = {L.W0fd, w->mw_w[1], w->mw_w[2]}, *B[3] = {nullptr, w->mw_b[1], w->mw_b[2]};
-        TR(hnr_mlp3_pack(3, W, mwld, mwN, mwK, B, L.img_mw, sp));
+        TR(hnr_mlp3_pack(3, W, MW_LD, MW_N, MW_K, B, L.img_mw, sp));
     }
-    const int mxN[3] = {45, 45, 45}, mxK[3] = {90, 45, 45}, mxld[3] = {90, 45, 45};
     {
         const float *W[3] = {w->mx_w[0], w->mx_w[1], w->mx_w[2]}, *B[3] = {w->mx_b[0], w->mx_b[1], w->mx_b[2]};
-        TR(hnr_mlp3_pack(3, W, mxld, mxN, mxK, B, L.img_mx, sp));
+        TR(hnr_mlp3_pack(3, W, MX_LD, MX_N, MX_K, B, L.img_mx, sp));
     }
     if (side.on & 8) HNR_HIP_CHECK(hipEventRecord(side.ev_w[1], side.stream_w));
     // ---- images of the TRANSPOSED weights (the backward call's input-gradient GEMMs): the same weights, so they are packed here, behind the
@@ -603,9 +585,7 @@ extern "C" int hnr_render_train_forward(const hnr_grid *grid, const hnr_train_pa
     if (side.on & 8) HNR_HIP_CHECK(hipEventRecord(side.ev_w[2], side.stream_w));
     TR(mark());
     // ---- query (jittered depths: cam->d_tmid with tmid_stride = D), padded outputs
-    hnr_query_params q;
-    q.R = R; q.D = p->D; q.SR = SR; q.K = K; q.radius2 = p->radius2; q.tmid_stride = p->tmid_stride; q.pad_outputs = 1; q.knn_order = p->knn_order;
-    for (int i = 0; i < 3; ++i) q.kernel_size[i] = p->kernel_size[i];
+    const hnr_query_params q = query_params(*p, 1);
     TR(hnr_march_query(grid, cam->d_campos, cam->d_raydir, cam->d_tmid, &q, o->d_sample_pidx, o->d_sample_loc_w, o->d_ray_nsamp, o->d_ray_mask, L.work, o->d_counts, stream));
     TR(hnr_chain_plan(L.work, o->d_sample_pidx, o->d_counts, K, R * SR, 0, L.vs_item, cap, L.scratch, stream));
     train_counts_kernel<<<1, 1, 0, st>>>(cnt, cap, o->d_status, L.tc, L.amax);
@@ -644,22 +624,21 @@ extern "C" int hnr_render_train_forward(const hnr_grid *grid, const hnr_train_pa
         return hnr_absmax(A, lda, cap, dS, nseg, segs, Nn, L.amax + slot, (void *)side.stream);
     };
     // ---- per-sample MLPs
-    const int act1110[4] = {1, 1, 1, 0}, act111[3] = {1, 1, 1}, act110[3] = {1, 1, 0};
-    TR(mlp3_forward_train(L.X5, 280, cap, o->d_counts, HNR_CNT_SAMPLES_VALID, 1, 0, L.img_cf, V > 0 ? 4 : 3, cfN, cfK, act1110, sl, nullptr, nullptr, 0, L.CF, 128,
+    TR(mlp3_forward_train(L.X5, 280, cap, o->d_counts, HNR_CNT_SAMPLES_VALID, 1, 0, L.img_cf, V > 0 ? 4 : 3, CF_N, CF_K, CF_ACT, sl, nullptr, nullptr, 0, L.CF, 128,
                           V > 0 ? L.pre : nullptr, 64, L.T1, 128, L.T2, 128, L.amax + AM_T1, stream));
     if (V > 0) {
         if (fwd_forked) HNR_HIP_CHECK(hipStreamWaitEvent(st, side.join_f, 0));      // the feature map is ready
         TR(hnr_proj_rows(o->d_sample_loc_w, L.vs_item, o->d_counts, vw->d_w2c, vw->d_intrinsic, cam->d_campos, vw->d_campos_nearest, L.fm, V, p->H, p->W, L.CF, 128, cap,
                          L.X6, 48, L.vmask, L.row_s, stream));
         TR(absmax_bwd(L.X6, 48, V, cap, 48, AM_X6));
-        TR(mlp3_forward_train(L.X6, 48, (int64_t)V * cap, o->d_counts, HNR_CNT_SAMPLES_VALID, V, cap, L.img_mw, 3, mwN, mwK, act111, sl, L.pre, L.row_s, 64, L.M3, 64,
+        TR(mlp3_forward_train(L.X6, 48, (int64_t)V * cap, o->d_counts, HNR_CNT_SAMPLES_VALID, V, cap, L.img_mw, 3, MW_N, MW_K, MW_ACT, sl, L.pre, L.row_s, 64, L.M3, 64,
                               nullptr, 0, L.M1, 64, L.M2, 64, L.amax + AM_M1, stream));
         TR(hnr_merge(L.X6, 48, L.M3, 64, w->mw_w[3], w->mw_b[3], L.vmask, vw->d_frame_w, L.CF, 128, o->d_counts, V, cap, L.X7, 92, L.ray_drop, L.vs_item, SR, stream));
     } else {
         train_x7_noviews_kernel<<<cdiv((int64_t)cap * 92, 256), 256, 0, st>>>(L.CF, L.tc + TC_S, L.X7);
     }
     TR(absmax_bwd(L.X7, 92, 1, 0, 90, AM_X7));
-    TR(mlp3_forward_train(L.X7, 92, cap, o->d_counts, HNR_CNT_SAMPLES_VALID, 1, 0, L.img_mx, 3, mxN, mxK, act110, sl, nullptr, nullptr, 0, L.Y3, 48, nullptr, 0,
+    TR(mlp3_forward_train(L.X7, 92, cap, o->d_counts, HNR_CNT_SAMPLES_VALID, 1, 0, L.img_mx, 3, MX_N, MX_K, MX_ACT, sl, nullptr, nullptr, 0, L.Y3, 48, nullptr, 0,
                           L.Y1, 48, L.Y2, 48, L.amax + AM_Y1, stream));
     TR(mark());
     TR(hnr_final_color(L.Y3, 48, L.CF, 128, w->fin_w, w->fin_b, L.sigma, L.vs_item, o->d_counts, cap, o->d_decoded, stream));
@@ -696,12 +675,7 @@ static int train_backward(const char *name, const hnr_train_params *p, const hnr
     const int64_t *dS = reinterpret_cast<const int64_t *>(L.tc + TC_S), *dM = reinterpret_cast<const int64_t *>(L.tc + TC_M8), *dU = reinterpret_cast<const int64_t *>(L.tc + TC_U);
     const int64_t rows = (int64_t)L.rows_cap, ucap = (int64_t)L.ucap;
     uint32_t *am = L.amax;
-    int stage = 0;
-    auto mark = [&]() -> int {
-        if (o->stage_events && o->stage_events[stage]) { if (hipEventRecord((hipEvent_t)o->stage_events[stage], st) != hipSuccess) { set_error("hipEventRecord failed"); return HNR_ERR_HIP; } }
-        ++stage;
-        return HNR_OK;
-    };
+    StageMarker mark{"hipEventRecord failed", o->stage_events, st};
     TR(mark());
     TrainSide &side = train_side();
     TrainSideGuard guard; guard.t = &side; guard.armed = side.on != 0;

@@ -478,6 +478,29 @@ def test_library_has_no_packed_instructions(tmp_path):
     assert not bad, bad
 
 
+def test_switch_table_lists_every_environment_variable_the_library_reads():
+    """INTEGRATION.md section 4c is the one list of the library's HNR_... switches: its names are exactly the names csrc/ passes to knob / knob_now
+    (csrc/hnr_launch.h, the only place that calls getenv)."""
+    csrc = os.path.join(ROOT, "hybridneuralrendering_amd", "csrc")
+    read, getenv_files = set(), set()
+    for d, _, files in os.walk(csrc):
+        for f in files:
+            if not f.endswith((".hip", ".h", ".cpp")):
+                continue
+            text = open(os.path.join(d, f)).read()
+            read |= set(re.findall(r'\b(?:knob|knob_now|getenv)\(\s*"(HNR_[A-Z0-9_]+)"', text))
+            if re.search(r"\bgetenv\s*\(", text):
+                getenv_files.add(f)
+    assert getenv_files == {"hnr_launch.h"}, getenv_files
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    section = doc[doc.index("## 4c. Environment switches"):]
+    section = section[:section.index("\n## ", 1)]
+    listed = re.findall(r"^\| `(HNR_[A-Z0-9_]+)` \|", section, flags=re.M)
+    assert len(listed) == len(set(listed)), "a switch is listed twice"
+    assert len(read) >= 20, "the scan of csrc/ found too few switches to be right"
+    assert set(listed) == read, (sorted(set(listed) - read), sorted(read - set(listed)))
+
+
 def test_committed_pmc_files_hold_the_kernels_bench_looks_up():
     """bench.py fills roofline.traffic / roofline_train.traffic from the newest profiles/r04_*.json by KERNEL NAME (round-3 verdict: a renamed kernel must not
     turn the field into null silently): the names it selects on are in the committed files."""
