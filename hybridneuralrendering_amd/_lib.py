@@ -12,6 +12,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # HNR_LIB_PATH: another build of the same library (A/B timing of kernel changes); there is no other fallback
 LIB_PATH = os.environ.get("HNR_LIB_PATH") or os.path.join(_HERE, "libhnr_hip.so")
 NCOUNTS = 9
+FEATNET_PACKED_ELEMS = 41368           # HNR_FEATNET_PACKED_ELEMS
+PREMLP_PACKED_ELEMS = 3104             # HNR_PREMLP_PACKED_ELEMS
 CNT = dict(RAYS_HIT=0, SAMPLES=1, RAYS_VALID=2, NEIGHBOURS=3, CELLS_VISITED=4, CANDIDATES=5, SAMPLES_VALID=6, SAMPLES_SMALL=7, SAMPLES_TINY=8)
 
 
@@ -190,6 +192,10 @@ SIGNATURES = {
     "hnr_range_crop": (_I, [_P, _P, ctypes.c_int64, ctypes.POINTER(_F), _P, _P, _P, ctypes.c_int64, _P]),
     "hnr_nearest_view": (_I, [_P, ctypes.c_int64, _P, _P, _I, _P, _P]),
     "hnr_point_view_attrs": (_I, [_P, ctypes.c_int64] + [ctypes.POINTER(_F)] * 4 + [_I, _I, _P, _I, _I, _I, _P, _P, _P, _P]),
+    # point embeddings from the MVS init checkpoint (csrc/featnet.hip)
+    "hnr_featnet_scratch_elems": (ctypes.c_int64, [_I, _I, _I]),
+    "hnr_featnet_forward": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.c_int64, _P]),
+    "hnr_point_embed": (_I, [_P, ctypes.c_int64] + [ctypes.POINTER(_F)] * 4 + [_I, _I] + [_P] * 10),
     # device-resident frame bank + batch sampler (csrc/frames.hip)
     "hnr_frame_batch_scratch_bytes": (ctypes.c_int64, [_I, _I]),
     "hnr_frame_batch": (_I, [ctypes.POINTER(FrameBankC), ctypes.POINTER(FrameBankC), _P, _I, ctypes.POINTER(FrameBatchParams), _P, _I, _P,

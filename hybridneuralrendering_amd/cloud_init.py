@@ -3,7 +3,8 @@
 Mirror of the reference's `load_points=2` start of a scene (run/train_ft.py:687-770): data/scannet_ft_dataset.py:616-647
 `load_init_depth_points` (back-projection + per-frame `construct_vox_points_xyz`), the range crop, `construct_vox_points_closest`, `nearest_view`
 (train_ft.py:48-57), the regrouping by view and `MvsPointsModel.query_embedding` (homo_warp_nongrid + extract_from_2d_grid + the `dir` branch).
-The reference's FeatureNet and premlp stay the user's torch modules: they produce `feature_maps` and consume `features`.
+The reference's FeatureNet and premlp run on the device too (mvs_init.MvsInit, csrc/featnet.hip): pass one as `init_net` and the embedding is the
+checkpoint's; without it the caller may still hand in `feature_maps` of their own.
 """
 import ctypes
 
@@ -219,7 +220,7 @@ def view_segments(sorted_ids):
     return [(int(ids[s]), int(s), int(e)) for s, e in zip(starts, ends)]
 
 
-def init_cloud_from_depth(frames, opt, campos, camdir, view_frame, capacity=None, frame_vox_res=100, device=None):
+def init_cloud_from_depth(frames, opt, campos, camdir, view_frame, capacity=None, frame_vox_res=100, device=None, init_net=None):
     """run/train_ft.py:687-770 for `load_points=2`.
 
     frames: iterable of (depth [H,W], c2w [4,4]) -- every depth frame of the scan; opt.depth_intrinsic is their intrinsic.  campos / camdir [M,3]: the
@@ -227,6 +228,10 @@ def init_cloud_from_depth(frames, opt, campos, camdir, view_frame, capacity=None
     Returns dict(xyz [N,3], embedding [1,N,C], color [1,N,3], dir [1,N,3], conf [1,N,1], view_of_point [N] int64): the arguments of
     NeuralPoints.set_points, points grouped by view in ascending view id.  Without feature maps the embedding is
     cloud_io.init_point_features(opt.feature_init_method).
+
+    init_net: an mvs_init.MvsInit holding the init checkpoint.  view_frame then needs to return only image, c2w and intrinsic: the image pyramid of
+    each used view is computed once and the embedding is init_net.embed_points' (train_ft.py:759-760); xyz, color, dir, conf and view_of_point are what
+    the call without init_net returns.
 
     capacity: points the fused cloud may hold (12 bytes each), allocated up front.  The default is the frames' upper bound
     len(frames) * min(H*W, (frame_vox_res + 1)^3), CAPPED at 2^24 points (192 MiB).  A long scan can need more: the overflow is only known once every
@@ -263,6 +268,10 @@ def init_cloud_from_depth(frames, opt, campos, camdir, view_frame, capacity=None
     colors, dirs, confs, feats = [], [], [], []
     for vid, s, e in segs:
         fr = view_frame(vid)
+        if init_net is not None:
+            f, c, d, cf = init_net.embed_points(xyz[s:e], fr["image"], fr["c2w"], fr.get("w2c"), fr["intrinsic"], getattr(opt, "default_conf", -1))
+            colors.append(c); dirs.append(d); confs.append(cf); feats.append(f)
+            continue
         f, c, d, cf = query_point_attributes(xyz[s:e], fr["image"], fr["c2w"], fr.get("w2c"), fr["intrinsic"], fr.get("feature_maps"),
                                              getattr(opt, "default_conf", -1))
         colors.append(c); dirs.append(d); confs.append(cf); feats.append(f)

@@ -12,6 +12,7 @@
 // restates them in NumPy and the GPU tests compare bits.  The fusion's voxel stage is the machinery of voxelize.hip (voxel_segments.h): keys -> stable
 // radix sort -> head flags -> scan -> per-voxel walk; the frame's bounds and the derived cell size stay on the device.
 #include "voxel_segments.h"
+#include "view_attrs.h"
 
 namespace hnr {
 
@@ -214,32 +215,19 @@ __global__ void __launch_bounds__(256) nearest_view_kernel(const float *__restri
     if (valid) out[i] = arg;
 }
 
-struct ViewCam {
-    float Wm[16];                   // w2c
-    float R[9];                     // c2w[:3,:3]
-    float cpc[3];                   // cam_pos_cam
-    float K[9];
-};
-
 __global__ void __launch_bounds__(256) view_attrs_kernel(const float *__restrict__ xyz, long long n, ViewCam vc, int H, int W, const float *__restrict__ feat, int C,
                                                          int Hl, int Wl, float *__restrict__ out_feat, float *__restrict__ out_dir, uint8_t *__restrict__ out_mask)
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float x = xyz[3 * i + 0], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
-    float c[3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) c[q] = ((x * vc.Wm[4 * q] + y * vc.Wm[4 * q + 1]) + z * vc.Wm[4 * q + 2]) + vc.Wm[4 * q + 3];
-    const float q0 = hnr_div(c[0], c[2]), q1 = hnr_div(c[1], c[2]);
-    const float gx = (q0 * vc.K[0] + q1 * vc.K[1]) + vc.K[2], gy = (q0 * vc.K[3] + q1 * vc.K[4]) + vc.K[5];
-    const bool mask = gx >= 0.f && gx <= (float)(W - 1) && gy >= 0.f && gy <= (float)(H - 1);          // NaN compares false
+    float c[3], gx, gy;
+    const bool mask = view_project(vc, xyz[3 * i + 0], xyz[3 * i + 1], xyz[3 * i + 2], H, W, c, gx, gy);
     if (out_mask) out_mask[i] = mask ? 1 : 0;
     if (out_dir) {
-        const float e0 = c[0] - vc.cpc[0], e1 = c[1] - vc.cpc[1], e2 = c[2] - vc.cpc[2];
-        const float den = sqrtf((e0 * e0 + e1 * e1) + e2 * e2) + 1e-6f;
-        const float u0 = hnr_div(e0, den), u1 = hnr_div(e1, den), u2 = hnr_div(e2, den);
+        float d[3];
+        view_dir(vc, c, d);
 #pragma unroll
-        for (int q = 0; q < 3; ++q) out_dir[3 * i + q] = (u0 * vc.R[3 * q] + u1 * vc.R[3 * q + 1]) + u2 * vc.R[3 * q + 2];
+        for (int q = 0; q < 3; ++q) out_dir[3 * i + q] = d[q];
     }
     if (!out_feat) return;
     float *o = out_feat + (size_t)i * C;
@@ -247,20 +235,9 @@ __global__ void __launch_bounds__(256) view_attrs_kernel(const float *__restrict
         for (int ch = 0; ch < C; ++ch) o[ch] = 0.f;
         return;
     }
-    // bilinear, zero padding, align_corners=True: the weights as F.grid_sample forms them (ix_se - ix, ix - ix_nw, ...)
-    const float sx = hnr_div(gx * (float)(Wl - 1), (float)(W - 1)), sy = hnr_div(gy * (float)(Hl - 1), (float)(H - 1));
-    const float x0f = floorf(sx), y0f = floorf(sy), x1f = x0f + 1.f, y1f = y0f + 1.f;
-    const float wx0 = x1f - sx, wx1 = sx - x0f, wy0 = y1f - sy, wy1 = sy - y0f;
-    const float w00 = wx0 * wy0, w01 = wx1 * wy0, w10 = wx0 * wy1, w11 = wx1 * wy1;
-    const int x0 = (int)x0f, y0 = (int)y0f, x1 = x0 + 1, y1 = y0 + 1;
-    const bool bx0 = x0 >= 0 && x0 < Wl, bx1 = x1 >= 0 && x1 < Wl, by0 = y0 >= 0 && y0 < Hl, by1 = y1 >= 0 && y1 < Hl;
+    const ViewTaps t = view_taps(gx, gy, H, W, Hl, Wl);
     const size_t plane = (size_t)Hl * Wl;
-    for (int ch = 0; ch < C; ++ch) {
-        const float *f = feat + ch * plane;
-        const float v00 = (bx0 && by0) ? f[(size_t)y0 * Wl + x0] : 0.f, v01 = (bx1 && by0) ? f[(size_t)y0 * Wl + x1] : 0.f;
-        const float v10 = (bx0 && by1) ? f[(size_t)y1 * Wl + x0] : 0.f, v11 = (bx1 && by1) ? f[(size_t)y1 * Wl + x1] : 0.f;
-        o[ch] = ((w00 * v00 + w01 * v01) + w10 * v10) + w11 * v11;
-    }
+    for (int ch = 0; ch < C; ++ch) o[ch] = view_sample(t, feat + ch * plane, Wl);
 }
 
 static int fuse_bits(int vox_res)
@@ -400,10 +377,7 @@ extern "C" int hnr_point_view_attrs(const float *d_xyz, int64_t n, const float *
         set_error("hnr_point_view_attrs: bad argument (n > 0, H, W >= 2, C, Hl, Wl > 0)"); return HNR_ERR_BADARG;
     }
     ViewCam vc;
-    memcpy(vc.Wm, w2c, sizeof(vc.Wm));
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) vc.R[3 * r + c] = c2w[4 * r + c];
-    memcpy(vc.cpc, cam_pos_cam, sizeof(vc.cpc));
-    memcpy(vc.K, K, sizeof(vc.K));
+    view_cam_fill(vc, w2c, c2w, cam_pos_cam, K);
     view_attrs_kernel<<<cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(d_xyz, (long long)n, vc, H, W, d_feat, C, Hl, Wl, d_out_feat, d_out_dir, d_out_mask);
     HNR_LAUNCH_CHECK();
     return HNR_OK;

@@ -11,6 +11,8 @@
 //   hnr::render_train                    hnr_render_train_forward + _backward    (the same in train mode; autograd formula registered)
 //   hnr::nearest_view                    hnr_nearest_view                        (run/train_ft.py:48-57)
 //   hnr::point_view_attrs                hnr_point_view_attrs                    (homo_warp_nongrid + extract_from_2d_grid + the `dir` branch of query_embedding)
+//   hnr::featnet_forward                 hnr_featnet_forward                     (FeatureNet(intermediate=True) in eval mode, models/mvs/models.py:717-764)
+//   hnr::point_embed                     hnr_point_embed                         (query_embedding with premlp, models/mvs/mvs_points_model.py:225-259)
 // Nothing is computed here: every op validates its tensors, fills the C structs, takes the current HIP stream and calls the library.  Errors
 // of the library surface as c10::Error with hnr_last_error() as the message.  Host code only (no kernels): built by g++ against libtorch.
 #include <ATen/ATen.h>
@@ -422,6 +424,55 @@ std::tuple<Tensor, Tensor, Tensor> point_view_attrs(const Tensor &xyz, c10::Arra
     return {out, dir, mask};
 }
 
+// ---- hnr::featnet_forward(Tensor images [V,3,H,W], Tensor packed [HNR_FEATNET_PACKED_ELEMS]) -> (x1 [V,8,H,W], x2 [V,16,H2,W2], x3 [V,32,H4,W4])
+std::tuple<Tensor, Tensor, Tensor> featnet_forward(const Tensor &images, const Tensor &packed)
+{
+    TORCH_CHECK(images.dim() == 4 && images.size(1) == 3, "hnr::featnet_forward: images must be [V,3,H,W]");
+    TORCH_CHECK(packed.dim() == 1 && packed.size(0) == HNR_FEATNET_PACKED_ELEMS && packed.device() == images.device(),
+                "hnr::featnet_forward: packed must hold HNR_FEATNET_PACKED_ELEMS values on the images' device");
+    const c10::DeviceGuard guard(images.device());
+    const int64_t V = images.size(0), H = images.size(2), W = images.size(3);
+    const int64_t H2 = (H - 1) / 2 + 1, W2 = (W - 1) / 2 + 1, H4 = (H2 - 1) / 2 + 1, W4 = (W2 - 1) / 2 + 1;
+    const int64_t ns = (V <= INT32_MAX && H <= INT32_MAX && W <= INT32_MAX) ? hnr_featnet_scratch_elems((int)V, (int)H, (int)W) : -1;
+    TORCH_CHECK(ns >= 0, "hnr::featnet_forward: unsupported shape (1 <= V <= 4096, 4 <= H, W <= 32768)");
+    Tensor x1 = new_f32({V, 8, H, W}, images), x2 = new_f32({V, 16, H2, W2}, images), x3 = new_f32({V, 32, H4, W4}, images), scratch = new_f32({ns}, images);
+    hnr_check(hnr_featnet_forward(fptr(images, "images"), (int)V, (int)H, (int)W, fptr(packed, "packed"), x1.data_ptr<float>(), x2.data_ptr<float>(),
+                                  x3.data_ptr<float>(), scratch.data_ptr<float>(), ns, cur_stream(images)),
+              "hnr_featnet_forward");
+    return {x1, x2, x3};
+}
+
+// ---- hnr::point_embed(Tensor xyz, float[] w2c, float[] c2w, float[] cam_pos_cam, float[] intrinsic, Tensor image [3,H,W], Tensor x1, Tensor x2, Tensor x3,
+//      Tensor premlp [HNR_PREMLP_PACKED_ELEMS], bool want_row) -> (emb [n,32], color [n,3], dir [n,3], row [n,63] or [n,0])
+std::tuple<Tensor, Tensor, Tensor, Tensor> point_embed(const Tensor &xyz, c10::ArrayRef<double> w2c, c10::ArrayRef<double> c2w, c10::ArrayRef<double> cam_pos_cam,
+                                                       c10::ArrayRef<double> intrinsic, const Tensor &image, const Tensor &x1, const Tensor &x2, const Tensor &x3,
+                                                       const Tensor &premlp, bool want_row)
+{
+    TORCH_CHECK(xyz.dim() == 2 && xyz.size(1) == 3, "hnr::point_embed: xyz must be [n,3]");
+    TORCH_CHECK(w2c.size() == 16 && c2w.size() == 16 && cam_pos_cam.size() == 3 && intrinsic.size() == 9, "hnr::point_embed: w2c / c2w hold 16 values, cam_pos_cam 3, intrinsic 9");
+    TORCH_CHECK(image.dim() == 3 && image.size(0) == 3, "hnr::point_embed: image must be [3,H,W]");
+    const int64_t H = image.size(1), W = image.size(2);
+    const int64_t H2 = (H - 1) / 2 + 1, W2 = (W - 1) / 2 + 1, H4 = (H2 - 1) / 2 + 1, W4 = (W2 - 1) / 2 + 1;
+    TORCH_CHECK(H >= 4 && W >= 4 && H <= 32768 && W <= 32768, "hnr::point_embed: 4 <= H, W <= 32768");
+    TORCH_CHECK(x1.sizes() == at::IntArrayRef({8, H, W}) && x2.sizes() == at::IntArrayRef({16, H2, W2}) && x3.sizes() == at::IntArrayRef({32, H4, W4}),
+                "hnr::point_embed: x1 / x2 / x3 must be [8,H,W], [16,H2,W2], [32,H4,W4] of the image's pyramid");
+    TORCH_CHECK(premlp.dim() == 1 && premlp.size(0) == HNR_PREMLP_PACKED_ELEMS, "hnr::point_embed: premlp must hold HNR_PREMLP_PACKED_ELEMS values");
+    for (const Tensor *t : {&image, &x1, &x2, &x3, &premlp}) TORCH_CHECK(t->device() == xyz.device(), "hnr::point_embed: every tensor must be on xyz's device");
+    const c10::DeviceGuard guard(xyz.device());
+    float m[16 + 16 + 3 + 9];
+    for (int i = 0; i < 16; ++i) { m[i] = (float)w2c[i]; m[16 + i] = (float)c2w[i]; }
+    for (int i = 0; i < 3; ++i) m[32 + i] = (float)cam_pos_cam[i];
+    for (int i = 0; i < 9; ++i) m[35 + i] = (float)intrinsic[i];
+    const int64_t n = xyz.size(0);
+    Tensor emb = new_f32({n, 32}, xyz), color = new_f32({n, 3}, xyz), dir = new_f32({n, 3}, xyz), row = new_f32({n, want_row ? 63 : 0}, xyz);
+    if (n > 0)
+        hnr_check(hnr_point_embed(fptr(xyz, "xyz"), n, m, m + 16, m + 32, m + 35, (int)H, (int)W, fptr(image, "image"), fptr(x1, "x1"), fptr(x2, "x2"),
+                                  fptr(x3, "x3"), fptr(premlp, "premlp"), emb.data_ptr<float>(), color.data_ptr<float>(), dir.data_ptr<float>(),
+                                  want_row ? row.data_ptr<float>() : nullptr, cur_stream(xyz)),
+                  "hnr_point_embed");
+    return {emb, color, dir, row};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(hnr, m)
@@ -441,6 +492,9 @@ TORCH_LIBRARY(hnr, m)
           "float vsize_z, int raydist_mode_unit, int knn_order, float slope, int cap_samples) -> Tensor[]");
     m.def("nearest_view(Tensor xyz, Tensor campos, Tensor camdir) -> Tensor");
     m.def("point_view_attrs(Tensor xyz, float[] w2c, float[] c2w, float[] cam_pos_cam, float[] intrinsic, int H, int W, Tensor? feat) -> (Tensor, Tensor, Tensor)");
+    m.def("featnet_forward(Tensor images, Tensor packed) -> (Tensor, Tensor, Tensor)");
+    m.def("point_embed(Tensor xyz, float[] w2c, float[] c2w, float[] cam_pos_cam, float[] intrinsic, Tensor image, Tensor x1, Tensor x2, Tensor x3, Tensor premlp, "
+          "bool want_row) -> (Tensor, Tensor, Tensor, Tensor)");
 }
 TORCH_LIBRARY_IMPL(hnr, CompositeExplicitAutograd, m)
 {
@@ -456,6 +510,8 @@ TORCH_LIBRARY_IMPL(hnr, CUDA, m)
     m.impl("render_train_bwd", &render_train_bwd);
     m.impl("nearest_view", &nearest_view);
     m.impl("point_view_attrs", &point_view_attrs);
+    m.impl("featnet_forward", &featnet_forward);
+    m.impl("point_embed", &point_embed);
 }
 TORCH_LIBRARY_IMPL(hnr, Autograd, m)
 {

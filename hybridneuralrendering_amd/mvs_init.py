@@ -1,0 +1,228 @@
+"""Point embeddings from the MVS init checkpoint, on the device (csrc/featnet.hip).
+
+The reference starts a `load_points=2` scene from LEARNED point embeddings (run/train_ft.py:751-765): the image of the view a point was given to goes
+through `FeatureNet(intermediate=True)` (models/mvs/models.py:717-764, built from InPlaceABN, a CUDA extension), the four pyramid levels are sampled at
+the point's projection and `[56 features | colour 3 | dir 3 | conf 1]` goes through `premlp` (models/mvs/mvs_points_model.py:22-34, :225-259).  Both
+networks come from the published init checkpoint (`*_net_mvs.pth`).  `MvsInit` carries the reference's parameter names, so that file loads as it is,
+and runs both networks as HIP kernels: `hnr_featnet_forward` and `hnr_point_embed`.  Inference only (no backward, results carry no graph), GPU only
+(no CPU or torch fallback: `HnrError`).
+
+The weights a fresh module starts from are torch's defaults, not the reference's `init_seq`: the module exists to load a checkpoint.
+"""
+import torch
+from torch import nn
+
+from . import _lib
+from ._lib import HnrError
+
+EPS = 1e-5                                                       # InPlaceABN's eps (variance and |weight|)
+SLOPE = 0.01                                                     # its activation_param, and premlp's LeakyReLU
+LAYERS = (("conv0", ((3, 8, 3, 1), (8, 8, 3, 1))), ("conv1", ((8, 16, 5, 2), (16, 16, 3, 1), (16, 16, 3, 1))),
+          ("conv2", ((16, 32, 5, 2), (32, 32, 3, 1), (32, 32, 3, 1))))             # (cin, cout, kernel, stride); pad = kernel // 2
+FEATURE_STR = ["imgfeat_0_0123", "dir_0", "point_conf"]
+
+
+def pyramid_shape(H, W):
+    """((H, W), (H2, W2), (H4, W4)) of x1, x2, x3."""
+    H2, W2 = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    return (H, W), (H2, W2), ((H2 - 1) // 2 + 1, (W2 - 1) // 2 + 1)
+
+
+class _Abn(nn.Module):
+    """Parameter holder with InPlaceABN's names; its arithmetic lives in the convolution kernel's epilogue."""
+
+    def __init__(self, ch):
+        super().__init__()
+        self.weight, self.bias = nn.Parameter(torch.ones(ch)), nn.Parameter(torch.zeros(ch))
+        self.register_buffer("running_mean", torch.zeros(ch))
+        self.register_buffer("running_var", torch.ones(ch))
+
+
+class _ConvBnReLU(nn.Module):
+    def __init__(self, cin, cout, ks, stride):
+        super().__init__()
+        self.conv = nn.Conv2d(cin, cout, ks, stride=stride, padding=ks // 2, bias=False)
+        self.bn = _Abn(cout)
+
+
+def featnet_forward(images, packed):
+    """hnr_featnet_forward: images [V,3,H,W], packed [FEATNET_PACKED_ELEMS] -> (x1 [V,8,H,W], x2 [V,16,H2,W2], x3 [V,32,H4,W4])."""
+    L = _lib.lib()
+    images, packed = _lib.require_gpu(images, "images", torch.float32), _lib.require_gpu(packed, "packed", torch.float32)
+    if images.dim() != 4 or images.shape[1] != 3:
+        raise HnrError("featnet_forward: images must be [V,3,H,W], got %s" % (tuple(images.shape),))
+    if packed.numel() != _lib.FEATNET_PACKED_ELEMS or packed.device != images.device:
+        raise HnrError("featnet_forward: packed must hold %d values on the images' device" % _lib.FEATNET_PACKED_ELEMS)
+    V, _, H, W = (int(s) for s in images.shape)
+    ns = int(L.hnr_featnet_scratch_elems(V, H, W)) if max(V, H, W) < 2 ** 31 else -1
+    if ns < 0:
+        raise HnrError("featnet_forward: unsupported shape V=%d H=%d W=%d (1 <= V <= 4096, 4 <= H, W <= 32768)" % (V, H, W))
+    dev = images.device
+    outs = [torch.empty((V, c, h, w), dtype=torch.float32, device=dev) for c, (h, w) in zip((8, 16, 32), pyramid_shape(H, W))]
+    scratch = torch.empty((ns,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.hnr_featnet_forward(_lib.ptr(images), V, H, W, _lib.ptr(packed), _lib.ptr(outs[0]), _lib.ptr(outs[1]), _lib.ptr(outs[2]),
+                                         _lib.ptr(scratch), ns, _lib.stream()), "hnr_featnet_forward")
+    return tuple(outs)
+
+
+def point_embed(xyz, w2c, c2w, cpc, intrinsic, image, x1, x2, x3, premlp, want_row=False):
+    """hnr_point_embed for one view: (emb [n,32], color [n,3], dir [n,3], row [n,63] or None).  image [3,H,W]; x1 / x2 / x3 its pyramid, channels first."""
+    from .cloud_init import _cf, _host_f32
+    L = _lib.lib()
+    xyz = _lib.require_gpu(xyz, "xyz", torch.float32).reshape(-1, 3)
+    image = _lib.require_gpu(image, "image", torch.float32)
+    if image.dim() != 3 or image.shape[0] != 3:
+        raise HnrError("point_embed: image must be [3,H,W]")
+    H, W = int(image.shape[1]), int(image.shape[2])
+    maps = [_lib.require_gpu(m, name, torch.float32) for m, name in ((x1, "x1"), (x2, "x2"), (x3, "x3"))]
+    for m, c, hw in zip(maps, (8, 16, 32), pyramid_shape(H, W)):
+        if tuple(m.shape) != (c,) + hw:
+            raise HnrError("point_embed: a pyramid level must be %s for a %dx%d image, got %s" % ((c,) + hw, H, W, tuple(m.shape)))
+    premlp = _lib.require_gpu(premlp, "premlp", torch.float32)
+    if premlp.numel() != _lib.PREMLP_PACKED_ELEMS:
+        raise HnrError("point_embed: premlp must hold %d values" % _lib.PREMLP_PACKED_ELEMS)
+    n, dev = int(xyz.shape[0]), xyz.device
+    if any(t.device != dev for t in [image, premlp] + maps):
+        raise HnrError("point_embed: every tensor must be on xyz's device")
+    emb, color, pdir = (torch.empty((n, c), dtype=torch.float32, device=dev) for c in (32, 3, 3))
+    row = torch.empty((n, 63), dtype=torch.float32, device=dev) if want_row else None
+    if n > 0:
+        a = [_host_f32(w2c, (4, 4), "w2c"), _host_f32(c2w, (4, 4), "c2w"), _host_f32(cpc, (3,), "cam_pos_cam"), _host_f32(intrinsic, (3, 3), "intrinsic")]
+        with torch.cuda.device(dev):
+            _lib.check(L.hnr_point_embed(_lib.ptr(xyz), n, _cf(a[0]), _cf(a[1]), _cf(a[2]), _cf(a[3]), H, W, _lib.ptr(image), _lib.ptr(maps[0]),
+                                         _lib.ptr(maps[1]), _lib.ptr(maps[2]), _lib.ptr(premlp), _lib.ptr(emb), _lib.ptr(color), _lib.ptr(pdir), _lib.ptr(row),
+                                         _lib.stream()), "hnr_point_embed")
+    return emb, color, pdir, row
+
+
+class _Packed:
+    """A packed copy of a module's weights on the device, rebuilt when a parameter or buffer changes or moves.  A change is seen through the tensors'
+    addresses and in-place version counters: `load_state_dict`, optimiser steps, `.to()` and any other in-place update are covered.  A tensor swapped in
+    through `p.data = other` can, in principle, land on a recycled address with the same counter: call `invalidate()` after such an assignment."""
+
+    def __init__(self):
+        self.key, self.value = None, None
+
+    def invalidate(self):
+        self.key, self.value = None, None
+
+    def get(self, tensors, build):
+        key = tuple((t.data_ptr(), t._version, str(t.device)) for t in tensors)
+        if key != self.key:
+            self.value, self.key = build(), key
+        return self.value
+
+
+class FeatureNet(nn.Module):
+    """The reference's `FeatureNet(intermediate=True)` in eval mode: its parameter and buffer names, its forward signature, HIP kernels inside."""
+
+    def __init__(self):
+        super().__init__()
+        for name, layers in LAYERS:
+            setattr(self, name, nn.Sequential(*[_ConvBnReLU(*l) for l in layers]))
+        self.toplayer = nn.Conv2d(32, 32, 1)
+        self._packed = _Packed()
+
+    def pack_host(self):
+        """fp32 [FEATNET_PACKED_ELEMS] on the CPU, the layout of include/hnr.h; mul = rsqrt(running_var + eps) * (|weight| + eps) is folded here, once."""
+        parts = []
+        with torch.no_grad():
+            for name, _ in LAYERS:
+                for blk in getattr(self, name):
+                    w, bn = blk.conv.weight.detach().float().cpu(), blk.bn
+                    var, gamma = bn.running_var.detach().float().cpu(), bn.weight.detach().float().cpu()
+                    mul = torch.rsqrt(var + EPS) * (gamma.abs() + EPS)
+                    parts += [w.permute(1, 2, 3, 0).reshape(-1), bn.running_mean.detach().float().cpu(), mul, bn.bias.detach().float().cpu()]
+            parts += [self.toplayer.weight.detach().float().cpu().reshape(-1), self.toplayer.bias.detach().float().cpu()]
+            out = torch.cat([p.contiguous().reshape(-1) for p in parts])
+        assert out.numel() == _lib.FEATNET_PACKED_ELEMS
+        return out
+
+    def packed(self):
+        tensors = list(self.parameters()) + list(self.buffers())
+        return self._packed.get(tensors, lambda: self.pack_host().to(self.toplayer.weight.device))
+
+    def forward(self, imgs):
+        """imgs [B,V,3,H,W] -> [x [B*V,3,H,W], x1, x2, x3] (the reference's `intermediate` return)."""
+        imgs = _lib.require_gpu(imgs, "imgs", torch.float32)
+        if imgs.dim() != 5 or imgs.shape[2] != 3:
+            raise HnrError("FeatureNet: imgs must be [B,V,3,H,W], got %s" % (tuple(imgs.shape),))
+        if self.toplayer.weight.device != imgs.device:
+            raise HnrError("FeatureNet: the module is on %s, imgs on %s" % (self.toplayer.weight.device, imgs.device))
+        x = imgs.detach().reshape((-1,) + tuple(imgs.shape[2:]))
+        return [x] + list(featnet_forward(x, self.packed()))
+
+
+def check_options(opt):
+    """The shipped family only: anything else would need another row layout or another network."""
+    fs = getattr(opt, "appr_feature_str0", FEATURE_STR)
+    fs = fs.split() if isinstance(fs, str) else list(fs)
+    if fs != FEATURE_STR:
+        raise HnrError("MvsInit: appr_feature_str0=%r is not implemented (only %r)" % (fs, " ".join(FEATURE_STR)))
+    for name, want in (("point_features_dim", 32), ("shading_feature_mlp_layer1", 2), ("act_type", "LeakyReLU")):
+        if getattr(opt, name, want) != want:
+            raise HnrError("MvsInit: %s=%r is not implemented (only %r)" % (name, getattr(opt, name), want))
+    if int(getattr(opt, "depth_occ", 0) or 0) > 0:
+        raise HnrError("MvsInit: depth_occ > 0 (occlusion-aware warps) is not implemented")
+    if int(getattr(opt, "shading_feature_mlp_layer0", 1)) < 1:
+        raise HnrError("MvsInit: shading_feature_mlp_layer0=0 leaves no premlp to run: use cloud_init.query_point_attributes")
+
+
+class MvsInit(nn.Module):
+    """`.FeatureNet` + `.premlp` under the names of the reference's MvsPointsModel, so that a `*_net_mvs.pth` loads with
+    `load_state_dict(sd, strict=False)`: `MVSNet.*` keys and `num_batches_tracked` entries are ignored, every key this module owns must be there."""
+
+    def __init__(self, opt=None):
+        super().__init__()
+        if opt is not None:
+            check_options(opt)
+        self.FeatureNet = FeatureNet()
+        self.premlp = nn.Sequential(nn.Linear(63, 32), nn.LeakyReLU(SLOPE, inplace=True), nn.Linear(32, 32), nn.LeakyReLU(SLOPE, inplace=True))
+        self._packed = _Packed()
+
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        sd = {k: v for k, v in state_dict.items() if not k.startswith("MVSNet.") and not k.endswith("num_batches_tracked")}
+        res = super().load_state_dict(sd, strict=False, **kw)
+        if res.missing_keys:
+            raise HnrError("MvsInit.load_state_dict: the checkpoint lacks %s" % ", ".join(sorted(res.missing_keys)))
+        if strict and res.unexpected_keys:
+            raise HnrError("MvsInit.load_state_dict: unexpected keys %s (pass strict=False to ignore them)" % ", ".join(sorted(res.unexpected_keys)))
+        return res
+
+    def premlp_packed(self):
+        """[PREMLP_PACKED_ELEMS] on the device: W0^T [63][32], b0, W1^T [32][32], b1."""
+        l0, l1 = self.premlp[0], self.premlp[2]
+
+        def build():
+            with torch.no_grad():
+                return torch.cat([l0.weight.detach().float().t().reshape(-1), l0.bias.detach().float(), l1.weight.detach().float().t().reshape(-1),
+                                  l1.bias.detach().float()]).contiguous()
+        return self._packed.get([l0.weight, l0.bias, l1.weight, l1.bias], build)
+
+    def invalidate_packed(self):
+        """Drops the packed device copies of both networks' weights; needed only after replacing a parameter's storage with `p.data = ...`
+        (in-place updates and load_state_dict are noticed by themselves)."""
+        self._packed.invalidate()
+        self.FeatureNet._packed.invalidate()
+
+    def get_image_features(self, imgs):
+        """imgs [B,V,3,H,W] -> [x, x1, x2, x3] (MvsPointsModel.get_image_features)."""
+        return self.FeatureNet(imgs)
+
+    def embed_points(self, xyz_world, image_chw, c2w, w2c, intrinsic, default_conf=-1, feats=None, want_row=False):
+        """What run/train_ft.py:759-761 computes for the points of one view: (embedding [1,n,32], color [1,n,3], dir [1,n,3], conf [1,n,1]).
+        image_chw [3,H,W] (or [1,3,H,W]); w2c None: the fp32 inverse of c2w, as the reference forms it.  feats: the view's [x, x1, x2, x3] from
+        get_image_features when it is already there.  want_row: a fifth result, the [n,63] rows premlp saw."""
+        from . import cloud_init as ci
+        img = _lib.require_gpu(image_chw, "image_chw", torch.float32)
+        img = img.reshape(img.shape[-3:]).contiguous()
+        if img.shape[0] != 3:
+            raise HnrError("image_chw must be [3,H,W]")
+        if feats is None:
+            feats = self.get_image_features(img[None, None])
+        w2c = torch.inverse(torch.from_numpy(ci._host_f32(c2w, (4, 4), "c2w"))).numpy() if w2c is None else w2c
+        cpc = ci.cam_pos_cam(c2w, w2c)
+        emb, color, pdir, row = point_embed(xyz_world, w2c, c2w, cpc, intrinsic, img, feats[1][0], feats[2][0], feats[3][0], self.premlp_packed(), want_row)
+        out = (emb[None], color[None], pdir[None], ci.point_conf(emb.shape[0], default_conf, emb.device))
+        return out + (row,) if want_row else out

@@ -2,7 +2,7 @@
 
 SURVEY 8b asks for both op layers: the C ABI (include/hnr.h, bound by ctypes in _lib.py -- needs no torch headers) and registered torch ops.  The
 ops are the same library calls with schemas: `hnr::grid_build`, `hnr::grid_free`, `hnr::march_query`, `hnr::nearest_view`, `hnr::point_view_attrs`
-(the cloud initialisation of cloud_init.py), `hnr::render_forward`
+(the cloud initialisation of cloud_init.py), `hnr::featnet_forward`, `hnr::point_embed` (the init checkpoint's networks, mvs_init.py), `hnr::render_forward`
 (NeuralPointsRayMarching.forward + fill_invalid in eval mode, /root/reference/models/neural_points_volumetric_model.py:257-391, :87-126) and
 `hnr::render_train` (the same in train mode with the backward pass registered as its autograd formula; the reference leaves that to torch autograd,
 models/mvs_points_volumetric_model.py:111-131).  This module loads the extension and builds the ops' argument lists from the host-side objects
@@ -104,6 +104,18 @@ def _register_fakes():
         n, e = xyz.shape[0], xyz.new_empty
         return (e((n, feat.shape[0] if feat is not None else 0), dtype=f32), e((n, 3), dtype=f32), e((n,), dtype=torch.uint8))
 
+    @torch.library.register_fake("hnr::featnet_forward")
+    def _(images, packed):
+        V, _, H, W = images.shape
+        H2, W2 = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        e = images.new_empty
+        return (e((V, 8, H, W), dtype=f32), e((V, 16, H2, W2), dtype=f32), e((V, 32, (H2 - 1) // 2 + 1, (W2 - 1) // 2 + 1), dtype=f32))
+
+    @torch.library.register_fake("hnr::point_embed")
+    def _(xyz, w2c, c2w, cam_pos_cam, intrinsic, image, x1, x2, x3, premlp, want_row):
+        n, e = xyz.shape[0], xyz.new_empty
+        return (e((n, 32), dtype=f32), e((n, 3), dtype=f32), e((n, 3), dtype=f32), e((n, 63 if want_row else 0), dtype=f32))
+
 
 def load():
     """Registers torch.ops.hnr (once), with shape functions for tracing.  libhnr_torch.so links libhnr_hip.so next to it."""
@@ -202,3 +214,20 @@ def point_view_attrs(xyz, w2c, c2w, cam_pos_cam, intrinsic, H, W, feat=None):
     flat = lambda a, n: [float(v) for v in np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float32).reshape(n)]
     return ops.point_view_attrs(_lib.require_gpu(xyz, "xyz", torch.float32).reshape(-1, 3), flat(w2c, 16), flat(c2w, 16), flat(cam_pos_cam, 3), flat(intrinsic, 9),
                                 int(H), int(W), None if feat is None else _lib.require_gpu(feat, "feat", torch.float32))
+
+
+def featnet_forward(images, packed):
+    """mvs_init.featnet_forward through torch.ops.hnr.featnet_forward: images [V,3,H,W], packed = FeatureNet.packed() -> (x1, x2, x3)."""
+    ops = load()
+    g = _lib.require_gpu
+    return ops.featnet_forward(g(images, "images", torch.float32), g(packed, "packed", torch.float32))
+
+
+def point_embed(xyz, w2c, c2w, cam_pos_cam, intrinsic, image, x1, x2, x3, premlp, want_row=False):
+    """mvs_init.point_embed through torch.ops.hnr.point_embed: (emb [n,32], color [n,3], dir [n,3], row [n,63] or [n,0])."""
+    ops = load()
+    g = _lib.require_gpu
+    flat = lambda a, n: [float(v) for v in np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float32).reshape(n)]
+    return ops.point_embed(g(xyz, "xyz", torch.float32).reshape(-1, 3), flat(w2c, 16), flat(c2w, 16), flat(cam_pos_cam, 3), flat(intrinsic, 9),
+                           g(image, "image", torch.float32), g(x1, "x1", torch.float32), g(x2, "x2", torch.float32), g(x3, "x3", torch.float32),
+                           g(premlp, "premlp", torch.float32), bool(want_row))

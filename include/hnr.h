@@ -24,6 +24,7 @@
  *              hnr_image_features*, hnr_render_forward* (+ workspace sizing), hnr_render_train_forward / _backward / _backward_depth (+ sizing),
  *              hnr_shipped_loss*, hnr_composite, hnr_ray_depth, hnr_ray_march, hnr_voxel_downsample*, hnr_probe_select, hnr_blur_*,
  *              hnr_frame_metrics* (and the HNR_FM_* row layout), hnr_depth_fuse*, hnr_range_crop*, hnr_nearest_view, hnr_point_view_attrs,
+ *              hnr_featnet_*, hnr_point_embed,
  *              hnr_frame_batch*, hnr_frame_item, hnr_ray_miss_rank.
  *   STAGE   -- everything else (hnr_chain_*, hnr_mlp3_*, hnr_merge*, hnr_mixup_stage, hnr_proj_*, hnr_h2*, hnr_linear_*, hnr_gather_*, hnr_ksum*,
  *              hnr_segment_*, hnr_absmax, hnr_div_probe, hnr_image_features_bwd_bbox, ...): the individual stages the two single-call entries are built from.  They are exported so
@@ -876,6 +877,39 @@ int hnr_nearest_view(const float *d_xyz, int64_t N, const float *d_campos, const
  * outputs may be NULL (not all); d_feat / C / Hl / Wl are read only with d_out_feat. */
 int hnr_point_view_attrs(const float *d_xyz, int64_t n, const float *w2c, const float *c2w, const float *cam_pos_cam, const float *K, int H, int W,
                          const float *d_feat, int C, int Hl, int Wl, float *d_out_feat, float *d_out_dir, uint8_t *d_out_mask, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Point embeddings from the MVS init checkpoint: the last stage of the `load_points=2` start of a scene (run/train_ft.py:751-765).  Inference only.
+ *
+ * hnr_featnet_forward -- `FeatureNet(intermediate=True)` in eval mode, models/mvs/models.py:717-764 (the reference builds it from InPlaceABN):
+ *   conv0: 3->8, 8->8 (3x3, stride 1, pad 1); conv1: 8->16 (5x5, stride 2, pad 2), 16->16, 16->16 (3x3); conv2: 16->32 (5x5, stride 2, pad 2), 32->32,
+ *   32->32 (3x3); the eight convolutions have no bias and each is followed by y = leaky_relu((x - running_mean) * mul + bias, 0.01) with
+ *   mul = rsqrt(running_var + 1e-5) * (|weight| + 1e-5) (the activated batch norm in inference form; mul is folded by whoever packs); `toplayer`: 1x1,
+ *   32->32, with bias, no activation, applied to conv2's output.
+ *   d_images [V,3,H,W] -> d_x1 [V,8,H,W], d_x2 [V,16,H2,W2], d_x3 [V,32,H4,W4], channels-first (what hnr_point_view_attrs / hnr_point_embed sample),
+ *   H2 = (H-1)/2 + 1, H4 = (H2-1)/2 + 1 (integer division), likewise W.  fp32 direct convolution; every output is ONE chain of fused multiply-adds over
+ *   (input channel, ky, kx) in that order, zero padding included, so two runs give the same bits.
+ *   d_packed [HNR_FEATNET_PACKED_ELEMS]: per convolution, in network order, w [cin][ky][kx][cout] (the transpose of torch's [cout][cin][ky][kx]),
+ *   running_mean [cout], mul [cout], bias [cout]; then the toplayer's w [cout][cin] (torch's own layout) and bias [cout].
+ *   d_scratch: hnr_featnet_scratch_elems(V, H, W) floats (negative: bad shape).  HNR_ERR_BADARG, before any launch, for a NULL pointer, V < 1,
+ *   H < 4 or W < 4 (limits: V <= 4096, H, W <= 32768). */
+#define HNR_FEATNET_PACKED_ELEMS 41368
+int64_t hnr_featnet_scratch_elems(int V, int H, int W);
+int hnr_featnet_forward(const float *d_images, int V, int H, int W, const float *d_packed, float *d_x1, float *d_x2, float *d_x3, float *d_scratch,
+                        int64_t scratch_elems, void *stream);
+
+/* hnr_point_embed -- `query_embedding` for the shipped feature string "imgfeat_0_0123 dir_0 point_conf" with shading_feature_mlp_layer0 = 1
+ * (models/mvs/mvs_points_model.py:225-259), one view, one launch: projection, mask, direction and samples are those of hnr_point_view_attrs (the same
+ * device functions: bit-equal results), the feature maps are one view of hnr_featnet_forward's pyramid for the H x W image d_image [3,H,W]:
+ *   row = [x1 8 | x2 16 | x3 32 | colour 3 | dir 3 | conf = 1]  (a point outside the frame: zero features and colour, its direction; it still goes
+ *   through premlp, as in the reference);  h = leaky_relu(b0 + row W0^T, 0.01);  d_emb [n,32] = leaky_relu(b1 + h W1^T, 0.01), each sum one chain of
+ *   fused multiply-adds starting from the bias, inputs in ascending order.
+ *   d_premlp [HNR_PREMLP_PACKED_ELEMS]: W0^T [63][32], b0 [32], W1^T [32][32], b1 [32] (the transposes of nn.Linear's weights).
+ *   d_color [n,3], d_dir [n,3]; d_row [n,63] (optional, NULL: not written) is the row premlp saw.  1 <= n <= (2^31 - 1) * 256, 4 <= H, W <= 32768. */
+#define HNR_PREMLP_PACKED_ELEMS 3104
+int hnr_point_embed(const float *d_xyz, int64_t n, const float *w2c, const float *c2w, const float *cam_pos_cam, const float *K, int H, int W,
+                    const float *d_image, const float *d_x1, const float *d_x2, const float *d_x3, const float *d_premlp, float *d_emb, float *d_color,
+                    float *d_dir, float *d_row, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * The per-step data path: a device-resident frame bank and the ray batch drawn from it (csrc/frames.hip).  Replaces the dataset item of the
