@@ -1,6 +1,7 @@
 """Inputs and float64 restatements for tests/test_image_branch.py (CPU) and tests/test_image_branch_gpu.py: the reference-view ("image") branch --
 reprojection into V views, truncation to a pixel + bounds rule, feature gather, merge over the views (models/aggregators/point_aggregators.py:1047-1217
 of the reference) and the transpose of the gather and of F.interpolate.  Plain numpy / torch; imports nothing from the product."""
+import functools
 import math
 
 import numpy as np
@@ -20,14 +21,24 @@ BWD_CASES = [(1, 1, (9, 7), False), (1, 37, (37, 51), True), (1, 1100, (48, 64),
              (9, 37, (48, 64), False), (9, 1100, (37, 51), True), (9, 1, (9, 7), True), (9, 1100, (9, 7), False)]
 
 
+# the fused merge stage (tests/test_fused_stages_gpu.py), V = 4: a wave owns 8 samples (7, 8, 9), a workgroup 12 waves (97 = one sample in a second
+# workgroup); 33 is run by the child processes of the other kernel forms only
+FUSED_N = (1, 7, 8, 9, 37, 97, 1100)
+FUSED_CASES = [(n, hw) for n in FUSED_N for hw in FWD_HW]
+FUSED_CHILD_N = (1, 33, 1100)
+FUSED_CHILD_HW = (37, 51)
+
+
 def case_seed(V, n, hw):
     return 100000 * V + 10 * n + hw[0]
 
 
 def all_sample_cases():
-    """(seed, n, V, H, W) of every random_samples / make_views call of the GPU module."""
+    """(seed, n, V, H, W) of every random_samples / make_views call of the GPU modules."""
     out = {(case_seed(V, n, hw), n, V, hw[0], hw[1]) for V, n, hw in FWD_CASES}
     out |= {(case_seed(V, n, hw), n, V, hw[0], hw[1]) for V, n, hw, _ in BWD_CASES}
+    out |= {(case_seed(4, n, hw), n, 4, hw[0], hw[1]) for n, hw in FUSED_CASES}
+    out |= {(case_seed(4, n, FUSED_CHILD_HW), n, 4, FUSED_CHILD_HW[0], FUSED_CHILD_HW[1]) for n in FUSED_CHILD_N}
     return sorted(out)
 
 
@@ -254,16 +265,182 @@ def merge_ref(f, hm, w_last, b_last, vmask, frame_w, dtype):
     return (f * wv[..., None]).sum(0) / (wv.sum(0) + 1e-6)[:, None]
 
 
-def delta_dirs(xyz, campos, campos_n):
-    """neural_points_volumetric_model.py:296-310 in float64: [V,n,3]."""
-    x = torch.as_tensor(xyz).double()
-    cur = x - torch.as_tensor(campos).double()
+def delta_dirs(xyz, campos, campos_n, dtype=torch.float64):
+    """neural_points_volumetric_model.py:296-310 in `dtype` (float64 unless told otherwise): [V,n,3]."""
+    x = torch.as_tensor(xyz).to(dtype)
+    cur = x - torch.as_tensor(campos).to(dtype)
     cur = cur / (torch.linalg.norm(cur, dim=-1, keepdim=True) + 1e-6)
     out = []
-    for c in torch.as_tensor(campos_n).double():
+    for c in torch.as_tensor(campos_n).to(dtype):
         nv = x - c
         out.append(nv / (torch.linalg.norm(nv, dim=-1, keepdim=True) + 1e-6) - cur)
     return torch.stack(out)
+
+
+# ---- the fused per-sample stages (csrc/mlp.hip: hnr_merge_stage, hnr_mixup_stage), restated ------------------------------------------------------------
+def mlp_ref(x, Ws, bs, acts, slope, dtype, addend=None):
+    """nn.Linear + LeakyReLU(slope) layers in `dtype`: x [..., K0]; bs[l] may be None; acts[l] != 0 applies the activation after layer l;
+    addend [..., N0] is added to layer 0 before its activation.  Returns the list of every layer's output."""
+    x = torch.as_tensor(x).to(dtype)
+    outs = []
+    for l, (W, b, a) in enumerate(zip(Ws, bs, acts)):
+        y = x @ W.to(dtype).T
+        if b is not None:
+            y = y + b.to(dtype)
+        if l == 0 and addend is not None:
+            y = y + addend.to(dtype)
+        x = torch.where(y > 0, y, y * slope) if a else y
+        outs.append(x)
+    return outs
+
+
+def frame_weights_with_a_zero(valid):
+    """Frame weights [V] in [0.5, 1.5) for a case whose validity mask is `valid` [V,n], with weight 0 on the view that is the ONLY unmasked view of
+    the most samples (ties: the first), so that "every unmasked view has weight 0" occurs wherever the samples allow it.  Returns (frame_w f32 [V],
+    the view, the number of such samples)."""
+    valid = torch.as_tensor(valid).bool()
+    only = valid & (valid.sum(0) == 1)[None]
+    per_view = only.sum(1)
+    z = int(per_view.argmax())
+    V = valid.shape[0]
+    fw = (0.5 + ((torch.arange(V) * 0.37 + 0.11) % 1.0)).float()
+    fw[z] = 0.0
+    return fw, z, int(per_view[z])
+
+
+def merge_stage_ref(xyz, w2c, K, campos, campos_n, fm, H, W, pre, Ws, bs, w_last, b_last, frame_w, slope, dtype, pix=None, hidden_scale=1.0):
+    """hnr_merge_stage restated: rows [fm[v, py, px, :45] | delta_dirs] [V,n,48] (a masked row reads pixel (0,0)); merge-weight MLP with first
+    layer Ws[0] [64,48] without bias and the per-sample addend pre [n,64], then two [64,64] layers with bias, all LeakyReLU; then merge_ref.
+    pix [V,n,2]: the pixels if they are given by a table, else the float64 restatement's (the generated samples truncate alike in every precision:
+    tests/test_image_branch.py).  hidden_scale multiplies the last hidden activations (0: what the result is without them).
+    Returns dict(merged [n,45], logits [V,n], valid [V,n], hidden [V,n,64])."""
+    if pix is None:
+        pix = restated_pixels(xyz, w2c, K, H, W)
+    valid = pix[..., 0] >= 0
+    px, py = pix[..., 0].clamp(min=0), pix[..., 1].clamp(min=0)
+    V = pix.shape[0]
+    f = torch.as_tensor(fm)[torch.arange(V)[:, None], py, px][..., :45].to(dtype)                   # [V,n,45]
+    f = torch.where(valid[..., None], f, torch.zeros_like(f))
+    rows = torch.cat([f, delta_dirs(xyz, campos, campos_n, dtype)], dim=-1)                         # [V,n,48]
+    hm = mlp_ref(rows, Ws, bs, (1, 1, 1), slope, dtype, addend=torch.as_tensor(pre)[None])[-1] * hidden_scale
+    w_last, b_last = torch.as_tensor(w_last).to(dtype), torch.as_tensor(b_last).to(dtype)
+    logits = (hm * w_last).sum(-1) + b_last
+    merged = merge_ref(f, hm, w_last, b_last, valid.to(dtype), frame_w, dtype)
+    return dict(merged=merged, logits=logits, valid=valid, hidden=hm)
+
+
+def mixup_ref(X7, CF, Ws, bs, w_fin, b_fin, slope, dtype):
+    """hnr_mixup_stage restated: Y = color_mixup_block(X7[:, :90]) (acts 1, 1, 0); x = [Y + CF[:, :45] | CF[:, 45:128]];
+    rgb = sigmoid(x w_fin^T + b_fin) * 1.002 - 0.001.  Returns dict(Y [S,45], pre [S,3] (before the sigmoid), rgb [S,3])."""
+    Y = mlp_ref(torch.as_tensor(X7)[:, :90], Ws, bs, (1, 1, 0), slope, dtype)[-1]
+    cf = torch.as_tensor(CF).to(dtype)
+    x = torch.cat([Y + cf[:, :45], cf[:, 45:128]], dim=-1)
+    p = x @ torch.as_tensor(w_fin).to(dtype).reshape(3, 128).T + torch.as_tensor(b_fin).to(dtype)
+    return dict(Y=Y, pre=p, rgb=torch.sigmoid(p) * 1.002 - 0.001)
+
+
+MERGE_SLOPE = 0.01
+FUSED_CAMPOS = np.array([0.3, -0.2, 0.1], np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def _views_and_samples(n, hw):
+    seed = case_seed(4, n, hw)
+    views = make_views(seed, 4, hw[0], hw[1])
+    return views, random_samples(seed, n, views, hw[0], hw[1])
+
+
+@functools.lru_cache(maxsize=None)
+def fused_merge_case(n, hw=None, base_n=None):
+    """Host-side inputs of one hnr_merge_stage case (V = 4), all float32 and read-only by convention.  hw = None: the hand-built edge table with its
+    two views laid out as views (0, 1, 1, 0) (n is ignored; pixels from `expect`); otherwise make_views / random_samples of case_seed(4, n, hw), or
+    -- base_n given -- the base_n-sample set of that image size repeated cyclically to n samples (the per-sample rows pre and CF stay fresh).
+    w_last is scaled so that the fp64 sigmoid logits have standard deviation 1.5 (n = 1: over its four rows)."""
+    if hw is None:
+        e = edge_samples()
+        order = [0, 1, 1, 0]
+        xyz, H, W = e["xyz"], e["H"], e["W"]
+        w2c, campos_n, K, pix = e["w2c"][order].copy(), e["campos_n"][order].copy(), e["intrinsic"], e["expect"][order].clone()
+        n, seed = xyz.shape[0], 4000
+    else:
+        H, W = hw
+        views, xyz = _views_and_samples(base_n or n, hw)
+        w2c, campos_n, K = views["w2c"], views["campos_n"], views["intrinsic"]
+        pix = restated_pixels(xyz, w2c, K, H, W)
+        if base_n:
+            idx = np.arange(n) % base_n
+            xyz, pix = np.ascontiguousarray(xyz[idx]), pix[:, torch.from_numpy(idx)]
+        seed = case_seed(4, n, hw)
+    g = torch.Generator().manual_seed(seed + 17)
+    fm = torch.randn((4, H, W, 48), generator=g)
+    fm[..., 45:] = 0
+    fm[:, 0, 0, :] = 0                                        # hnr_image_features zeroes pixel (0,0): what a masked row gathers
+    dims = [(64, 48), (64, 64), (64, 64)]
+    Ws = [(torch.rand(d, generator=g) * 2 - 1) * (3.0 / d[1]) ** 0.5 for d in dims]
+    bs = [None] + [(torch.rand(64, generator=g) - 0.5) * 0.2 for _ in range(2)]
+    pre = torch.randn((n, 64), generator=g) * 0.5
+    CF = torch.randn((n, 128), generator=g)
+    w_last = torch.randn(64, generator=g)
+    b_last = torch.randn(1, generator=g) * 0.1
+    c = dict(n=n, H=H, W=W, xyz=xyz, w2c=w2c, K=K, campos=FUSED_CAMPOS, campos_n=campos_n, pix=pix, fm=fm, Ws=Ws, bs=bs, pre=pre, CF=CF, b_last=b_last,
+             slope=MERGE_SLOPE)
+    raw = merge_stage_ref(w_last=w_last, frame_w=None, dtype=torch.float64, **_ref_args(c))["logits"]
+    c["w_last"] = (w_last.double() * (1.5 / float((raw - b_last.double()).std()))).float()
+    return c
+
+
+def _ref_args(c):
+    return {k: c[k] for k in ("xyz", "w2c", "K", "campos", "campos_n", "fm", "H", "W", "pre", "Ws", "bs", "b_last", "slope", "pix") if k in c}
+
+
+def fused_merge_refs(c, frame_w=None, **override):
+    """(fp64 restatement, the same restatement in float32) of a fused_merge_case; `override` replaces inputs (campos_n=..., hidden_scale=...)."""
+    a = dict(_ref_args(c), w_last=c["w_last"], frame_w=frame_w)
+    a.update(override)
+    return merge_stage_ref(dtype=torch.float64, **a), merge_stage_ref(dtype=torch.float32, **a)
+
+
+MERGE_FACTOR, MERGE_FLOOR = 4.0, 3e-7                       # err <= 4 e32 + 3e-7
+
+
+def merge_bound(r64, r32):
+    e32 = float((r32["merged"].double() - r64["merged"]).abs().max())
+    return e32, MERGE_FACTOR * e32 + MERGE_FLOOR
+
+
+def merge_sensitivity(c, frame_w=None):
+    """How far the fp64 merged columns move (max abs) when (a) the last hidden activations are zeroed, (b) campos_n of views 1 and 2 are swapped:
+    a test that holds the kernel to `bound` sees those parts only if they move the result by much more than the bound."""
+    r64, r32 = fused_merge_refs(c, frame_w)
+    _, bound = merge_bound(r64, r32)
+    cn = np.ascontiguousarray(c["campos_n"][[0, 2, 1, 3]])
+    d_hidden = float((fused_merge_refs(c, frame_w, hidden_scale=0.0)[0]["merged"] - r64["merged"]).abs().max())
+    d_swap = float((fused_merge_refs(c, frame_w, campos_n=cn)[0]["merged"] - r64["merged"]).abs().max())
+    return bound, d_hidden, d_swap
+
+
+@functools.lru_cache(maxsize=None)
+def fused_mixup_case(S):
+    """Host-side inputs of one hnr_mixup_stage case: X7 [S,90], CF [S,128], sigma [S], the color_mixup_block weights, and color_final_block scaled
+    so that the fp64 pre-sigmoid values reach at most 1.9 in magnitude."""
+    g = torch.Generator().manual_seed(9000 + S)
+    dims = [(45, 90), (45, 45), (45, 45)]
+    Ws = [(torch.rand(d, generator=g) * 2 - 1) * (3.0 / d[1]) ** 0.5 for d in dims]
+    bs = [(torch.rand(45, generator=g) - 0.5) * 0.2 for _ in range(3)]
+    X7 = torch.randn((S, 90), generator=g)
+    CF = torch.randn((S, 128), generator=g)
+    sigma = torch.rand((S,), generator=g) * 5
+    w_fin = torch.randn((3, 128), generator=g)
+    b_fin = torch.randn(3, generator=g) * 0.1
+    c = dict(S=S, X7=X7, CF=CF, sigma=sigma, Ws=Ws, bs=bs, b_fin=b_fin, slope=MERGE_SLOPE)
+    raw = mixup_ref(X7, CF, Ws, bs, w_fin, torch.zeros(3), MERGE_SLOPE, torch.float64)["pre"]
+    c["w_fin"] = (w_fin.double() * ((1.9 - float(b_fin.abs().max())) / float(raw.abs().max()))).float()
+    return c
+
+
+def fused_mixup_refs(c):
+    a = (c["X7"], c["CF"], c["Ws"], c["bs"], c["w_fin"], c["b_fin"], c["slope"])
+    return mixup_ref(*a, torch.float64), mixup_ref(*a, torch.float32)
 
 
 # ---- whole-path tests at V > 4: the fixture's four cameras plus copies of them moved by a few centimetres ---------------------------------------------

@@ -7,6 +7,7 @@ import ctypes
 import numpy as np
 import pytest
 import torch
+import torch.nn.functional as F
 
 from tests import image_branch_ref as ib
 
@@ -66,6 +67,69 @@ def test_generated_samples_truncate_alike_in_fp32_and_fp64(seed, n, V, H, W):
     if n >= 37:
         valid = p64[..., 0] >= 0
         assert bool(valid.any()) and bool((~valid.any(0)).any())                                   # samples inside a view, samples outside every view
+
+
+_FUSED_SETS = [(0, None)] + ib.FUSED_CASES + [(n, ib.FUSED_CHILD_HW) for n in ib.FUSED_CHILD_N if (n, ib.FUSED_CHILD_HW) not in ib.FUSED_CASES]
+
+
+@pytest.mark.parametrize("n,hw", _FUSED_SETS, ids=["edge" if hw is None else "n%d_%dx%d" % (n, hw[0], hw[1]) for n, hw in _FUSED_SETS])
+def test_fused_merge_stage_inputs_are_what_the_gpu_module_assumes(n, hw):
+    """The V = 4 sets of tests/test_fused_stages_gpu.py: logits of a useful spread, samples merged to exactly 0 for both reasons, and a reference that
+    moves by far more than the tolerance when the hidden activations or the view order of campos_nearest are wrong."""
+    c = ib.fused_merge_case(n, hw)
+    n = c["n"]
+    r64, r32 = ib.fused_merge_refs(c)
+    assert r64["merged"].shape == (n, 45) and r64["logits"].shape == (4, n) and bool(torch.isfinite(r64["merged"]).all())
+    sd = float(r64["logits"].std())
+    assert 0.5 <= sd <= 3.0, sd
+    e32, bound = ib.merge_bound(r64, r32)
+    assert e32 < 1e-5 and bound == 4 * e32 + 3e-7
+    valid = r64["valid"]
+    fw, z, n_only = ib.frame_weights_with_a_zero(valid)
+    assert float(fw[z]) == 0.0 and int((fw == 0).sum()) == 1 and float(fw.min()) == 0.0 and float(fw[fw > 0].min()) >= 0.5
+    if hw is None:
+        assert torch.equal(c["pix"], ib.edge_samples()["expect"][[0, 1, 1, 0]])
+        assert bool((~valid.any(0)).any())                  # (views 0 and 3, 1 and 2 are the same camera: no sample has one unmasked view only)
+    if n >= 37 and hw is not None:
+        assert int((~valid.any(0)).sum()) >= 3                                                      # masked in all four views
+        assert n_only >= 1                                                                          # unmasked only where frame_w = 0
+        assert int((valid.sum(0) >= 2).sum()) >= n // 4                                             # the merge weights matter: several views to weigh
+    if n >= 37 or hw is None:
+        for w in (None, fw):
+            b, d_hidden, d_swap = ib.merge_sensitivity(c, w)
+            assert d_hidden > 100 * b, (d_hidden, b)
+            # (the edge table's views 1 and 2 are the same camera: nothing to swap there)
+            assert d_swap > 100 * b or hw is None, (d_swap, b)
+
+
+def test_fused_stage_restatements_are_torchs_own_layers():
+    g = torch.Generator().manual_seed(2)
+    x = torch.randn((9, 48), generator=g, dtype=torch.float64)
+    Ws = [torch.randn(d, generator=g) for d in ((64, 48), (64, 64), (5, 64))]
+    bs = [None, torch.randn(64, generator=g), torch.randn(5, generator=g)]
+    add = torch.randn((9, 64), generator=g)
+    y = F.leaky_relu(F.linear(x, Ws[0].double()) + add.double(), 0.01)
+    y = F.leaky_relu(F.linear(y, Ws[1].double(), bs[1].double()), 0.01)
+    y = F.linear(y, Ws[2].double(), bs[2].double())
+    outs = ib.mlp_ref(x, Ws, bs, (1, 1, 0), 0.01, torch.float64, addend=add)
+    assert len(outs) == 3 and outs[2].dtype == torch.float64
+    torch.testing.assert_close(outs[2], y, rtol=0, atol=1e-12)
+    assert ib.mlp_ref(x, Ws, bs, (1, 1, 0), 0.01, torch.float32)[2].dtype == torch.float32
+    # the mix-up case: pre-sigmoid values inside +-2 (so that the sigmoid does not flatten an error), colours from them
+    for S in (1, 33, 385):
+        c = ib.fused_mixup_case(S)
+        r64, r32 = ib.fused_mixup_refs(c)
+        assert float(r64["pre"].abs().max()) <= 2.0 and r64["Y"].shape == (S, 45) and r32["rgb"].dtype == torch.float32
+        x = torch.cat([r64["Y"] + c["CF"][:, :45].double(), c["CF"][:, 45:].double()], dim=1)
+        torch.testing.assert_close(r64["rgb"], torch.sigmoid(F.linear(x, c["w_fin"].double(), c["b_fin"].double())) * 1.002 - 0.001, rtol=0, atol=1e-14)
+    # frame weights: the zero goes to the view that is the only unmasked one of the most samples
+    v = torch.tensor([[1, 0, 0, 1], [0, 0, 1, 1], [0, 0, 1, 0], [0, 0, 0, 0]]).bool()
+    fw, z, k = ib.frame_weights_with_a_zero(v)
+    assert (z, k) == (0, 1) or (z, k) == (2, 1)
+    # delta view directions in float32 are the float64 ones to rounding
+    e = ib.edge_samples()
+    d64, d32 = ib.delta_dirs(e["xyz"], ib.FUSED_CAMPOS, e["campos_n"]), ib.delta_dirs(e["xyz"], ib.FUSED_CAMPOS, e["campos_n"], torch.float32)
+    assert d32.dtype == torch.float32 and float((d32.double() - d64).abs().max()) < 1e-6
 
 
 def test_fixture_samples_truncate_alike_in_their_first_views():
