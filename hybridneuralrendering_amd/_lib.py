@@ -196,6 +196,12 @@ SIGNATURES = {
     "hnr_featnet_scratch_elems": (ctypes.c_int64, [_I, _I, _I]),
     "hnr_featnet_forward": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.c_int64, _P]),
     "hnr_point_embed": (_I, [_P, ctypes.c_int64] + [ctypes.POINTER(_F)] * 4 + [_I, _I] + [_P] * 10),
+    "hnr_point_embed_conf": (_I, [_P, ctypes.c_int64] + [ctypes.POINTER(_F)] * 4 + [_I, _I] + [_P] * 11),
+    # geometric-consistency filter of MVS depth maps (csrc/geo_filter.hip)
+    "hnr_geo_consistency": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "hnr_geo_filter_select_scratch_bytes": (ctypes.c_int64, [_I, _I, _I]),
+    "hnr_geo_filter_select": (_I, [_P] * 5 + [_I, _I, _I, _P, _F, _I, ctypes.POINTER(_F), ctypes.POINTER(_F), _P, _P, _P, _P, ctypes.c_int64, _P, _P, _P, _P,
+                                   ctypes.c_int64, _P]),
     # device-resident frame bank + batch sampler (csrc/frames.hip)
     "hnr_frame_batch_scratch_bytes": (ctypes.c_int64, [_I, _I]),
     "hnr_frame_batch": (_I, [ctypes.POINTER(FrameBankC), ctypes.POINTER(FrameBankC), _P, _I, ctypes.POINTER(FrameBatchParams), _P, _I, _P,

@@ -169,9 +169,10 @@ def point_view_attrs(xyz, w2c, c2w, cpc, intrinsic, H, W, feat=None, want_dir=Tr
     return out_f, out_d, out_m
 
 
-def query_point_attributes(xyz, image_chw, c2w, w2c, intrinsic, feature_maps=None, default_conf=-1):
+def query_point_attributes(xyz, image_chw, c2w, w2c, intrinsic, feature_maps=None, default_conf=-1, conf=None):
     """World points [n,3] seen from one posed frame -> (features [1,n,sum C] or None, color [1,n,3], dir [1,n,3], conf [1,n,1]): what
-    `query_embedding` returns at train_ft.py:760 before premlp.  image_chw [3,H,W] (or [1,3,H,W]); feature_maps: list of [C,Hl,Wl]."""
+    `query_embedding` returns at train_ft.py:760 before premlp.  image_chw [3,H,W] (or [1,3,H,W]); feature_maps: list of [C,Hl,Wl].
+    conf [n]: the points' photometric confidence (the MVS start, train_ft.py:176-180), returned as [1,n,1] in place of the ones."""
     img = _lib.require_gpu(image_chw, "image_chw", torch.float32)
     img = img.reshape(img.shape[-3:]).contiguous()
     if img.shape[0] != 3:
@@ -185,6 +186,11 @@ def query_point_attributes(xyz, image_chw, c2w, w2c, intrinsic, feature_maps=Non
     if feature_maps:
         feats = torch.cat([point_view_attrs(xyz, w2c, c2w, cpc, K, H, W, feat=f.reshape(f.shape[-3:]), want_dir=False, want_mask=False)[0]
                            for f in feature_maps], dim=-1)[None]
+    if conf is not None:
+        conf = _lib.require_gpu(conf, "conf", torch.float32).reshape(-1)
+        if conf.shape[0] != color.shape[0]:
+            raise HnrError("query_point_attributes: conf must hold one value per point")
+        return feats, color[None], pdir[None], conf.reshape(1, -1, 1).clone()
     return feats, color[None], pdir[None], point_conf(color.shape[0], default_conf, color.device)
 
 
@@ -282,4 +288,80 @@ def init_cloud_from_depth(frames, opt, campos, camdir, view_frame, capacity=None
     else:
         emb = torch.cat(feats, dim=1)
     return dict(xyz=xyz, embedding=emb, color=torch.cat(colors, dim=1), dir=torch.cat(dirs, dim=1), conf=torch.cat(confs, dim=1),
+                view_of_point=sorted_ids.long())
+
+
+def init_cloud_from_mvs_depth(views, opt, init_net=None, spacemin=None, spacemax=None, alphas=None, capacity=None):
+    """`gen_points_filter_embeddings` after `gen_points` (run/train_ft.py:104-190) for `load_points=0`, `manual_depth_view=1`: the initial cloud from
+    per-view depth and confidence maps -- MVSNet's, or any other estimator's.
+
+    views: list of dict(cam_xyz [H,W,3] -- the camera-space point of every pixel, z = depth -- or depth [H,W] (cam_xyz is then K^-1 (x d, y d, d),
+    what gen_points hands over), confidence [H,W], points_mask [H,W] bool (optional: all true), intrinsic [3,3], w2c [4,4], c2w [4,4] (optional: the
+    fp32 inverse of w2c), image [3,H,W][, feature_maps]); the maps on the GPU.  opt: depth_conf_thresh, geo_cnsst_num, ranges, default_conf, vox_res
+    (and the options of init_cloud_from_depth's last stage).  spacemin / spacemax [3]: the dataset's crop (train_ft.py:144-149).
+    Stages: geo_filter.filter_views (ONE host read), the crop (folded into the filter's range mask: both are per-point comparisons), then
+    voxel.construct_vox_points_closest -- the cloud's points are the voxel CENTROIDS, view and confidence those of the voxel's picked point, as at
+    train_ft.py:164-166 -- the regrouping by source view (`points_vid`, not the nearest camera) and, per view, init_net.embed_points or
+    query_point_attributes with the filtered confidence.
+    Returns the dict init_cloud_from_depth returns; conf [1,N,1] is the filtered photometric confidence.  `alphas` (visual-hull masking) raises."""
+    from . import cloud_io, geo_filter as gf, voxel
+    if alphas is not None:
+        raise HnrError("init_cloud_from_mvs_depth: dataset.alphas (visual-hull masking, mvs_utils.alpha_masking) is not implemented")
+    gf.check_options(opt, "init_cloud_from_mvs_depth")
+    views = list(views)
+    if not views:
+        raise HnrError("init_cloud_from_mvs_depth: no view")
+    cams, confs, masks = [], [], []
+    for v in views:
+        c = v.get("cam_xyz")
+        if c is None:
+            d = _lib.require_gpu(v["depth"], "depth", torch.float32)
+            Ki = torch.inverse(torch.from_numpy(_host_f32(v["intrinsic"], (3, 3), "intrinsic"))).to(d.device)
+            py, px = torch.meshgrid(torch.arange(d.shape[0], device=d.device), torch.arange(d.shape[1], device=d.device), indexing="ij")
+            c = (Ki @ (torch.stack([px.reshape(-1), py.reshape(-1), torch.ones_like(px.reshape(-1))], dim=0) * d.reshape(-1))).t().reshape(d.shape + (3,))
+        c = _lib.require_gpu(c, "cam_xyz", torch.float32)
+        c = c.reshape(c.shape[-3:])
+        cams.append(c)
+        confs.append(_lib.require_gpu(v["confidence"], "confidence", torch.float32).reshape(c.shape[:2]))
+        m = v.get("points_mask")
+        masks.append(torch.ones(c.shape[:2], dtype=torch.bool, device=c.device) if m is None else m.reshape(c.shape[:2]))
+    dev = cams[0].device
+    ranges = [float(r) for r in getattr(opt, "ranges", [-100.0] * 6)]
+    if (spacemin is None) != (spacemax is None):
+        raise HnrError("init_cloud_from_mvs_depth: spacemin and spacemax come together")
+    if spacemin is not None:
+        lo, hi = _host_f32(spacemin, (3,), "spacemin"), _host_f32(spacemax, (3,), "spacemax")
+        if ranges[0] > -99.0:                                              # x >= a and x >= b  <=>  x >= max(a, b): exact
+            lo, hi = np.maximum(lo, np.asarray(ranges[:3], np.float32)), np.minimum(hi, np.asarray(ranges[3:], np.float32))
+        if lo[0] <= -99.0:
+            raise HnrError("init_cloud_from_mvs_depth: spacemin[0] <= -99 collides with the `keep everything` value of opt.ranges")
+        ranges = [float(r) for r in np.concatenate([lo, hi])]
+    tab = gf.CameraTables([v["intrinsic"] for v in views], [v["w2c"] for v in views], dev)
+    flt = gf.filter_views(torch.stack(cams), torch.stack(confs), torch.stack(masks), tab, opt, ranges=ranges, capacity=capacity)
+    pts, conf, vid = flt["world"], flt["conf"], flt["view"]
+    if pts.shape[0] == 0:
+        raise HnrError("init_cloud_from_mvs_depth: no point survives the filter")
+    if getattr(opt, "vox_res", 0) > 0:
+        pts, _, min_idx = voxel.construct_vox_points_closest(pts.contiguous(), opt.vox_res)
+        conf, vid = conf[min_idx], vid[min_idx]
+    perm, sorted_ids = group_by_view(vid.contiguous())
+    xyz, conf = pts[perm].contiguous(), conf[perm].contiguous()
+    colors, dirs, feats = [], [], []
+    for v, s, e in view_segments(sorted_ids.cpu().numpy()):
+        fr = views[v]
+        w2c = tab.host["E"][v]
+        c2w = fr.get("c2w")
+        c2w = tab.host["Einv"][v] if c2w is None else c2w
+        if init_net is not None:
+            f, c, d, _ = init_net.embed_points(xyz[s:e], fr["image"], c2w, w2c, fr["intrinsic"], conf=conf[s:e])
+        else:
+            f, c, d, _ = query_point_attributes(xyz[s:e], fr["image"], c2w, w2c, fr["intrinsic"], fr.get("feature_maps"), conf=conf[s:e])
+        colors.append(c); dirs.append(d); feats.append(f)
+    if any(f is None for f in feats):
+        if not all(f is None for f in feats):
+            raise HnrError("init_cloud_from_mvs_depth: every view must come with feature_maps, or none")
+        emb, _ = cloud_io.init_point_features(xyz, opt.point_features_dim, opt.feature_init_method, xyz.device, opt.point_features_dim)
+    else:
+        emb = torch.cat(feats, dim=1)
+    return dict(xyz=xyz, embedding=emb, color=torch.cat(colors, dim=1), dir=torch.cat(dirs, dim=1), conf=conf.reshape(1, -1, 1),
                 view_of_point=sorted_ids.long())

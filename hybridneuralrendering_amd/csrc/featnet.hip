@@ -142,13 +142,13 @@ __device__ __forceinline__ void pe_level(bool mask, const ViewTaps &t, const flo
     }
 }
 
-// one point per thread.  The row [x1 8 | x2 16 | x3 32 | colour 3 | dir 3 | conf = 1] is consumed a few inputs at a time, in its own order, so only the
+// one point per thread.  The row [x1 8 | x2 16 | x3 32 | colour 3 | dir 3 | conf] is consumed a few inputs at a time, in its own order, so only the
 // 32 sums of premlp's first layer stay in registers; premlp's weights sit in LDS and every lane reads the same word at a time (broadcast).  A point
-// outside the frame has zero features and colour: its row still goes through premlp.
+// outside the frame has zero features and colour: its row still goes through premlp.  conf NULL: the row's last column is 1.
 __global__ void __launch_bounds__(256) point_embed_kernel(const float *__restrict__ xyz, long long n, ViewCam vc, int H, int W, const float *__restrict__ img,
                                                           const float *__restrict__ x1, const float *__restrict__ x2, const float *__restrict__ x3, int H2, int W2,
                                                           int H4, int W4, const float *__restrict__ premlp, float *__restrict__ emb, float *__restrict__ color,
-                                                          float *__restrict__ dir, float *__restrict__ row_out)
+                                                          float *__restrict__ dir, float *__restrict__ row_out, const float *__restrict__ conf)
 {
     __shared__ float wsm[HNR_PREMLP_PACKED_ELEMS];
     for (int e = threadIdx.x; e < HNR_PREMLP_PACKED_ELEMS; e += 256) wsm[e] = premlp[e];
@@ -169,7 +169,7 @@ __global__ void __launch_bounds__(256) point_embed_kernel(const float *__restric
     pe_level(mask, t2, x3, (size_t)H4 * W4, W4, 32, 24, wsm, h, row);
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) tail[ch] = mask ? view_sample(t0, img + ch * p0, W) : 0.f;
-    tail[6] = 1.f;
+    tail[6] = conf ? conf[i] : 1.f;
     pe_fold<7>(tail, 56, wsm, h, row);
 #pragma unroll
     for (int q = 0; q < 3; ++q) { color[3 * i + q] = tail[q]; dir[3 * i + q] = tail[3 + q]; }
@@ -224,6 +224,13 @@ extern "C" int hnr_point_embed(const float *d_xyz, int64_t n, const float *w2c, 
                                const float *d_image, const float *d_x1, const float *d_x2, const float *d_x3, const float *d_premlp, float *d_emb,
                                float *d_color, float *d_dir, float *d_row, void *stream)
 {
+    return hnr_point_embed_conf(d_xyz, n, w2c, c2w, cam_pos_cam, K, H, W, d_image, d_x1, d_x2, d_x3, d_premlp, nullptr, d_emb, d_color, d_dir, d_row, stream);
+}
+
+extern "C" int hnr_point_embed_conf(const float *d_xyz, int64_t n, const float *w2c, const float *c2w, const float *cam_pos_cam, const float *K, int H, int W,
+                                    const float *d_image, const float *d_x1, const float *d_x2, const float *d_x3, const float *d_premlp, const float *d_conf,
+                                    float *d_emb, float *d_color, float *d_dir, float *d_row, void *stream)
+{
     if (!d_xyz || !w2c || !c2w || !cam_pos_cam || !K || !d_image || !d_x1 || !d_x2 || !d_x3 || !d_premlp || !d_emb || !d_color || !d_dir) {
         set_error("hnr_point_embed: NULL argument"); return HNR_ERR_BADARG;
     }
@@ -234,7 +241,7 @@ extern "C" int hnr_point_embed(const float *d_xyz, int64_t n, const float *w2c, 
     view_cam_fill(vc, w2c, c2w, cam_pos_cam, K);
     const int H2 = (H - 1) / 2 + 1, W2 = (W - 1) / 2 + 1, H4 = (H2 - 1) / 2 + 1, W4 = (W2 - 1) / 2 + 1;
     point_embed_kernel<<<cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(d_xyz, (long long)n, vc, H, W, d_image, d_x1, d_x2, d_x3, H2, W2, H4, W4, d_premlp, d_emb,
-                                                                      d_color, d_dir, d_row);
+                                                                      d_color, d_dir, d_row, d_conf);
     HNR_LAUNCH_CHECK();
     return HNR_OK;
 }

@@ -66,8 +66,9 @@ def featnet_forward(images, packed):
     return tuple(outs)
 
 
-def point_embed(xyz, w2c, c2w, cpc, intrinsic, image, x1, x2, x3, premlp, want_row=False):
-    """hnr_point_embed for one view: (emb [n,32], color [n,3], dir [n,3], row [n,63] or None).  image [3,H,W]; x1 / x2 / x3 its pyramid, channels first."""
+def point_embed(xyz, w2c, c2w, cpc, intrinsic, image, x1, x2, x3, premlp, want_row=False, conf=None):
+    """hnr_point_embed for one view: (emb [n,32], color [n,3], dir [n,3], row [n,63] or None).  image [3,H,W]; x1 / x2 / x3 its pyramid, channels first.
+    conf [n] (optional): the photometric confidence premlp sees in the row's last column (hnr_point_embed_conf); None: ones."""
     from .cloud_init import _cf, _host_f32
     L = _lib.lib()
     xyz = _lib.require_gpu(xyz, "xyz", torch.float32).reshape(-1, 3)
@@ -85,14 +86,23 @@ def point_embed(xyz, w2c, c2w, cpc, intrinsic, image, x1, x2, x3, premlp, want_r
     n, dev = int(xyz.shape[0]), xyz.device
     if any(t.device != dev for t in [image, premlp] + maps):
         raise HnrError("point_embed: every tensor must be on xyz's device")
+    if conf is not None:
+        conf = _lib.require_gpu(conf, "conf", torch.float32).reshape(-1)
+        if conf.shape[0] != n or conf.device != dev:
+            raise HnrError("point_embed: conf must hold one value per point, on xyz's device")
     emb, color, pdir = (torch.empty((n, c), dtype=torch.float32, device=dev) for c in (32, 3, 3))
     row = torch.empty((n, 63), dtype=torch.float32, device=dev) if want_row else None
     if n > 0:
         a = [_host_f32(w2c, (4, 4), "w2c"), _host_f32(c2w, (4, 4), "c2w"), _host_f32(cpc, (3,), "cam_pos_cam"), _host_f32(intrinsic, (3, 3), "intrinsic")]
         with torch.cuda.device(dev):
-            _lib.check(L.hnr_point_embed(_lib.ptr(xyz), n, _cf(a[0]), _cf(a[1]), _cf(a[2]), _cf(a[3]), H, W, _lib.ptr(image), _lib.ptr(maps[0]),
-                                         _lib.ptr(maps[1]), _lib.ptr(maps[2]), _lib.ptr(premlp), _lib.ptr(emb), _lib.ptr(color), _lib.ptr(pdir), _lib.ptr(row),
-                                         _lib.stream()), "hnr_point_embed")
+            if conf is None:
+                _lib.check(L.hnr_point_embed(_lib.ptr(xyz), n, _cf(a[0]), _cf(a[1]), _cf(a[2]), _cf(a[3]), H, W, _lib.ptr(image), _lib.ptr(maps[0]),
+                                             _lib.ptr(maps[1]), _lib.ptr(maps[2]), _lib.ptr(premlp), _lib.ptr(emb), _lib.ptr(color), _lib.ptr(pdir), _lib.ptr(row),
+                                             _lib.stream()), "hnr_point_embed")
+            else:
+                _lib.check(L.hnr_point_embed_conf(_lib.ptr(xyz), n, _cf(a[0]), _cf(a[1]), _cf(a[2]), _cf(a[3]), H, W, _lib.ptr(image), _lib.ptr(maps[0]),
+                                                  _lib.ptr(maps[1]), _lib.ptr(maps[2]), _lib.ptr(premlp), _lib.ptr(conf), _lib.ptr(emb), _lib.ptr(color),
+                                                  _lib.ptr(pdir), _lib.ptr(row), _lib.stream()), "hnr_point_embed_conf")
     return emb, color, pdir, row
 
 
@@ -210,10 +220,12 @@ class MvsInit(nn.Module):
         """imgs [B,V,3,H,W] -> [x, x1, x2, x3] (MvsPointsModel.get_image_features)."""
         return self.FeatureNet(imgs)
 
-    def embed_points(self, xyz_world, image_chw, c2w, w2c, intrinsic, default_conf=-1, feats=None, want_row=False):
+    def embed_points(self, xyz_world, image_chw, c2w, w2c, intrinsic, default_conf=-1, feats=None, want_row=False, conf=None):
         """What run/train_ft.py:759-761 computes for the points of one view: (embedding [1,n,32], color [1,n,3], dir [1,n,3], conf [1,n,1]).
         image_chw [3,H,W] (or [1,3,H,W]); w2c None: the fp32 inverse of c2w, as the reference forms it.  feats: the view's [x, x1, x2, x3] from
-        get_image_features when it is already there.  want_row: a fifth result, the [n,63] rows premlp saw."""
+        get_image_features when it is already there.  want_row: a fifth result, the [n,63] rows premlp saw.
+        conf [n]: the points' photometric confidence (run/train_ft.py:176-180, the MVS start): premlp sees it in place of the ones and it is returned
+        as [1,n,1], untouched by default_conf (which the reference applies on the depth-frame path only); None: today's ones."""
         from . import cloud_init as ci
         img = _lib.require_gpu(image_chw, "image_chw", torch.float32)
         img = img.reshape(img.shape[-3:]).contiguous()
@@ -223,6 +235,8 @@ class MvsInit(nn.Module):
             feats = self.get_image_features(img[None, None])
         w2c = torch.inverse(torch.from_numpy(ci._host_f32(c2w, (4, 4), "c2w"))).numpy() if w2c is None else w2c
         cpc = ci.cam_pos_cam(c2w, w2c)
-        emb, color, pdir, row = point_embed(xyz_world, w2c, c2w, cpc, intrinsic, img, feats[1][0], feats[2][0], feats[3][0], self.premlp_packed(), want_row)
-        out = (emb[None], color[None], pdir[None], ci.point_conf(emb.shape[0], default_conf, emb.device))
+        emb, color, pdir, row = point_embed(xyz_world, w2c, c2w, cpc, intrinsic, img, feats[1][0], feats[2][0], feats[3][0], self.premlp_packed(), want_row,
+                                            conf=conf)
+        out = (emb[None], color[None], pdir[None],
+               ci.point_conf(emb.shape[0], default_conf, emb.device) if conf is None else conf.detach().to(torch.float32).reshape(1, -1, 1).clone())
         return out + (row,) if want_row else out

@@ -24,7 +24,7 @@
  *              hnr_image_features*, hnr_render_forward* (+ workspace sizing), hnr_render_train_forward / _backward / _backward_depth (+ sizing),
  *              hnr_shipped_loss*, hnr_composite, hnr_ray_depth, hnr_ray_march, hnr_voxel_downsample*, hnr_probe_select, hnr_blur_*,
  *              hnr_frame_metrics* (and the HNR_FM_* row layout), hnr_depth_fuse*, hnr_range_crop*, hnr_nearest_view, hnr_point_view_attrs,
- *              hnr_featnet_*, hnr_point_embed,
+ *              hnr_featnet_*, hnr_point_embed*, hnr_geo_consistency, hnr_geo_filter_select*,
  *              hnr_frame_batch*, hnr_frame_item, hnr_ray_miss_rank.
  *   STAGE   -- everything else (hnr_chain_*, hnr_mlp3_*, hnr_merge*, hnr_mixup_stage, hnr_proj_*, hnr_h2*, hnr_linear_*, hnr_gather_*, hnr_ksum*,
  *              hnr_segment_*, hnr_absmax, hnr_div_probe, hnr_image_features_bwd_bbox, ...): the individual stages the two single-call entries are built from.  They are exported so
@@ -910,6 +910,11 @@ int hnr_featnet_forward(const float *d_images, int V, int H, int W, const float 
 int hnr_point_embed(const float *d_xyz, int64_t n, const float *w2c, const float *c2w, const float *cam_pos_cam, const float *K, int H, int W,
                     const float *d_image, const float *d_x1, const float *d_x2, const float *d_x3, const float *d_premlp, float *d_emb, float *d_color,
                     float *d_dir, float *d_row, void *stream);
+/* The same with a photometric confidence per point: d_conf [n] (NULL: ones, hnr_point_embed itself) takes the row's last column, as
+ * `query_embedding` does when it is handed one (mvs_points_model.py:252-258, from run/train_ft.py:176-180). */
+int hnr_point_embed_conf(const float *d_xyz, int64_t n, const float *w2c, const float *c2w, const float *cam_pos_cam, const float *K, int H, int W,
+                         const float *d_image, const float *d_x1, const float *d_x2, const float *d_x3, const float *d_premlp, const float *d_conf,
+                         float *d_emb, float *d_color, float *d_dir, float *d_row, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * The per-step data path: a device-resident frame bank and the ray batch drawn from it (csrc/frames.hip).  Replaces the dataset item of the
@@ -1002,6 +1007,48 @@ int hnr_frame_item(const hnr_frame_bank *target, const hnr_frame_bank *reference
 int hnr_ray_miss_rank(const float *d_color /*[R,3]*/, const float *d_gt /*[R,3]*/, const int8_t *d_ray_mask /*[R]*/, int R,
                       const int32_t *d_frame_id /*[1], device*/, int32_t *d_ids /*[n]*/, float *d_losses /*[n]*/, int n,
                       float *d_miss_out /*[2] or NULL: loss, number of missed rays*/, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Geometric-consistency filter of MVS depth maps: the `load_points=0`, `manual_depth_view=1` start of a scene (csrc/geo_filter.hip).  Replaces
+ * models/mvs/filter_utils.py:157-297 (`reproject_with_depth_gpu`, `check_geometric_consistency_gpu`, `filter_by_masks_gpu`, `reassign_conf`) and
+ * `range_mask_torch` (:146-154), called from run/train_ft.py:105-114: a Python double loop over the views with about 35 full-frame torch ops and
+ * three matrix inverses per ordered pair.  Stream-ordered, nothing is allocated, nothing is read back, no atomics: two runs give the same bits.
+ * Every fp32 operation below is rounded on its own, in the order written (divisions and the square root correctly rounded);
+ * tests/geo_filter_ref.py restates them in NumPy and the GPU tests compare bits.  Depth maps must be finite.
+ *
+ * hnr_geo_consistency -- one launch for all reference views (workgroups of 32 x 8 pixels; grid z = the reference view).
+ *   d_depth [V,H,W]; d_K, d_Kinv [V,3,3]; d_E (world to camera), d_Einv [V,4,4], row-major, on the device (the caller inverts, in fp32).
+ *   For the reference view r, pixel (x, y) with d = depth[r][y][x], and every source view s != r in ASCENDING order:
+ *     mat3(M, a)[c] = (M[c][0]*a0 + M[c][1]*a1) + M[c][2]*a2;         mat34(T, a)[c] = ((T[c][0]*a0 + T[c][1]*a1) + T[c][2]*a2) + T[c][3];
+ *     pair(A, B)[i][j] = ((A[i][0]*B[0][j] + A[i][1]*B[1][j]) + A[i][2]*B[2][j]) + A[i][3]*B[3][j]   (rows 0..2; formed once per workgroup and pair)
+ *     p  = mat3(Kinv_r, (x*d, y*d, d));      q  = mat34(pair(E_s, Einv_r), p);      k = mat3(K_s, q);     xs = k0 / k2,  ys = k1 / k2
+ *     sd = bilinear sample of depth[s] at (xs, ys), border clamp (grid_sample(align_corners=True, padding_mode='border'), without the round trip
+ *          through [-1, 1]):  cx = fmin(fmax(xs, 0), W-1) (a NaN becomes 0), x0 = floor(cx), wx1 = cx - x0, wx0 = (x0 + 1) - cx, likewise y;
+ *          sd = (((wx0*wy0)*t00 + (wx1*wy0)*t01) + (wx0*wy1)*t10) + (wx1*wy1)*t11, t_ab = depth[s][min(y0+a, H-1)][min(x0+b, W-1)]
+ *     p' = mat3(Kinv_s, (xs*sd, ys*sd, sd)); q' = mat34(pair(E_r, Einv_s), p');     k' = mat3(K_r, q');   xr = k'0 / k'2, yr = k'1 / k'2
+ *     ex = xr - x, ey = yr - y;  dist = sqrt(ex*ex + ey*ey);  rel = |q'2 - d| / d;   ok = dist < 1 && rel < 0.01f   (inf / NaN fail both)
+ *     count += ok;  sum += ok ? q'2 : 0
+ *   d_count [V,H,W] int32 = count;  d_depth_avg [V,H,W] = (sum + d) / (float)(count + 1)   (V = 1: count 0, depth_avg = depth).
+ *   HNR_ERR_BADARG, before any launch: a NULL pointer, V < 1 or > 65535, H or W outside 2 .. 32768, V*H*W > 2^30.
+ *
+ * hnr_geo_filter_select -- final mask, world points, range mask, confidence, ordered compaction (flags, one scan, scatter).
+ *   keep = d_conf > conf_thresh && d_points_mask != 0 && (V == 1 || count >= geo_cnsst_num)
+ *   cam = (d_cam_xyz[v][y][x][0], d_cam_xyz[v][y][x][1], depth_avg)   (x and y are NOT rescaled to the averaged depth: filter_utils.py:264-265)
+ *   world = mat34(Einv_v, cam);  keep &&= ranges[0:3] <= world <= ranges[3:6] unless ranges[0] <= -99 (6 host floats)
+ *   conf_table != NULL (opt.default_conf > 1: `reassign_conf`): conf *= conf_table[min(max(count - geo_cnsst_num + 1, 1), 10) - 1]; the caller
+ *   computes the ten host floats 1 - 1 / 1.14869^k, k = 1..10, with the reference's own expression.
+ *   The kept pixels of all views, views ascending, row-major inside a view (what train_ft.py:133-137 concatenates), go to d_world [capacity,3],
+ *   d_cam [capacity,3], d_conf_out [capacity], d_view [capacity] int32.  d_view_counts [V] int64 = kept pixels per view, d_total[0] = their sum (also
+ *   beyond capacity: then d_status[0] |= HNR_CLOUD_OVERFLOW -- the caller zeroes the word -- and nothing is written at or past row `capacity`).  d_cam_xyz [V,H,W,3], d_conf [V,H,W],
+ *   d_points_mask [V,H,W] uint8.  d_scratch: hnr_geo_filter_select_scratch_bytes(V, H, W) bytes (negative: bad shape).
+ *   HNR_ERR_BADARG, before any launch: a NULL pointer (conf_table aside), the shape limits above, capacity < 0, geo_cnsst_num < 0, short scratch. */
+int hnr_geo_consistency(const float *d_depth, int V, int H, int W, const float *d_K, const float *d_Kinv, const float *d_E, const float *d_Einv,
+                        int32_t *d_count, float *d_depth_avg, void *stream);
+int64_t hnr_geo_filter_select_scratch_bytes(int V, int H, int W);
+int hnr_geo_filter_select(const float *d_cam_xyz, const float *d_conf, const uint8_t *d_points_mask, const int32_t *d_count, const float *d_depth_avg,
+                          int V, int H, int W, const float *d_Einv, float conf_thresh, int geo_cnsst_num, const float *ranges, const float *conf_table,
+                          float *d_world, float *d_cam, float *d_conf_out, int32_t *d_view, int64_t capacity, int64_t *d_view_counts, int64_t *d_total,
+                          int32_t *d_status, void *d_scratch, int64_t scratch_bytes, void *stream);
 
 #ifdef __cplusplus
 }
