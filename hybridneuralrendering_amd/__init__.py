@@ -15,4 +15,7 @@ def __getattr__(name):
     if name in ("lighting_fast_querier", "VoxelGrid", "march_query", "compact_rays", "tmid_table"):
         from . import querier
         return getattr(querier, name)
+    if name in ("MVSNet", "depth_views"):
+        from . import mvs_depth
+        return getattr(mvs_depth, name)
     raise AttributeError(name)

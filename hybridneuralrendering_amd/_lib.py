@@ -14,6 +14,8 @@ LIB_PATH = os.environ.get("HNR_LIB_PATH") or os.path.join(_HERE, "libhnr_hip.so"
 NCOUNTS = 9
 FEATNET_PACKED_ELEMS = 41368           # HNR_FEATNET_PACKED_ELEMS
 PREMLP_PACKED_ELEMS = 3104             # HNR_PREMLP_PACKED_ELEMS
+MVSNET_FEATURE_PACKED_ELEMS = 40248    # HNR_MVSNET_FEATURE_PACKED_ELEMS
+MVSNET_REG_PACKED_ELEMS = 298297       # HNR_MVSNET_REG_PACKED_ELEMS
 CNT = dict(RAYS_HIT=0, SAMPLES=1, RAYS_VALID=2, NEIGHBOURS=3, CELLS_VISITED=4, CANDIDATES=5, SAMPLES_VALID=6, SAMPLES_SMALL=7, SAMPLES_TINY=8)
 
 
@@ -202,6 +204,14 @@ SIGNATURES = {
     "hnr_geo_filter_select_scratch_bytes": (ctypes.c_int64, [_I, _I, _I]),
     "hnr_geo_filter_select": (_I, [_P] * 5 + [_I, _I, _I, _P, _F, _I, ctypes.POINTER(_F), ctypes.POINTER(_F), _P, _P, _P, _P, ctypes.c_int64, _P, _P, _P, _P,
                                    ctypes.c_int64, _P]),
+    # depth maps from the pretrained MVSNet (csrc/mvsnet.hip)
+    "hnr_mvsnet_feature_scratch_elems": (ctypes.c_int64, [_I, _I, _I]),
+    "hnr_mvsnet_feature": (_I, [_P, _I, _I, _I, _P, _P, _P, ctypes.c_int64, _P]),
+    "hnr_mvsnet_cost_volume": (_I, [_P, _I, _I, _I, _P, _P, _I, _P, _P]),
+    "hnr_mvsnet_cost_reg_scratch_elems": (ctypes.c_int64, [_I, _I, _I]),
+    "hnr_mvsnet_cost_reg": (_I, [_P, _I, _I, _I, _P, _P, _P, ctypes.c_int64, _P]),
+    "hnr_mvsnet_depth_head": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "hnr_mvsnet_depth_points": (_I, [_P, _P, _I, _I, _I, _I, _F, _F, ctypes.POINTER(_F), _P, _P, _P, _P]),
     # device-resident frame bank + batch sampler (csrc/frames.hip)
     "hnr_frame_batch_scratch_bytes": (ctypes.c_int64, [_I, _I]),
     "hnr_frame_batch": (_I, [ctypes.POINTER(FrameBankC), ctypes.POINTER(FrameBankC), _P, _I, ctypes.POINTER(FrameBatchParams), _P, _I, _P,

@@ -293,7 +293,7 @@ def init_cloud_from_depth(frames, opt, campos, camdir, view_frame, capacity=None
 
 def init_cloud_from_mvs_depth(views, opt, init_net=None, spacemin=None, spacemax=None, alphas=None, capacity=None):
     """`gen_points_filter_embeddings` after `gen_points` (run/train_ft.py:104-190) for `load_points=0`, `manual_depth_view=1`: the initial cloud from
-    per-view depth and confidence maps -- MVSNet's, or any other estimator's.
+    per-view depth and confidence maps -- the pretrained MVSNet's (mvs_depth.depth_views returns exactly these `views`), or any other estimator's.
 
     views: list of dict(cam_xyz [H,W,3] -- the camera-space point of every pixel, z = depth -- or depth [H,W] (cam_xyz is then K^-1 (x d, y d, d),
     what gen_points hands over), confidence [H,W], points_mask [H,W] bool (optional: all true), intrinsic [3,3], w2c [4,4], c2w [4,4] (optional: the

@@ -13,6 +13,8 @@
 //   hnr::point_view_attrs                hnr_point_view_attrs                    (homo_warp_nongrid + extract_from_2d_grid + the `dir` branch of query_embedding)
 //   hnr::featnet_forward                 hnr_featnet_forward                     (FeatureNet(intermediate=True) in eval mode, models/mvs/models.py:717-764)
 //   hnr::point_embed                     hnr_point_embed                         (query_embedding with premlp, models/mvs/mvs_points_model.py:225-259)
+//   hnr::mvsnet_feature / _cost_volume / _cost_reg / _depth_head / _depth_points   hnr_mvsnet_*   (models/depth_estimators/mvsnet.py in eval mode and
+//                                        the tail of MvsPointsModel.gen_points, models/mvs/mvs_points_model.py:300-341)
 // Nothing is computed here: every op validates its tensors, fills the C structs, takes the current HIP stream and calls the library.  Errors
 // of the library surface as c10::Error with hnr_last_error() as the message.  Host code only (no kernels): built by g++ against libtorch.
 #include <ATen/ATen.h>
@@ -473,6 +475,94 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> point_embed(const Tensor &xyz, c10::A
     return {emb, color, dir, row};
 }
 
+// ---- hnr::mvsnet_*: the depth estimator stage by stage (hnr_mvsnet_* in include/hnr.h)
+Tensor mvsnet_feature(const Tensor &images, const Tensor &packed)
+{
+    TORCH_CHECK(images.dim() == 4 && images.size(1) == 3, "hnr::mvsnet_feature: images must be [V,3,H,W]");
+    TORCH_CHECK(packed.dim() == 1 && packed.size(0) == HNR_MVSNET_FEATURE_PACKED_ELEMS && packed.device() == images.device(),
+                "hnr::mvsnet_feature: packed must hold HNR_MVSNET_FEATURE_PACKED_ELEMS values on the images' device");
+    const c10::DeviceGuard guard(images.device());
+    const int64_t V = images.size(0), H = images.size(2), W = images.size(3);
+    const int64_t ns = (V <= INT32_MAX && H <= INT32_MAX && W <= INT32_MAX) ? hnr_mvsnet_feature_scratch_elems((int)V, (int)H, (int)W) : -1;
+    TORCH_CHECK(ns >= 0, "hnr::mvsnet_feature: unsupported shape (1 <= V <= 64, 4 <= H, W <= 32768)");
+    Tensor feat = new_f32({V, 32, (((H - 1) / 2 + 1) - 1) / 2 + 1, (((W - 1) / 2 + 1) - 1) / 2 + 1}, images), scratch = new_f32({ns}, images);
+    hnr_check(hnr_mvsnet_feature(fptr(images, "images"), (int)V, (int)H, (int)W, fptr(packed, "packed"), feat.data_ptr<float>(), scratch.data_ptr<float>(), ns,
+                                 cur_stream(images)),
+              "hnr_mvsnet_feature");
+    return feat;
+}
+
+bool mvsnet_volume_ok(int64_t D, int64_t h, int64_t w)
+{
+    return D >= 1 && D <= 4096 && h >= 2 && h <= 8192 && w >= 2 && w <= 8192 && D * h * w <= ((int64_t)1 << 26);
+}
+
+Tensor mvsnet_cost_volume(const Tensor &feat, const Tensor &proj, const Tensor &depth_values)
+{
+    TORCH_CHECK(feat.dim() == 4 && feat.size(1) == 32, "hnr::mvsnet_cost_volume: feat must be [V,32,h,w]");
+    const int64_t V = feat.size(0), h = feat.size(2), w = feat.size(3);
+    TORCH_CHECK(proj.dim() == 3 && proj.size(0) == V && proj.size(1) == 3 && proj.size(2) == 4 && depth_values.dim() == 1,
+                "hnr::mvsnet_cost_volume: proj must be [V,3,4], depth_values [D]");
+    TORCH_CHECK(proj.device() == feat.device() && depth_values.device() == feat.device(), "hnr::mvsnet_cost_volume: every tensor must be on feat's device");
+    const int64_t D = depth_values.size(0);
+    TORCH_CHECK(V >= 1 && V <= 64 && mvsnet_volume_ok(D, h, w), "hnr::mvsnet_cost_volume: unsupported shape");
+    const c10::DeviceGuard guard(feat.device());
+    Tensor vol = new_f32({32, D, h, w}, feat);
+    hnr_check(hnr_mvsnet_cost_volume(fptr(feat, "feat"), (int)V, (int)h, (int)w, fptr(proj, "proj"), fptr(depth_values, "depth_values"), (int)D,
+                                     vol.data_ptr<float>(), cur_stream(feat)),
+              "hnr_mvsnet_cost_volume");
+    return vol;
+}
+
+Tensor mvsnet_cost_reg(const Tensor &volume, const Tensor &packed)
+{
+    TORCH_CHECK(volume.dim() == 4 && volume.size(0) == 32, "hnr::mvsnet_cost_reg: volume must be [32,D,h,w]");
+    TORCH_CHECK(packed.dim() == 1 && packed.size(0) == HNR_MVSNET_REG_PACKED_ELEMS && packed.device() == volume.device(),
+                "hnr::mvsnet_cost_reg: packed must hold HNR_MVSNET_REG_PACKED_ELEMS values on the volume's device");
+    const int64_t D = volume.size(1), h = volume.size(2), w = volume.size(3);
+    const int64_t ns = mvsnet_volume_ok(D, h, w) ? hnr_mvsnet_cost_reg_scratch_elems((int)D, (int)h, (int)w) : -1;
+    TORCH_CHECK(ns >= 0, "hnr::mvsnet_cost_reg: unsupported shape (D, h and w multiples of 8, D <= 4096, h, w <= 8192, D*h*w <= 2^26)");
+    const c10::DeviceGuard guard(volume.device());
+    Tensor logits = new_f32({D, h, w}, volume), scratch = new_f32({ns}, volume);
+    hnr_check(hnr_mvsnet_cost_reg(fptr(volume, "volume"), (int)D, (int)h, (int)w, fptr(packed, "packed"), logits.data_ptr<float>(), scratch.data_ptr<float>(), ns,
+                                  cur_stream(volume)),
+              "hnr_mvsnet_cost_reg");
+    return logits;
+}
+
+// -> (depth [h,w], confidence [h,w], prob [D,h,w] or [0])
+std::tuple<Tensor, Tensor, Tensor> mvsnet_depth_head(const Tensor &logits, const Tensor &depth_values, bool want_prob)
+{
+    TORCH_CHECK(logits.dim() == 3 && depth_values.dim() == 1 && depth_values.size(0) == logits.size(0) && depth_values.device() == logits.device(),
+                "hnr::mvsnet_depth_head: logits must be [D,h,w], depth_values [D] on the same device");
+    const int64_t D = logits.size(0), h = logits.size(1), w = logits.size(2);
+    TORCH_CHECK(mvsnet_volume_ok(D, h, w), "hnr::mvsnet_depth_head: unsupported shape");
+    const c10::DeviceGuard guard(logits.device());
+    Tensor depth = new_f32({h, w}, logits), conf = new_f32({h, w}, logits), prob = want_prob ? new_f32({D, h, w}, logits) : new_f32({0}, logits);
+    hnr_check(hnr_mvsnet_depth_head(fptr(logits, "logits"), fptr(depth_values, "depth_values"), (int)D, (int)h, (int)w, depth.data_ptr<float>(),
+                                    conf.data_ptr<float>(), want_prob ? prob.data_ptr<float>() : nullptr, cur_stream(logits)),
+              "hnr_mvsnet_depth_head");
+    return {depth, conf, prob};
+}
+
+// -> (cam_xyz [H,W,3], confidence [H,W], points_mask [H,W] uint8)
+std::tuple<Tensor, Tensor, Tensor> mvsnet_depth_points(const Tensor &depth, const Tensor &conf, int64_t H, int64_t W, double near, double far,
+                                                       c10::ArrayRef<double> kt_inv)
+{
+    TORCH_CHECK(depth.dim() == 2 && conf.sizes() == depth.sizes() && conf.device() == depth.device(), "hnr::mvsnet_depth_points: depth and conf must be [h,w]");
+    TORCH_CHECK(kt_inv.size() == 9, "hnr::mvsnet_depth_points: kt_inv holds 9 values");
+    const int64_t h = depth.size(0), w = depth.size(1);
+    TORCH_CHECK(H >= 2 && W >= 2 && H <= 32768 && W <= 32768 && h >= 1 && w >= 1 && h <= H && w <= W, "hnr::mvsnet_depth_points: 2 <= H, W <= 32768, h <= H, w <= W");
+    const c10::DeviceGuard guard(depth.device());
+    float m[9];
+    for (int i = 0; i < 9; ++i) m[i] = (float)kt_inv[i];
+    Tensor cam = new_f32({H, W, 3}, depth), cf = new_f32({H, W}, depth), mask = at::empty({H, W}, depth.options().dtype(at::kByte));
+    hnr_check(hnr_mvsnet_depth_points(fptr(depth, "depth"), fptr(conf, "conf"), (int)h, (int)w, (int)H, (int)W, (float)near, (float)far, m, cam.data_ptr<float>(),
+                                      cf.data_ptr<float>(), mask.data_ptr<uint8_t>(), cur_stream(depth)),
+              "hnr_mvsnet_depth_points");
+    return {cam, cf, mask};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(hnr, m)
@@ -495,6 +585,11 @@ TORCH_LIBRARY(hnr, m)
     m.def("featnet_forward(Tensor images, Tensor packed) -> (Tensor, Tensor, Tensor)");
     m.def("point_embed(Tensor xyz, float[] w2c, float[] c2w, float[] cam_pos_cam, float[] intrinsic, Tensor image, Tensor x1, Tensor x2, Tensor x3, Tensor premlp, "
           "bool want_row) -> (Tensor, Tensor, Tensor, Tensor)");
+    m.def("mvsnet_feature(Tensor images, Tensor packed) -> Tensor");
+    m.def("mvsnet_cost_volume(Tensor feat, Tensor proj, Tensor depth_values) -> Tensor");
+    m.def("mvsnet_cost_reg(Tensor volume, Tensor packed) -> Tensor");
+    m.def("mvsnet_depth_head(Tensor logits, Tensor depth_values, bool want_prob) -> (Tensor, Tensor, Tensor)");
+    m.def("mvsnet_depth_points(Tensor depth, Tensor conf, int H, int W, float near, float far, float[] kt_inv) -> (Tensor, Tensor, Tensor)");
 }
 TORCH_LIBRARY_IMPL(hnr, CompositeExplicitAutograd, m)
 {
@@ -512,6 +607,11 @@ TORCH_LIBRARY_IMPL(hnr, CUDA, m)
     m.impl("point_view_attrs", &point_view_attrs);
     m.impl("featnet_forward", &featnet_forward);
     m.impl("point_embed", &point_embed);
+    m.impl("mvsnet_feature", &mvsnet_feature);
+    m.impl("mvsnet_cost_volume", &mvsnet_cost_volume);
+    m.impl("mvsnet_cost_reg", &mvsnet_cost_reg);
+    m.impl("mvsnet_depth_head", &mvsnet_depth_head);
+    m.impl("mvsnet_depth_points", &mvsnet_depth_points);
 }
 TORCH_LIBRARY_IMPL(hnr, Autograd, m)
 {

@@ -1,0 +1,329 @@
+"""Depth maps from the pretrained MVSNet, on the device (csrc/mvsnet.hip).
+
+The reference starts a `load_points=0`, `manual_depth_view=1` scene from the depth maps of a pretrained estimator (run/train_ft.py:104-190):
+`models/depth_estimators/mvsnet.py`, loaded by `MvsPointsModel.load_pretrained_d_est` from `--pre_d_est .../MVSNet/model_000014.ckpt`, then the tail
+of `MvsPointsModel.gen_points` (models/mvs/mvs_points_model.py:300-341).  `MVSNet` here carries that network's parameter and buffer names, so the
+checkpoint loads as it is, and runs it as HIP kernels, stage by stage: `feature_forward`, `cost_volume`, `cost_reg`, `depth_head`, `depth_points`.
+`depth_views` is the `manual_depth_view == 1` branch of `gen_points`: its result is what `cloud_init.init_cloud_from_mvs_depth` takes.
+Inference only (no backward, results carry no graph), GPU only (no CPU or torch fallback: `HnrError`).
+
+NOT the `MVSNet.*` keys of a `*_net_mvs.pth`: those belong to another network (models/mvs/models.py, `cost_reg_2`, the `manual_depth_view=-1` path),
+which `mvs_init.MvsInit` ignores and nothing here loads.
+"""
+import numpy as np
+import torch
+from torch import nn
+
+from . import _lib
+from ._lib import HnrError
+from .mvs_init import _Packed
+
+EPS = 1e-5                                                       # nn.BatchNorm's eps
+NUM_DEPTH = 192                                                  # gen_points' depth planes
+FEATURE_LAYERS = ((3, 8, 3, 1), (8, 8, 3, 1), (8, 16, 5, 2), (16, 16, 3, 1), (16, 16, 3, 1), (16, 32, 5, 2), (32, 32, 3, 1))    # (cin, cout, kernel, stride)
+REG_CONVS = ((32, 8, 1), (8, 16, 2), (16, 16, 1), (16, 32, 2), (32, 32, 1), (32, 64, 2), (64, 64, 1))                           # (cin, cout, stride)
+REG_DECONVS = (("conv7", 64, 32), ("conv9", 32, 16), ("conv11", 16, 8))
+
+
+def feature_shape(H, W):
+    """(h, w) of the feature map and of the depth map."""
+    return ((H - 1) // 2 + 1 - 1) // 2 + 1, ((W - 1) // 2 + 1 - 1) // 2 + 1
+
+
+def _gpu(t, name, shape=None):
+    t = _lib.require_gpu(t, name, torch.float32).detach()
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise HnrError("%s must be %s, got %s" % (name, tuple(shape), tuple(t.shape)))
+    return t
+
+
+def _same_device(what, *ts):
+    if any(t.device != ts[0].device for t in ts):
+        raise HnrError("%s: every tensor must be on the same device" % what)
+
+
+def feature_forward(images, packed):
+    """hnr_mvsnet_feature: images [V,3,H,W], packed [MVSNET_FEATURE_PACKED_ELEMS] -> [V,32,h,w]."""
+    L = _lib.lib()
+    images, packed = _gpu(images, "images"), _gpu(packed, "packed", (_lib.MVSNET_FEATURE_PACKED_ELEMS,))
+    if images.dim() != 4 or images.shape[1] != 3:
+        raise HnrError("feature_forward: images must be [V,3,H,W], got %s" % (tuple(images.shape),))
+    _same_device("feature_forward", images, packed)
+    V, _, H, W = (int(s) for s in images.shape)
+    ns = int(L.hnr_mvsnet_feature_scratch_elems(V, H, W)) if max(V, H, W) < 2 ** 31 else -1
+    if ns < 0:
+        raise HnrError("feature_forward: unsupported shape V=%d H=%d W=%d (1 <= V <= 64, 4 <= H, W <= 32768)" % (V, H, W))
+    out = torch.empty((V, 32) + feature_shape(H, W), dtype=torch.float32, device=images.device)
+    scratch = torch.empty((ns,), dtype=torch.float32, device=images.device)
+    with torch.cuda.device(images.device):
+        _lib.check(L.hnr_mvsnet_feature(_lib.ptr(images), V, H, W, _lib.ptr(packed), _lib.ptr(out), _lib.ptr(scratch), ns, _lib.stream()), "hnr_mvsnet_feature")
+    return out
+
+
+def cost_volume(features, proj, depth_values):
+    """hnr_mvsnet_cost_volume for one reference view: features [V,32,h,w], proj [V,3,4] (or [V,4,4]), depth_values [D] -> [32,D,h,w]."""
+    L = _lib.lib()
+    features, proj, depth_values = _gpu(features, "features"), _gpu(proj, "proj"), _gpu(depth_values, "depth_values")
+    if features.dim() != 4 or features.shape[1] != 32:
+        raise HnrError("cost_volume: features must be [V,32,h,w], got %s" % (tuple(features.shape),))
+    V, _, h, w = (int(s) for s in features.shape)
+    if proj.dim() != 3 or proj.shape[0] != V or tuple(proj.shape[1:]) not in ((3, 4), (4, 4)) or depth_values.dim() != 1:
+        raise HnrError("cost_volume: proj must be [V,3,4] or [V,4,4] and depth_values [D]")
+    _same_device("cost_volume", features, proj, depth_values)
+    proj, D = proj[:, :3].contiguous(), int(depth_values.shape[0])
+    if not (1 <= V <= 64 and 2 <= h <= 8192 and 2 <= w <= 8192 and 1 <= D <= 4096 and D * h * w <= 2 ** 26):
+        raise HnrError("cost_volume: unsupported shape V=%d D=%d h=%d w=%d (V <= 64, 2 <= h, w <= 8192, D <= 4096, D*h*w <= 2^26)" % (V, D, h, w))
+    out = torch.empty((32, D, h, w), dtype=torch.float32, device=features.device)
+    with torch.cuda.device(features.device):
+        _lib.check(L.hnr_mvsnet_cost_volume(_lib.ptr(features), V, h, w, _lib.ptr(proj), _lib.ptr(depth_values), D, _lib.ptr(out), _lib.stream()),
+                   "hnr_mvsnet_cost_volume")
+    return out
+
+
+def cost_reg(volume, packed):
+    """hnr_mvsnet_cost_reg: volume [32,D,h,w], packed [MVSNET_REG_PACKED_ELEMS] -> logits [D,h,w].  D, h and w must be multiples of 8."""
+    L = _lib.lib()
+    volume, packed = _gpu(volume, "volume"), _gpu(packed, "packed", (_lib.MVSNET_REG_PACKED_ELEMS,))
+    if volume.dim() != 4 or volume.shape[0] != 32:
+        raise HnrError("cost_reg: volume must be [32,D,h,w], got %s" % (tuple(volume.shape),))
+    _same_device("cost_reg", volume, packed)
+    D, h, w = (int(s) for s in volume.shape[1:])
+    ns = int(L.hnr_mvsnet_cost_reg_scratch_elems(D, h, w))
+    if ns < 0:
+        raise HnrError("cost_reg: unsupported shape D=%d h=%d w=%d: each must be a multiple of 8 (the skip connections do not line up otherwise; the "
+                       "reference fails there too), D <= 4096, h, w <= 8192, D*h*w <= 2^26" % (D, h, w))
+    out = torch.empty((D, h, w), dtype=torch.float32, device=volume.device)
+    scratch = torch.empty((ns,), dtype=torch.float32, device=volume.device)
+    with torch.cuda.device(volume.device):
+        _lib.check(L.hnr_mvsnet_cost_reg(_lib.ptr(volume), D, h, w, _lib.ptr(packed), _lib.ptr(out), _lib.ptr(scratch), ns, _lib.stream()), "hnr_mvsnet_cost_reg")
+    return out
+
+
+def depth_head(logits, depth_values, want_prob=False):
+    """hnr_mvsnet_depth_head: logits [D,h,w], depth_values [D] -> (depth [h,w], confidence [h,w], prob [D,h,w] or None)."""
+    L = _lib.lib()
+    logits, depth_values = _gpu(logits, "logits"), _gpu(depth_values, "depth_values")
+    if logits.dim() != 3 or tuple(depth_values.shape) != (logits.shape[0],):
+        raise HnrError("depth_head: logits must be [D,h,w] and depth_values [D]")
+    _same_device("depth_head", logits, depth_values)
+    D, h, w = (int(s) for s in logits.shape)
+    depth, conf = (torch.empty((h, w), dtype=torch.float32, device=logits.device) for _ in range(2))
+    prob = torch.empty_like(logits) if want_prob else None
+    with torch.cuda.device(logits.device):
+        _lib.check(L.hnr_mvsnet_depth_head(_lib.ptr(logits), _lib.ptr(depth_values), D, h, w, _lib.ptr(depth), _lib.ptr(conf), _lib.ptr(prob), _lib.stream()),
+                   "hnr_mvsnet_depth_head")
+    return depth, conf, prob
+
+
+def kt_inverse(intrinsic):
+    """inverse(K^T) in fp32 on the host, as mvs_utils.ndc_2_cam forms it."""
+    from .cloud_init import _host_f32
+    return torch.inverse(torch.from_numpy(_host_f32(intrinsic, (3, 3), "intrinsic")).t()).contiguous().numpy()
+
+
+def depth_points(depth, confidence, H, W, near, far, intrinsic):
+    """hnr_mvsnet_depth_points: depth, confidence [h,w] -> (cam_xyz [H,W,3], confidence [H,W], points_mask [H,W] bool)."""
+    from .cloud_init import _cf
+    L = _lib.lib()
+    depth, confidence = _gpu(depth, "depth"), _gpu(confidence, "confidence")
+    if depth.dim() != 2 or confidence.shape != depth.shape:
+        raise HnrError("depth_points: depth and confidence must be [h,w]")
+    _same_device("depth_points", depth, confidence)
+    h, w, H, W = int(depth.shape[0]), int(depth.shape[1]), int(H), int(W)
+    M = kt_inverse(intrinsic)
+    cam = torch.empty((H, W, 3), dtype=torch.float32, device=depth.device)
+    conf = torch.empty((H, W), dtype=torch.float32, device=depth.device)
+    mask = torch.empty((H, W), dtype=torch.uint8, device=depth.device)
+    with torch.cuda.device(depth.device):
+        _lib.check(L.hnr_mvsnet_depth_points(_lib.ptr(depth), _lib.ptr(confidence), h, w, H, W, float(np.float32(near)), float(np.float32(far)), _cf(M),
+                                             _lib.ptr(cam), _lib.ptr(conf), _lib.ptr(mask), _lib.stream()), "hnr_mvsnet_depth_points")
+    return cam, conf, mask.bool()
+
+
+class _Norm(nn.Module):
+    """Parameter holder with nn.BatchNorm's names; its arithmetic lives in the convolution kernels' epilogue."""
+
+    def __init__(self, ch):
+        super().__init__()
+        self.weight, self.bias = nn.Parameter(torch.ones(ch)), nn.Parameter(torch.zeros(ch))
+        self.register_buffer("running_mean", torch.zeros(ch))
+        self.register_buffer("running_var", torch.ones(ch))
+
+
+class _ConvBnReLU(nn.Module):
+    def __init__(self, conv):
+        super().__init__()
+        self.conv, self.bn = conv, _Norm(conv.out_channels)
+
+
+def _f(t):
+    return t.detach().float().cpu()
+
+
+def _normed(w, bn):
+    """[w, running_mean, mul, bias] of one layer; mul = weight * rsqrt(running_var + eps) is folded here, once."""
+    return [w, _f(bn.running_mean), _f(bn.weight) * torch.rsqrt(_f(bn.running_var) + EPS), _f(bn.bias)]
+
+
+class _FeatureNet(nn.Module):
+    def __init__(self):
+        super().__init__()
+        for i, (cin, cout, ks, stride) in enumerate(FEATURE_LAYERS):
+            setattr(self, "conv%d" % i, _ConvBnReLU(nn.Conv2d(cin, cout, ks, stride=stride, padding=ks // 2, bias=False)))
+        self.feature = nn.Conv2d(32, 32, 3, 1, 1)
+
+
+class _CostRegNet(nn.Module):
+    def __init__(self):
+        super().__init__()
+        for i, (cin, cout, stride) in enumerate(REG_CONVS):
+            setattr(self, "conv%d" % i, _ConvBnReLU(nn.Conv3d(cin, cout, 3, stride=stride, padding=1, bias=False)))
+        for name, cin, cout in REG_DECONVS:
+            setattr(self, name, nn.Sequential(nn.ConvTranspose3d(cin, cout, 3, padding=1, output_padding=1, stride=2, bias=False), _Norm(cout)))
+        self.prob = nn.Conv3d(8, 1, 3, stride=1, padding=1)
+
+
+class MVSNet(nn.Module):
+    """The reference's depth estimator `MVSNet(refine=False)` in eval mode: its parameter and buffer names (`feature.conv0.conv.weight`, ...,
+    `cost_regularization.conv7.1.running_var`, `cost_regularization.prob.bias`), its forward signature, HIP kernels inside."""
+
+    def __init__(self, refine=False):
+        super().__init__()
+        if refine:
+            raise HnrError("MVSNet: refine=True (RefineNet) is not implemented")
+        self.refine = False
+        self.feature = _FeatureNet()
+        self.cost_regularization = _CostRegNet()
+        self._packed = _Packed()
+
+    def load_pretrained(self, path_or_dict):
+        """`MvsPointsModel.load_pretrained_d_est`: the checkpoint's ['model'] with `module.` stripped.  `num_batches_tracked` entries are ignored; a
+        missing key is an HnrError."""
+        ckpt = torch.load(path_or_dict, map_location="cpu") if isinstance(path_or_dict, (str, bytes)) or hasattr(path_or_dict, "__fspath__") else path_or_dict
+        sd = ckpt["model"] if "model" in ckpt else ckpt
+        sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items() if not k.endswith("num_batches_tracked")}
+        res = self.load_state_dict(sd, strict=False)
+        if res.missing_keys:
+            raise HnrError("MVSNet.load_pretrained: the checkpoint lacks %s" % ", ".join(sorted(res.missing_keys)))
+        if res.unexpected_keys:
+            raise HnrError("MVSNet.load_pretrained: unexpected keys %s" % ", ".join(sorted(res.unexpected_keys)))
+        return self
+
+    def pack_host(self):
+        """(feature [MVSNET_FEATURE_PACKED_ELEMS], cost_reg [MVSNET_REG_PACKED_ELEMS]) fp32 on the CPU, the layouts of include/hnr.h."""
+        fn, cr = self.feature, self.cost_regularization
+        with torch.no_grad():
+            parts = []
+            for i in range(len(FEATURE_LAYERS)):
+                blk = getattr(fn, "conv%d" % i)
+                parts += _normed(_f(blk.conv.weight).permute(1, 2, 3, 0), blk.bn)
+            parts += [_f(fn.feature.weight).permute(1, 2, 3, 0), _f(fn.feature.bias)]
+            feat = torch.cat([p.contiguous().reshape(-1) for p in parts])
+            parts = []
+            for i in range(len(REG_CONVS)):
+                blk = getattr(cr, "conv%d" % i)
+                parts += _normed(_f(blk.conv.weight).permute(1, 2, 3, 4, 0), blk.bn)
+            for name, _, _ in REG_DECONVS:
+                seq = getattr(cr, name)
+                parts += _normed(_f(seq[0].weight).permute(0, 2, 3, 4, 1), seq[1])             # ConvTranspose3d keeps [cin][cout][kz][ky][kx]
+            parts += [_f(cr.prob.weight).permute(1, 2, 3, 4, 0), _f(cr.prob.bias)]
+            reg = torch.cat([p.contiguous().reshape(-1) for p in parts])
+        assert feat.numel() == _lib.MVSNET_FEATURE_PACKED_ELEMS and reg.numel() == _lib.MVSNET_REG_PACKED_ELEMS
+        return feat, reg
+
+    def packed(self):
+        tensors = list(self.parameters()) + list(self.buffers())
+        dev = self.feature.feature.weight.device
+        return self._packed.get(tensors, lambda: tuple(p.to(dev) for p in self.pack_host()))
+
+    def invalidate_packed(self):
+        """Needed only after replacing a parameter's storage with `p.data = ...` (mvs_init._Packed)."""
+        self._packed.invalidate()
+
+    def image_features(self, imgs):
+        """imgs [V,3,H,W] -> [V,32,h,w]: the feature maps of every view, computed once for all reference views."""
+        return feature_forward(imgs, self.packed()[0])
+
+    def forward(self, imgs, proj_matrices, depth_values, features=None, prob_only=False, want_prob=False):
+        """imgs [B,V,3,H,W], proj_matrices [B,V,3,4] or [B,V,4,4], depth_values [B,D] -> (depth [B,h,w], photometric_confidence [B,h,w], features,
+        prob_volume [B,D,h,w] or None).  features: a list of V maps [B,32,h,w], the reference's form (also what is returned), or one tensor [V,32,h,w]
+        shared by every batch row (`depth_views`: the rows are the same images under other projections)."""
+        if prob_only:
+            raise HnrError("MVSNet: prob_only=True (the top-k path, manual_depth_view > 1) is not implemented")
+        for t, name in ((imgs, "imgs"), (proj_matrices, "proj_matrices"), (depth_values, "depth_values")):
+            if not isinstance(t, torch.Tensor):
+                raise HnrError("MVSNet: %s must be a tensor" % name)
+        if imgs.dim() != 5 or imgs.shape[2] != 3:
+            raise HnrError("MVSNet: imgs must be [B,V,3,H,W], got %s" % (tuple(imgs.shape),))
+        B, V, _, H, W = (int(s) for s in imgs.shape)
+        if proj_matrices.dim() != 4 or tuple(proj_matrices.shape[:2]) != (B, V) or depth_values.dim() != 2 or depth_values.shape[0] != B:
+            raise HnrError("MVSNet: proj_matrices must be [B,V,3,4] or [B,V,4,4] and depth_values [B,D]")
+        h, w = feature_shape(H, W)
+        D = int(depth_values.shape[1])
+        if h % 8 or w % 8 or D % 8:
+            raise HnrError("MVSNet: the depth map's height %d and width %d and the number of depth planes %d must be multiples of 8 (images of %dx%d: the "
+                           "skip connections of the 3-D network do not line up otherwise, and the reference fails there too)" % (h, w, D, H, W))
+        imgs, proj_matrices, depth_values = _gpu(imgs, "imgs"), _gpu(proj_matrices, "proj_matrices"), _gpu(depth_values, "depth_values")
+        dev = self.feature.feature.weight.device
+        if dev != imgs.device:
+            raise HnrError("MVSNet: the module is on %s, imgs on %s" % (dev, imgs.device))
+        feat_pk, reg_pk = self.packed()
+        shared = isinstance(features, torch.Tensor)
+        if features is None:
+            per_row = self.image_features(imgs.reshape(B * V, 3, H, W)).reshape(B, V, 32, h, w)
+            features = [per_row[:, v] for v in range(V)]
+        elif shared:
+            features = _gpu(features, "features", (V, 32, h, w))
+        else:
+            per_row = torch.stack([_gpu(f, "features[v]", (B, 32, h, w)) for f in features], dim=1)
+        depths, confs, probs = [], [], []
+        for b in range(B):
+            vol = cost_volume(features if shared else per_row[b], proj_matrices[b], depth_values[b])
+            d, c, p = depth_head(cost_reg(vol, reg_pk), depth_values[b], want_prob)
+            depths.append(d); confs.append(c); probs.append(p)
+        return torch.stack(depths), torch.stack(confs), features, (torch.stack(probs) if want_prob else None)
+
+
+def check_options(opt):
+    if int(getattr(opt, "manual_depth_view", 1)) != 1:
+        raise HnrError("depth_views: manual_depth_view=%r is not implemented (only 1: the expected depth of the pretrained estimator)" % opt.manual_depth_view)
+    if float(getattr(opt, "manual_std_depth", 0.0) or 0.0) != 0.0:
+        raise HnrError("depth_views: manual_std_depth != 0 (Gaussian depth sampling) is not implemented")
+    if int(getattr(opt, "depth_occ", 0) or 0) > 0:
+        raise HnrError("depth_views: depth_occ > 0 is not implemented")
+
+
+def depth_views(batch, net, opt):
+    """The `manual_depth_view == 1` branch of `MvsPointsModel.gen_points` (models/mvs/mvs_points_model.py:300-341).  batch: the dataset item on the GPU
+    -- images [1,N,3,H,W] (mvs_images, when present, is what the estimator sees), proj_mats [1,N,N,3,4] (row i: every view seen from view i),
+    near_fars [1,N,2], near_fars_depth [1,2], intrinsics [1,N,3,3], w2cs [1,N,4,4] and optionally c2ws.  opt: init_view_num, depth_vid.
+    Returns one dict per entry of depth_vid -- cam_xyz [H,W,3], confidence [H,W], points_mask [H,W], intrinsic, w2c[, c2w], image [3,H,W], depth [h,w] --
+    the `views` of cloud_init.init_cloud_from_mvs_depth.  The feature maps are computed once, not once per entry of depth_vid."""
+    check_options(opt)
+    if not isinstance(net, MVSNet):
+        raise HnrError("depth_views: net must be an mvs_depth.MVSNet")
+    imgs = _gpu(batch["images"], "images")
+    dimgs = _gpu(batch["mvs_images"], "mvs_images") if "mvs_images" in batch else imgs
+    if dimgs.dim() != 5 or dimgs.shape[0] != 1 or dimgs.shape[2] != 3:
+        raise HnrError("depth_views: images must be [1,N,3,H,W], got %s" % (tuple(dimgs.shape),))
+    nv = int(opt.init_view_num)
+    depth_vid = [int(v) for v in opt.depth_vid]
+    if not 1 <= nv <= dimgs.shape[1] or not depth_vid or any(not 0 <= v < batch["proj_mats"].shape[1] for v in depth_vid):
+        raise HnrError("depth_views: init_view_num=%d / depth_vid=%r do not fit %d views" % (nv, depth_vid, dimgs.shape[1]))
+    H, W = int(dimgs.shape[-2]), int(dimgs.shape[-1])
+    nfd = _gpu(batch["near_fars_depth"], "near_fars_depth")[0]
+    interval = (nfd[1] - nfd[0]) / 192.
+    depth_values = (nfd[0] + torch.arange(0, NUM_DEPTH, device=dimgs.device, dtype=torch.float32) * interval)[None, :]
+    proj = _gpu(batch["proj_mats"], "proj_mats")[0, torch.as_tensor(depth_vid, dtype=torch.long, device=dimgs.device)][:, :nv]
+    feats = net.image_features(dimgs[0, :nv])
+    depth, conf, _, _ = net(dimgs[:, :nv].expand(len(depth_vid), -1, -1, -1, -1), proj, depth_values.expand(len(depth_vid), -1), features=feats)
+    near_fars = batch["near_fars"].detach().float().cpu().numpy()[0]
+    views = []
+    for i, vid in enumerate(depth_vid):
+        K = batch["intrinsics"][0, vid]
+        cam, cf, mask = depth_points(depth[i], conf[i], H, W, near_fars[vid, 0], near_fars[vid, 1], K)
+        v = dict(cam_xyz=cam, confidence=cf, points_mask=mask, intrinsic=K, w2c=batch["w2cs"][0, vid], image=imgs[0, vid], depth=depth[i])
+        if "c2ws" in batch:
+            v["c2w"] = batch["c2ws"][0, vid]
+        views.append(v)
+    return views

@@ -2,7 +2,8 @@
 
 SURVEY 8b asks for both op layers: the C ABI (include/hnr.h, bound by ctypes in _lib.py -- needs no torch headers) and registered torch ops.  The
 ops are the same library calls with schemas: `hnr::grid_build`, `hnr::grid_free`, `hnr::march_query`, `hnr::nearest_view`, `hnr::point_view_attrs`
-(the cloud initialisation of cloud_init.py), `hnr::featnet_forward`, `hnr::point_embed` (the init checkpoint's networks, mvs_init.py), `hnr::render_forward`
+(the cloud initialisation of cloud_init.py), `hnr::featnet_forward`, `hnr::point_embed` (the init checkpoint's networks, mvs_init.py), `hnr::mvsnet_feature`,
+`hnr::mvsnet_cost_volume`, `hnr::mvsnet_cost_reg`, `hnr::mvsnet_depth_head`, `hnr::mvsnet_depth_points` (the depth estimator, mvs_depth.py), `hnr::render_forward`
 (NeuralPointsRayMarching.forward + fill_invalid in eval mode, /root/reference/models/neural_points_volumetric_model.py:257-391, :87-126) and
 `hnr::render_train` (the same in train mode with the backward pass registered as its autograd formula; the reference leaves that to torch autograd,
 models/mvs_points_volumetric_model.py:111-131).  This module loads the extension and builds the ops' argument lists from the host-side objects
@@ -115,6 +116,30 @@ def _register_fakes():
     def _(xyz, w2c, c2w, cam_pos_cam, intrinsic, image, x1, x2, x3, premlp, want_row):
         n, e = xyz.shape[0], xyz.new_empty
         return (e((n, 32), dtype=f32), e((n, 3), dtype=f32), e((n, 3), dtype=f32), e((n, 63 if want_row else 0), dtype=f32))
+
+    @torch.library.register_fake("hnr::mvsnet_feature")
+    def _(images, packed):
+        V, _, H, W = images.shape
+        return images.new_empty((V, 32, ((H - 1) // 2 + 1 - 1) // 2 + 1, ((W - 1) // 2 + 1 - 1) // 2 + 1), dtype=f32)
+
+    @torch.library.register_fake("hnr::mvsnet_cost_volume")
+    def _(feat, proj, depth_values):
+        return feat.new_empty((32, depth_values.shape[0], feat.shape[2], feat.shape[3]), dtype=f32)
+
+    @torch.library.register_fake("hnr::mvsnet_cost_reg")
+    def _(volume, packed):
+        return volume.new_empty(tuple(volume.shape[1:]), dtype=f32)
+
+    @torch.library.register_fake("hnr::mvsnet_depth_head")
+    def _(logits, depth_values, want_prob):
+        D, h, w = logits.shape
+        e = logits.new_empty
+        return (e((h, w), dtype=f32), e((h, w), dtype=f32), e((D, h, w) if want_prob else (0,), dtype=f32))
+
+    @torch.library.register_fake("hnr::mvsnet_depth_points")
+    def _(depth, conf, H, W, near, far, kt_inv):
+        e = depth.new_empty
+        return (e((H, W, 3), dtype=f32), e((H, W), dtype=f32), e((H, W), dtype=torch.uint8))
 
 
 def load():
@@ -231,3 +256,36 @@ def point_embed(xyz, w2c, c2w, cam_pos_cam, intrinsic, image, x1, x2, x3, premlp
     return ops.point_embed(g(xyz, "xyz", torch.float32).reshape(-1, 3), flat(w2c, 16), flat(c2w, 16), flat(cam_pos_cam, 3), flat(intrinsic, 9),
                            g(image, "image", torch.float32), g(x1, "x1", torch.float32), g(x2, "x2", torch.float32), g(x3, "x3", torch.float32),
                            g(premlp, "premlp", torch.float32), bool(want_row))
+
+
+def mvsnet_feature(images, packed):
+    """mvs_depth.feature_forward through torch.ops.hnr.mvsnet_feature: images [V,3,H,W], packed = MVSNet.packed()[0] -> [V,32,h,w]."""
+    g = _lib.require_gpu
+    return load().mvsnet_feature(g(images, "images", torch.float32), g(packed, "packed", torch.float32))
+
+
+def mvsnet_cost_volume(features, proj, depth_values):
+    """mvs_depth.cost_volume through torch.ops.hnr.mvsnet_cost_volume: features [V,32,h,w], proj [V,3,4] or [V,4,4], depth_values [D] -> [32,D,h,w]."""
+    g = _lib.require_gpu
+    return load().mvsnet_cost_volume(g(features, "features", torch.float32), g(proj, "proj", torch.float32)[:, :3].contiguous(),
+                                     g(depth_values, "depth_values", torch.float32))
+
+
+def mvsnet_cost_reg(volume, packed):
+    """mvs_depth.cost_reg through torch.ops.hnr.mvsnet_cost_reg: volume [32,D,h,w], packed = MVSNet.packed()[1] -> logits [D,h,w]."""
+    g = _lib.require_gpu
+    return load().mvsnet_cost_reg(g(volume, "volume", torch.float32), g(packed, "packed", torch.float32))
+
+
+def mvsnet_depth_head(logits, depth_values, want_prob=False):
+    """mvs_depth.depth_head through torch.ops.hnr.mvsnet_depth_head: (depth [h,w], confidence [h,w], prob [D,h,w] or [0])."""
+    g = _lib.require_gpu
+    return load().mvsnet_depth_head(g(logits, "logits", torch.float32), g(depth_values, "depth_values", torch.float32), bool(want_prob))
+
+
+def mvsnet_depth_points(depth, confidence, H, W, near, far, intrinsic):
+    """mvs_depth.depth_points through torch.ops.hnr.mvsnet_depth_points: (cam_xyz [H,W,3], confidence [H,W], points_mask [H,W] uint8)."""
+    from .mvs_depth import kt_inverse
+    g = _lib.require_gpu
+    return load().mvsnet_depth_points(g(depth, "depth", torch.float32), g(confidence, "confidence", torch.float32), int(H), int(W), float(np.float32(near)),
+                                      float(np.float32(far)), [float(v) for v in kt_inverse(intrinsic).reshape(9)])

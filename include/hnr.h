@@ -24,7 +24,7 @@
  *              hnr_image_features*, hnr_render_forward* (+ workspace sizing), hnr_render_train_forward / _backward / _backward_depth (+ sizing),
  *              hnr_shipped_loss*, hnr_composite, hnr_ray_depth, hnr_ray_march, hnr_voxel_downsample*, hnr_probe_select, hnr_blur_*,
  *              hnr_frame_metrics* (and the HNR_FM_* row layout), hnr_depth_fuse*, hnr_range_crop*, hnr_nearest_view, hnr_point_view_attrs,
- *              hnr_featnet_*, hnr_point_embed*, hnr_geo_consistency, hnr_geo_filter_select*,
+ *              hnr_featnet_*, hnr_point_embed*, hnr_geo_consistency, hnr_geo_filter_select*, hnr_mvsnet_*,
  *              hnr_frame_batch*, hnr_frame_item, hnr_ray_miss_rank.
  *   STAGE   -- everything else (hnr_chain_*, hnr_mlp3_*, hnr_merge*, hnr_mixup_stage, hnr_proj_*, hnr_h2*, hnr_linear_*, hnr_gather_*, hnr_ksum*,
  *              hnr_segment_*, hnr_absmax, hnr_div_probe, hnr_image_features_bwd_bbox, ...): the individual stages the two single-call entries are built from.  They are exported so
@@ -1049,6 +1049,64 @@ int hnr_geo_filter_select(const float *d_cam_xyz, const float *d_conf, const uin
                           int V, int H, int W, const float *d_Einv, float conf_thresh, int geo_cnsst_num, const float *ranges, const float *conf_table,
                           float *d_world, float *d_cam, float *d_conf_out, int32_t *d_view, int64_t capacity, int64_t *d_view_counts, int64_t *d_total,
                           int32_t *d_status, void *d_scratch, int64_t scratch_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Depth maps from the pretrained MVSNet: the first stage of the `load_points=0`, `manual_depth_view=1` start of a scene (csrc/mvsnet.hip).  Replaces
+ * models/depth_estimators/mvsnet.py (`MVSNet(refine=False)` in eval mode, loaded by `MvsPointsModel.load_pretrained_d_est`) and the tail of
+ * `MvsPointsModel.gen_points` (models/mvs/mvs_points_model.py:300-341).  Inference only.  All arithmetic is fp32, every intended fused multiply-add is
+ * an explicit one, every sum has a fixed order: two runs give the same bits.  Stream-ordered, nothing is allocated, nothing is read back, no atomics.
+ * A batch norm is y = (x - running_mean) * mul + bias with mul = weight * rsqrt(running_var + 1e-5), folded by whoever packs (plain BatchNorm: no
+ * |weight|, eps on the variance only).  HNR_ERR_BADARG, before any launch, for a NULL pointer, a shape outside the limits given or a short scratch.
+ *
+ * hnr_mvsnet_feature -- `FeatureNet`, mvsnet.py:7-27: conv + BatchNorm2d + ReLU 3->8, 8->8 (3x3), 8->16 (5x5, stride 2), 16->16, 16->16 (3x3), 16->32
+ *   (5x5, stride 2), 32->32 (3x3), pad = kernel / 2, no bias; then `feature`: 3x3, 32->32, with bias, no norm, no activation.
+ *   d_images [V,3,H,W] -> d_feat [V,32,h,w], h = ((H-1)/2+1-1)/2+1 (integer division), likewise w.  Direct convolution, one chain of fmaf per output
+ *   over (input channel, ky, kx).  d_packed [HNR_MVSNET_FEATURE_PACKED_ELEMS]: per ConvBnReLU, in network order, w [cin][ky][kx][cout], running_mean
+ *   [cout], mul [cout], bias [cout]; then `feature`: w [cin][ky][kx][cout], bias [cout].  d_scratch: hnr_mvsnet_feature_scratch_elems(V, H, W) floats
+ *   (negative: bad shape).  1 <= V <= 64, 4 <= H, W <= 32768.
+ *
+ * hnr_mvsnet_cost_volume -- mvsnet.py:109-122 with `homo_warping` (module.py:36-70), one reference view: d_volume [32,D,h,w] =
+ *   sum_v f_v^2 / V - (sum_v f_v / V)^2, views ascending, f_v the bilinear sample of d_feat[v] [32,h,w] at the projection of (x, y, depth d_k):
+ *     P = d_proj[v] [3,4] (device, row-major): r = (P[c][0]*x + P[c][1]*y) + P[c][2];  q[c] = r[c]*d_k + P[c][3];  px = q0/q2, py = q1/q2;
+ *     gx = px / ((w-1)/2) - 1, gy = py / ((h-1)/2) - 1   (the align_corners=True normalisation) ...
+ *     ix = ((gx+1)*w - 1)/2, iy = ((gy+1)*h - 1)/2       (... undone as grid_sample's default align_corners=False does: the reference's mismatch,
+ *                                                         kept; it moves every sample, the identity view's included)
+ *     x0 = floor(ix), y0 = floor(iy); f = (((x0+1-ix)*(y0+1-iy))*t00 + ((ix-x0)*(y0+1-iy))*t01 + ((x0+1-ix)*(iy-y0))*t10) + ((ix-x0)*(iy-y0))*t11,
+ *     a tap outside the map is zero; a coordinate that is not finite or not inside (-1, w) x (-1, h) reads nothing and contributes zero.
+ *   d_depth_values [D].  1 <= V <= 64, 2 <= h, w <= 8192, 1 <= D <= 4096, D*h*w <= 2^26.
+ *
+ * hnr_mvsnet_cost_reg -- `CostRegNet`, mvsnet.py:30-70: d_volume [32,D,h,w] -> d_logits [D,h,w].  ConvBnReLU3D 32->8, 8->16 (stride 2), 16->16, 16->32
+ *   (stride 2), 32->32, 32->64 (stride 2), 64->64 (3x3x3, pad 1, no bias); ConvTranspose3d (3x3x3, stride 2, pad 1, output_padding 1, no bias) +
+ *   BatchNorm3d + ReLU 64->32, 32->16, 16->8, each followed by `skip + y` (the skip is added after the activation); `prob`: 3x3x3, 8->1, with bias.
+ *   Direct convolution; a transposed convolution is a gather over the output voxel's parity class (1, 2, 4 or 8 taps per input channel); one chain
+ *   of fmaf per output over (input channel, kz, ky, kx).  D, h and w must be multiples of 8 (the skips do not line up otherwise: HNR_ERR_BADARG).
+ *   d_packed [HNR_MVSNET_REG_PACKED_ELEMS]: the ten normed layers in network order (conv0 .. conv6, conv7, conv9, conv11), each w [cin][kz][ky][kx][cout],
+ *   running_mean [cout], mul [cout], bias [cout]; then `prob`: w [cin][kz][ky][kx], bias [1].  d_scratch: hnr_mvsnet_cost_reg_scratch_elems(D, h, w)
+ *   floats (negative: bad shape).  Limits as for the cost volume.
+ *
+ * hnr_mvsnet_depth_head -- mvsnet.py:126-136, one thread per pixel: m = max_k logit_k, e_k = exp(logit_k - m), S = sum_k e_k (k ascending);
+ *   d_depth [h,w] = (sum_k e_k d_k) / S;  i = (sum_k e_k k) / S, idx = (int) i (truncation);  d_conf [h,w] = sum_{k = idx-1 .. idx+2, 0 <= k < D} e_k / S
+ *   (the reference's 4 * avg_pool3d over the pad (1, 2), gathered at idx);  d_prob [D,h,w] (optional, NULL: not written) = e_k / S.
+ *
+ * hnr_mvsnet_depth_points -- mvs_points_model.py:329-337 with manual_std_depth = 0 (`gau_single_sampler`, `depth2point`, mvs_utils.ndc_2_cam):
+ *   d = d_depth[sy][sx], sy = min((int)floor(y * ((float)h / H)), h-1), sx likewise (torch's `nearest`);  d_mask [H,W] = near <= d && d <= far;
+ *   z = min(max((d - near) / (far - near), 0), 1);  cz = z * (far - near) + near;  cx = ((x / (W-1)) * (W-1)) * cz, cy likewise;
+ *   d_cam_xyz [H,W,3][j] = (cx*M[0][j] + cy*M[1][j]) + cz*M[2][j], M = Kt_inv = inverse(K^T) [3,3], host floats (the caller inverts, in fp32);
+ *   d_conf_out [H,W] = d_conf[sy][sx].  2 <= H, W <= 32768, 1 <= h <= H, 1 <= w <= W. */
+#define HNR_MVSNET_FEATURE_PACKED_ELEMS 40248
+#define HNR_MVSNET_REG_PACKED_ELEMS 298297
+int64_t hnr_mvsnet_feature_scratch_elems(int V, int H, int W);
+int hnr_mvsnet_feature(const float *d_images, int V, int H, int W, const float *d_packed, float *d_feat, float *d_scratch, int64_t scratch_elems,
+                       void *stream);
+int hnr_mvsnet_cost_volume(const float *d_feat, int V, int h, int w, const float *d_proj, const float *d_depth_values, int D, float *d_volume,
+                           void *stream);
+int64_t hnr_mvsnet_cost_reg_scratch_elems(int D, int h, int w);
+int hnr_mvsnet_cost_reg(const float *d_volume, int D, int h, int w, const float *d_packed, float *d_logits, float *d_scratch, int64_t scratch_elems,
+                        void *stream);
+int hnr_mvsnet_depth_head(const float *d_logits, const float *d_depth_values, int D, int h, int w, float *d_depth, float *d_conf, float *d_prob,
+                          void *stream);
+int hnr_mvsnet_depth_points(const float *d_depth, const float *d_conf, int h, int w, int H, int W, float near, float far, const float *Kt_inv,
+                            float *d_cam_xyz, float *d_conf_out, uint8_t *d_mask, void *stream);
 
 #ifdef __cplusplus
 }
