@@ -18,4 +18,7 @@ def __getattr__(name):
     if name in ("MVSNet", "depth_views"):
         from . import mvs_depth
         return getattr(mvs_depth, name)
+    if name in ("AlphaMasks", "alpha_masking", "visual_hull_select", "point_occlusion", "init_cloud_from_mvs_depth"):
+        from . import cloud_init
+        return getattr(cloud_init, name)
     raise AttributeError(name)

@@ -194,11 +194,20 @@ SIGNATURES = {
     "hnr_range_crop": (_I, [_P, _P, ctypes.c_int64, ctypes.POINTER(_F), _P, _P, _P, ctypes.c_int64, _P]),
     "hnr_nearest_view": (_I, [_P, ctypes.c_int64, _P, _P, _I, _P, _P]),
     "hnr_point_view_attrs": (_I, [_P, ctypes.c_int64] + [ctypes.POINTER(_F)] * 4 + [_I, _I, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "hnr_point_view_attrs_vis": (_I, [_P, ctypes.c_int64] + [ctypes.POINTER(_F)] * 4 + [_I, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
     # point embeddings from the MVS init checkpoint (csrc/featnet.hip)
     "hnr_featnet_scratch_elems": (ctypes.c_int64, [_I, _I, _I]),
     "hnr_featnet_forward": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.c_int64, _P]),
     "hnr_point_embed": (_I, [_P, ctypes.c_int64] + [ctypes.POINTER(_F)] * 4 + [_I, _I] + [_P] * 10),
     "hnr_point_embed_conf": (_I, [_P, ctypes.c_int64] + [ctypes.POINTER(_F)] * 4 + [_I, _I] + [_P] * 11),
+    "hnr_point_embed_vis": (_I, [_P, ctypes.c_int64] + [ctypes.POINTER(_F)] * 4 + [_I, _I] + [_P] * 12),
+    # visual-hull masking and the occlusion test of the synthetic scenes (csrc/hull.hip)
+    "hnr_alpha_pack": (_I, [_P, _I, _I, _I, _P, _P]),
+    "hnr_visual_hull_select_scratch_bytes": (ctypes.c_int64, [ctypes.c_int64]),
+    "hnr_visual_hull_select": (_I, [_P, _P, _P, ctypes.c_int64, _P, _P, _I, _I, _I, ctypes.POINTER(_F), _I, _P, _P, _P, _P, ctypes.c_int64, _P, _P, _P,
+                                    ctypes.c_int64, _P]),
+    "hnr_point_occlusion_scratch_bytes": (ctypes.c_int64, [_I, _I]),
+    "hnr_point_occlusion": (_I, [_P, ctypes.c_int64, ctypes.POINTER(_F), ctypes.POINTER(_F), _I, _I, _F, _P, _P, ctypes.c_int64, _P]),
     # geometric-consistency filter of MVS depth maps (csrc/geo_filter.hip)
     "hnr_geo_consistency": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "hnr_geo_filter_select_scratch_bytes": (ctypes.c_int64, [_I, _I, _I]),

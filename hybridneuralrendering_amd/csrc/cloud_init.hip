@@ -216,12 +216,14 @@ __global__ void __launch_bounds__(256) nearest_view_kernel(const float *__restri
 }
 
 __global__ void __launch_bounds__(256) view_attrs_kernel(const float *__restrict__ xyz, long long n, ViewCam vc, int H, int W, const float *__restrict__ feat, int C,
-                                                         int Hl, int Wl, float *__restrict__ out_feat, float *__restrict__ out_dir, uint8_t *__restrict__ out_mask)
+                                                         int Hl, int Wl, float *__restrict__ out_feat, float *__restrict__ out_dir, uint8_t *__restrict__ out_mask,
+                                                         const uint8_t *__restrict__ visible)
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     float c[3], gx, gy;
-    const bool mask = view_project(vc, xyz[3 * i + 0], xyz[3 * i + 1], xyz[3 * i + 2], H, W, c, gx, gy);
+    bool mask = view_project(vc, xyz[3 * i + 0], xyz[3 * i + 1], xyz[3 * i + 2], H, W, c, gx, gy);
+    if (visible) mask = mask && visible[i] != 0;                     // an occluded point is a point outside the frame (hnr_point_occlusion)
     if (out_mask) out_mask[i] = mask ? 1 : 0;
     if (out_dir) {
         float d[3];
@@ -370,6 +372,13 @@ extern "C" int hnr_nearest_view(const float *d_xyz, int64_t N, const float *d_ca
 extern "C" int hnr_point_view_attrs(const float *d_xyz, int64_t n, const float *w2c, const float *c2w, const float *cam_pos_cam, const float *K, int H, int W,
                                     const float *d_feat, int C, int Hl, int Wl, float *d_out_feat, float *d_out_dir, uint8_t *d_out_mask, void *stream)
 {
+    return hnr_point_view_attrs_vis(d_xyz, n, w2c, c2w, cam_pos_cam, K, H, W, d_feat, C, Hl, Wl, nullptr, d_out_feat, d_out_dir, d_out_mask, stream);
+}
+
+extern "C" int hnr_point_view_attrs_vis(const float *d_xyz, int64_t n, const float *w2c, const float *c2w, const float *cam_pos_cam, const float *K, int H, int W,
+                                        const float *d_feat, int C, int Hl, int Wl, const uint8_t *d_visible, float *d_out_feat, float *d_out_dir,
+                                        uint8_t *d_out_mask, void *stream)
+{
     if (!d_xyz || !w2c || !c2w || !cam_pos_cam || !K || (!d_out_feat && !d_out_dir && !d_out_mask) || (d_out_feat && !d_feat)) {
         set_error("hnr_point_view_attrs: NULL argument"); return HNR_ERR_BADARG;
     }
@@ -378,7 +387,7 @@ extern "C" int hnr_point_view_attrs(const float *d_xyz, int64_t n, const float *
     }
     ViewCam vc;
     view_cam_fill(vc, w2c, c2w, cam_pos_cam, K);
-    view_attrs_kernel<<<cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(d_xyz, (long long)n, vc, H, W, d_feat, C, Hl, Wl, d_out_feat, d_out_dir, d_out_mask);
+    view_attrs_kernel<<<cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(d_xyz, (long long)n, vc, H, W, d_feat, C, Hl, Wl, d_out_feat, d_out_dir, d_out_mask, d_visible);
     HNR_LAUNCH_CHECK();
     return HNR_OK;
 }

@@ -144,11 +144,13 @@ __device__ __forceinline__ void pe_level(bool mask, const ViewTaps &t, const flo
 
 // one point per thread.  The row [x1 8 | x2 16 | x3 32 | colour 3 | dir 3 | conf] is consumed a few inputs at a time, in its own order, so only the
 // 32 sums of premlp's first layer stay in registers; premlp's weights sit in LDS and every lane reads the same word at a time (broadcast).  A point
-// outside the frame has zero features and colour: its row still goes through premlp.  conf NULL: the row's last column is 1.
+// outside the frame has zero features and colour: its row still goes through premlp.  conf NULL: the row's last column is 1.  visible (optional):
+// where it is 0 the point is treated as outside the frame.
 __global__ void __launch_bounds__(256) point_embed_kernel(const float *__restrict__ xyz, long long n, ViewCam vc, int H, int W, const float *__restrict__ img,
                                                           const float *__restrict__ x1, const float *__restrict__ x2, const float *__restrict__ x3, int H2, int W2,
                                                           int H4, int W4, const float *__restrict__ premlp, float *__restrict__ emb, float *__restrict__ color,
-                                                          float *__restrict__ dir, float *__restrict__ row_out, const float *__restrict__ conf)
+                                                          float *__restrict__ dir, float *__restrict__ row_out, const float *__restrict__ conf,
+                                                          const uint8_t *__restrict__ visible)
 {
     __shared__ float wsm[HNR_PREMLP_PACKED_ELEMS];
     for (int e = threadIdx.x; e < HNR_PREMLP_PACKED_ELEMS; e += 256) wsm[e] = premlp[e];
@@ -156,7 +158,8 @@ __global__ void __launch_bounds__(256) point_embed_kernel(const float *__restric
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     float c[3], gx, gy, tail[7], h[PE_OUT], o[PE_OUT];
-    const bool mask = view_project(vc, xyz[3 * i + 0], xyz[3 * i + 1], xyz[3 * i + 2], H, W, c, gx, gy);
+    bool mask = view_project(vc, xyz[3 * i + 0], xyz[3 * i + 1], xyz[3 * i + 2], H, W, c, gx, gy);
+    if (visible) mask = mask && visible[i] != 0;                        // an occluded point is a point outside the frame (hnr_point_occlusion)
     view_dir(vc, c, tail + 3);
     float *row = row_out ? row_out + (size_t)i * PE_IN : nullptr;
 #pragma unroll
@@ -231,6 +234,13 @@ extern "C" int hnr_point_embed_conf(const float *d_xyz, int64_t n, const float *
                                     const float *d_image, const float *d_x1, const float *d_x2, const float *d_x3, const float *d_premlp, const float *d_conf,
                                     float *d_emb, float *d_color, float *d_dir, float *d_row, void *stream)
 {
+    return hnr_point_embed_vis(d_xyz, n, w2c, c2w, cam_pos_cam, K, H, W, d_image, d_x1, d_x2, d_x3, d_premlp, d_conf, nullptr, d_emb, d_color, d_dir, d_row, stream);
+}
+
+extern "C" int hnr_point_embed_vis(const float *d_xyz, int64_t n, const float *w2c, const float *c2w, const float *cam_pos_cam, const float *K, int H, int W,
+                                   const float *d_image, const float *d_x1, const float *d_x2, const float *d_x3, const float *d_premlp, const float *d_conf,
+                                   const uint8_t *d_visible, float *d_emb, float *d_color, float *d_dir, float *d_row, void *stream)
+{
     if (!d_xyz || !w2c || !c2w || !cam_pos_cam || !K || !d_image || !d_x1 || !d_x2 || !d_x3 || !d_premlp || !d_emb || !d_color || !d_dir) {
         set_error("hnr_point_embed: NULL argument"); return HNR_ERR_BADARG;
     }
@@ -241,7 +251,7 @@ extern "C" int hnr_point_embed_conf(const float *d_xyz, int64_t n, const float *
     view_cam_fill(vc, w2c, c2w, cam_pos_cam, K);
     const int H2 = (H - 1) / 2 + 1, W2 = (W - 1) / 2 + 1, H4 = (H2 - 1) / 2 + 1, W4 = (W2 - 1) / 2 + 1;
     point_embed_kernel<<<cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(d_xyz, (long long)n, vc, H, W, d_image, d_x1, d_x2, d_x3, H2, W2, H4, W4, d_premlp, d_emb,
-                                                                      d_color, d_dir, d_row, d_conf);
+                                                                      d_color, d_dir, d_row, d_conf, d_visible);
     HNR_LAUNCH_CHECK();
     return HNR_OK;
 }

@@ -13,6 +13,8 @@
 //   hnr::point_view_attrs                hnr_point_view_attrs                    (homo_warp_nongrid + extract_from_2d_grid + the `dir` branch of query_embedding)
 //   hnr::featnet_forward                 hnr_featnet_forward                     (FeatureNet(intermediate=True) in eval mode, models/mvs/models.py:717-764)
 //   hnr::point_embed                     hnr_point_embed                         (query_embedding with premlp, models/mvs/mvs_points_model.py:225-259)
+//   hnr::alpha_pack / visual_hull_select / point_occlusion   hnr_alpha_pack, hnr_visual_hull_select, hnr_point_occlusion (mvs_utils.alpha_masking +
+//                                        masking, homo_warp_nongrid_occ); point_view_attrs / point_embed take the flags as an optional `visible`
 //   hnr::mvsnet_feature / _cost_volume / _cost_reg / _depth_head / _depth_points   hnr_mvsnet_*   (models/depth_estimators/mvsnet.py in eval mode and
 //                                        the tail of MvsPointsModel.gen_points, models/mvs/mvs_points_model.py:300-341)
 // Nothing is computed here: every op validates its tensors, fills the C structs, takes the current HIP stream and calls the library.  Errors
@@ -385,6 +387,82 @@ std::vector<Tensor> render_train_nograd(int64_t grid, const OptList &in_l, c10::
     return outs;
 }
 
+// the optional occlusion flags of point_view_attrs / point_embed: [n] u8 on xyz's device, or NULL
+const uint8_t *vis_ptr(const OptT &visible, const Tensor &xyz, const char *op)
+{
+    if (!visible.has_value() || !visible->defined()) return nullptr;
+    TORCH_CHECK(visible->dim() == 1 && visible->size(0) == xyz.size(0) && visible->device() == xyz.device(), op, ": visible must be [n] uint8 on xyz's device");
+    return cptr<uint8_t>(*visible, "visible", at::kByte);
+}
+
+// ---- hnr::alpha_pack(Tensor alphas [M,H,W]) -> Tensor [M,H,(W+31)/32] i32: the bit patterns of hnr_alpha_pack's uint32 words
+Tensor alpha_pack(const Tensor &alphas)
+{
+    TORCH_CHECK(alphas.dim() == 3 && alphas.numel() > 0, "hnr::alpha_pack: alphas must be [M,H,W]");
+    TORCH_CHECK(alphas.size(0) <= 65535 && alphas.size(1) <= 32768 && alphas.size(2) <= 32768, "hnr::alpha_pack: M <= 65535, H, W <= 32768");
+    const c10::DeviceGuard guard(alphas.device());
+    const int64_t M = alphas.size(0), H = alphas.size(1), W = alphas.size(2);
+    Tensor bits = at::empty({M, H, (W + 31) / 32}, alphas.options().dtype(at::kInt));
+    hnr_check(hnr_alpha_pack(fptr(alphas, "alphas"), (int)M, (int)H, (int)W, (uint32_t *)bits.data_ptr<int32_t>(), cur_stream(alphas)), "hnr_alpha_pack");
+    return bits;
+}
+
+// ---- hnr::visual_hull_select(Tensor xyz [n,3], Tensor? conf [n], Tensor? view [n] i32, Tensor bits [M,H,Wp] i32, Tensor cams [M,21], int W,
+//      float[] near_far (near - 1, far; empty: none), bool range_mask, int capacity) -> (mask [n] u8, xyz [capacity,3], conf [capacity] or [0], view [capacity] or [0],
+//      count [1] i64, status [1] i32)
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> visual_hull_select(const Tensor &xyz, const OptT &conf, const OptT &view, const Tensor &bits,
+                                                                              const Tensor &cams, int64_t W, c10::ArrayRef<double> near_far,
+                                                                              bool range_mask, int64_t capacity)
+{
+    TORCH_CHECK(xyz.dim() == 2 && xyz.size(1) == 3 && xyz.size(0) > 0, "hnr::visual_hull_select: xyz must be [n,3], n > 0");
+    TORCH_CHECK(bits.dim() == 3 && W >= 1 && W <= 32768 && bits.size(2) == (W + 31) / 32 && bits.size(0) <= 65535 && bits.size(1) <= 32768,
+                "hnr::visual_hull_select: bits must be [M,H,(W+31)/32]");
+    TORCH_CHECK(cams.dim() == 2 && cams.size(0) == bits.size(0) && cams.size(1) == 21, "hnr::visual_hull_select: cams must be [M,21]");
+    TORCH_CHECK(bits.device() == xyz.device() && cams.device() == xyz.device(), "hnr::visual_hull_select: every tensor must be on xyz's device");
+    TORCH_CHECK(near_far.size() == 0 || near_far.size() == 2, "hnr::visual_hull_select: near_far holds 2 values (near - 1, far), or none");
+    TORCH_CHECK(capacity >= 0, "hnr::visual_hull_select: capacity must not be negative");
+    const int64_t n = xyz.size(0);
+    const bool hc = conf.has_value() && conf->defined(), hv = view.has_value() && view->defined();
+    if (hc) TORCH_CHECK(conf->dim() == 1 && conf->size(0) == n && conf->device() == xyz.device(), "hnr::visual_hull_select: conf must be [n] on xyz's device");
+    if (hv) TORCH_CHECK(view->dim() == 1 && view->size(0) == n && view->device() == xyz.device(), "hnr::visual_hull_select: view must be [n] on xyz's device");
+    const c10::DeviceGuard guard(xyz.device());
+    const int64_t nbytes = hnr_visual_hull_select_scratch_bytes(n);
+    TORCH_CHECK(nbytes >= 0, "hnr::visual_hull_select: n must be at most 2^30");
+    const int64_t rows = capacity > 0 ? capacity : 1;
+    Tensor mask = at::empty({n}, xyz.options().dtype(at::kByte)), oxyz = new_f32({rows, 3}, xyz), oconf = new_f32({hc ? rows : 0}, xyz),
+           oview = at::empty({hv ? rows : 0}, xyz.options().dtype(at::kInt)), count = at::zeros({1}, xyz.options().dtype(at::kLong)),
+           status = at::zeros({1}, xyz.options().dtype(at::kInt)), scratch = at::empty({nbytes}, xyz.options().dtype(at::kByte));
+    float nf[2] = {0.f, 0.f};
+    if (near_far.size() == 2) { nf[0] = (float)near_far[0]; nf[1] = (float)near_far[1]; }
+    hnr_check(hnr_visual_hull_select(fptr(xyz, "xyz"), hc ? fptr(*conf, "conf") : nullptr, hv ? cptr<int32_t>(*view, "view", at::kInt) : nullptr, n,
+                                     cptr<uint32_t>(bits, "bits", at::kInt), fptr(cams, "cams"), (int)bits.size(0), (int)bits.size(1), (int)W,
+                                     near_far.size() == 2 ? nf : nullptr, range_mask ? 1 : 0, mask.data_ptr<uint8_t>(), oxyz.data_ptr<float>(),
+                                     hc ? oconf.data_ptr<float>() : nullptr, hv ? oview.data_ptr<int32_t>() : nullptr, capacity, count.data_ptr<int64_t>(),
+                                     status.data_ptr<int32_t>(), scratch.data_ptr(), nbytes, cur_stream(xyz)),
+              "hnr_visual_hull_select");
+    return {mask, oxyz, oconf, oview, count, status};
+}
+
+// ---- hnr::point_occlusion(Tensor xyz [n,3], float[] w2c, float[] intrinsic, int H, int W, float tolerate) -> Tensor [n] u8
+Tensor point_occlusion(const Tensor &xyz, c10::ArrayRef<double> w2c, c10::ArrayRef<double> intrinsic, int64_t H, int64_t W, double tolerate)
+{
+    TORCH_CHECK(xyz.dim() == 2 && xyz.size(1) == 3, "hnr::point_occlusion: xyz must be [n,3]");
+    TORCH_CHECK(w2c.size() == 16 && intrinsic.size() == 9, "hnr::point_occlusion: w2c holds 16 values, intrinsic 9");
+    TORCH_CHECK(H >= 2 && W >= 2 && H <= 32768 && W <= 32768, "hnr::point_occlusion: 2 <= H, W <= 32768");
+    const c10::DeviceGuard guard(xyz.device());
+    float m[16 + 9];
+    for (int i = 0; i < 16; ++i) m[i] = (float)w2c[i];
+    for (int i = 0; i < 9; ++i) m[16 + i] = (float)intrinsic[i];
+    const int64_t n = xyz.size(0), nbytes = hnr_point_occlusion_scratch_bytes((int)H, (int)W);
+    TORCH_CHECK(nbytes >= 0, "hnr::point_occlusion: H*W must be at most 2^24");
+    Tensor vis = at::empty({n}, xyz.options().dtype(at::kByte)), scratch = at::empty({nbytes}, xyz.options().dtype(at::kByte));
+    if (n > 0)
+        hnr_check(hnr_point_occlusion(fptr(xyz, "xyz"), n, m, m + 16, (int)H, (int)W, (float)tolerate, vis.data_ptr<uint8_t>(), scratch.data_ptr(), nbytes,
+                                      cur_stream(xyz)),
+                  "hnr_point_occlusion");
+    return vis;
+}
+
 // ---- hnr::nearest_view(Tensor xyz [N,3], Tensor campos [M,3], Tensor camdir [M,3]) -> Tensor [N] i32
 Tensor nearest_view(const Tensor &xyz, const Tensor &campos, const Tensor &camdir)
 {
@@ -400,16 +478,17 @@ Tensor nearest_view(const Tensor &xyz, const Tensor &campos, const Tensor &camdi
     return out;
 }
 
-// ---- hnr::point_view_attrs(Tensor xyz, float[] w2c, float[] c2w, float[] cam_pos_cam, float[] intrinsic, int H, int W, Tensor? feat [C,Hl,Wl])
-//      -> (features [n,C], dir [n,3], mask [n] u8).  The matrices are host values, row-major, as in the C ABI.  Without feat (the C ABI's NULL
+// ---- hnr::point_view_attrs(Tensor xyz, float[] w2c, float[] c2w, float[] cam_pos_cam, float[] intrinsic, int H, int W, Tensor? feat [C,Hl,Wl],
+//      Tensor? visible [n] u8 = None) -> (features [n,C], dir [n,3], mask [n] u8).  The matrices are host values, row-major, as in the C ABI.  Without feat (the C ABI's NULL
 //      d_feat / d_out_feat) features is [n,0].
 std::tuple<Tensor, Tensor, Tensor> point_view_attrs(const Tensor &xyz, c10::ArrayRef<double> w2c, c10::ArrayRef<double> c2w, c10::ArrayRef<double> cam_pos_cam,
-                                                    c10::ArrayRef<double> intrinsic, int64_t H, int64_t W, const OptT &feat_opt)
+                                                    c10::ArrayRef<double> intrinsic, int64_t H, int64_t W, const OptT &feat_opt, const OptT &visible)
 {
     TORCH_CHECK(xyz.dim() == 2 && xyz.size(1) == 3, "hnr::point_view_attrs: xyz must be [n,3]");
     TORCH_CHECK(w2c.size() == 16 && c2w.size() == 16 && cam_pos_cam.size() == 3 && intrinsic.size() == 9, "hnr::point_view_attrs: w2c / c2w hold 16 values, cam_pos_cam 3, intrinsic 9");
     const bool sample = feat_opt.has_value() && feat_opt->defined();
     if (sample) TORCH_CHECK(feat_opt->dim() == 3 && feat_opt->device() == xyz.device(), "hnr::point_view_attrs: feat must be [C,Hl,Wl] on xyz's device");
+    const uint8_t *vis = vis_ptr(visible, xyz, "hnr::point_view_attrs");
     const c10::DeviceGuard guard(xyz.device());              // the tensor's device is current for the allocations and the launch
     float m[16 + 16 + 3 + 9];
     for (int i = 0; i < 16; ++i) { m[i] = (float)w2c[i]; m[16 + i] = (float)c2w[i]; }
@@ -419,9 +498,9 @@ std::tuple<Tensor, Tensor, Tensor> point_view_attrs(const Tensor &xyz, c10::Arra
     const int64_t C = sample ? feat_opt->size(0) : 0;
     Tensor out = new_f32({n, C}, xyz), dir = new_f32({n, 3}, xyz), mask = at::empty({n}, xyz.options().dtype(at::kByte));
     if (n > 0)
-        hnr_check(hnr_point_view_attrs(fptr(xyz, "xyz"), n, m, m + 16, m + 32, m + 35, (int)H, (int)W, sample ? fptr(*feat_opt, "feat") : nullptr, (int)C,
-                                       sample ? (int)feat_opt->size(1) : 0, sample ? (int)feat_opt->size(2) : 0, sample ? out.data_ptr<float>() : nullptr,
-                                       dir.data_ptr<float>(), mask.data_ptr<uint8_t>(), cur_stream(xyz)),
+        hnr_check(hnr_point_view_attrs_vis(fptr(xyz, "xyz"), n, m, m + 16, m + 32, m + 35, (int)H, (int)W, sample ? fptr(*feat_opt, "feat") : nullptr, (int)C,
+                                           sample ? (int)feat_opt->size(1) : 0, sample ? (int)feat_opt->size(2) : 0, vis, sample ? out.data_ptr<float>() : nullptr,
+                                           dir.data_ptr<float>(), mask.data_ptr<uint8_t>(), cur_stream(xyz)),
                   "hnr_point_view_attrs");
     return {out, dir, mask};
 }
@@ -445,10 +524,10 @@ std::tuple<Tensor, Tensor, Tensor> featnet_forward(const Tensor &images, const T
 }
 
 // ---- hnr::point_embed(Tensor xyz, float[] w2c, float[] c2w, float[] cam_pos_cam, float[] intrinsic, Tensor image [3,H,W], Tensor x1, Tensor x2, Tensor x3,
-//      Tensor premlp [HNR_PREMLP_PACKED_ELEMS], bool want_row) -> (emb [n,32], color [n,3], dir [n,3], row [n,63] or [n,0])
+//      Tensor premlp [HNR_PREMLP_PACKED_ELEMS], bool want_row, Tensor? visible [n] u8 = None) -> (emb [n,32], color [n,3], dir [n,3], row [n,63] or [n,0])
 std::tuple<Tensor, Tensor, Tensor, Tensor> point_embed(const Tensor &xyz, c10::ArrayRef<double> w2c, c10::ArrayRef<double> c2w, c10::ArrayRef<double> cam_pos_cam,
                                                        c10::ArrayRef<double> intrinsic, const Tensor &image, const Tensor &x1, const Tensor &x2, const Tensor &x3,
-                                                       const Tensor &premlp, bool want_row)
+                                                       const Tensor &premlp, bool want_row, const OptT &visible)
 {
     TORCH_CHECK(xyz.dim() == 2 && xyz.size(1) == 3, "hnr::point_embed: xyz must be [n,3]");
     TORCH_CHECK(w2c.size() == 16 && c2w.size() == 16 && cam_pos_cam.size() == 3 && intrinsic.size() == 9, "hnr::point_embed: w2c / c2w hold 16 values, cam_pos_cam 3, intrinsic 9");
@@ -460,6 +539,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> point_embed(const Tensor &xyz, c10::A
                 "hnr::point_embed: x1 / x2 / x3 must be [8,H,W], [16,H2,W2], [32,H4,W4] of the image's pyramid");
     TORCH_CHECK(premlp.dim() == 1 && premlp.size(0) == HNR_PREMLP_PACKED_ELEMS, "hnr::point_embed: premlp must hold HNR_PREMLP_PACKED_ELEMS values");
     for (const Tensor *t : {&image, &x1, &x2, &x3, &premlp}) TORCH_CHECK(t->device() == xyz.device(), "hnr::point_embed: every tensor must be on xyz's device");
+    const uint8_t *vis = vis_ptr(visible, xyz, "hnr::point_embed");
     const c10::DeviceGuard guard(xyz.device());
     float m[16 + 16 + 3 + 9];
     for (int i = 0; i < 16; ++i) { m[i] = (float)w2c[i]; m[16 + i] = (float)c2w[i]; }
@@ -468,9 +548,9 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> point_embed(const Tensor &xyz, c10::A
     const int64_t n = xyz.size(0);
     Tensor emb = new_f32({n, 32}, xyz), color = new_f32({n, 3}, xyz), dir = new_f32({n, 3}, xyz), row = new_f32({n, want_row ? 63 : 0}, xyz);
     if (n > 0)
-        hnr_check(hnr_point_embed(fptr(xyz, "xyz"), n, m, m + 16, m + 32, m + 35, (int)H, (int)W, fptr(image, "image"), fptr(x1, "x1"), fptr(x2, "x2"),
-                                  fptr(x3, "x3"), fptr(premlp, "premlp"), emb.data_ptr<float>(), color.data_ptr<float>(), dir.data_ptr<float>(),
-                                  want_row ? row.data_ptr<float>() : nullptr, cur_stream(xyz)),
+        hnr_check(hnr_point_embed_vis(fptr(xyz, "xyz"), n, m, m + 16, m + 32, m + 35, (int)H, (int)W, fptr(image, "image"), fptr(x1, "x1"), fptr(x2, "x2"),
+                                      fptr(x3, "x3"), fptr(premlp, "premlp"), nullptr, vis, emb.data_ptr<float>(), color.data_ptr<float>(),
+                                      dir.data_ptr<float>(), want_row ? row.data_ptr<float>() : nullptr, cur_stream(xyz)),
                   "hnr_point_embed");
     return {emb, color, dir, row};
 }
@@ -581,10 +661,14 @@ TORCH_LIBRARY(hnr, m)
     m.def("render_train_bwd(Tensor?[] inputs, Tensor[] weights, Tensor[] fwd, Tensor g_raycolor, Tensor? g_conf_coefficient, int SR, int[] kernel_size, float radius2, "
           "float vsize_z, int raydist_mode_unit, int knn_order, float slope, int cap_samples) -> Tensor[]");
     m.def("nearest_view(Tensor xyz, Tensor campos, Tensor camdir) -> Tensor");
-    m.def("point_view_attrs(Tensor xyz, float[] w2c, float[] c2w, float[] cam_pos_cam, float[] intrinsic, int H, int W, Tensor? feat) -> (Tensor, Tensor, Tensor)");
+    m.def("point_view_attrs(Tensor xyz, float[] w2c, float[] c2w, float[] cam_pos_cam, float[] intrinsic, int H, int W, Tensor? feat, Tensor? visible=None) -> (Tensor, Tensor, Tensor)");
+    m.def("alpha_pack(Tensor alphas) -> Tensor");
+    m.def("visual_hull_select(Tensor xyz, Tensor? conf, Tensor? view, Tensor bits, Tensor cams, int W, float[] near_far, bool range_mask, int capacity) -> "
+          "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("point_occlusion(Tensor xyz, float[] w2c, float[] intrinsic, int H, int W, float tolerate) -> Tensor");
     m.def("featnet_forward(Tensor images, Tensor packed) -> (Tensor, Tensor, Tensor)");
     m.def("point_embed(Tensor xyz, float[] w2c, float[] c2w, float[] cam_pos_cam, float[] intrinsic, Tensor image, Tensor x1, Tensor x2, Tensor x3, Tensor premlp, "
-          "bool want_row) -> (Tensor, Tensor, Tensor, Tensor)");
+          "bool want_row, Tensor? visible=None) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("mvsnet_feature(Tensor images, Tensor packed) -> Tensor");
     m.def("mvsnet_cost_volume(Tensor feat, Tensor proj, Tensor depth_values) -> Tensor");
     m.def("mvsnet_cost_reg(Tensor volume, Tensor packed) -> Tensor");
@@ -605,6 +689,9 @@ TORCH_LIBRARY_IMPL(hnr, CUDA, m)
     m.impl("render_train_bwd", &render_train_bwd);
     m.impl("nearest_view", &nearest_view);
     m.impl("point_view_attrs", &point_view_attrs);
+    m.impl("alpha_pack", &alpha_pack);
+    m.impl("visual_hull_select", &visual_hull_select);
+    m.impl("point_occlusion", &point_occlusion);
     m.impl("featnet_forward", &featnet_forward);
     m.impl("point_embed", &point_embed);
     m.impl("mvsnet_feature", &mvsnet_feature);

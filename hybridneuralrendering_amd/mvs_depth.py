@@ -284,22 +284,24 @@ class MVSNet(nn.Module):
         return torch.stack(depths), torch.stack(confs), features, (torch.stack(probs) if want_prob else None)
 
 
-def check_options(opt):
+def check_options(opt, occlusion=None):
     if int(getattr(opt, "manual_depth_view", 1)) != 1:
         raise HnrError("depth_views: manual_depth_view=%r is not implemented (only 1: the expected depth of the pretrained estimator)" % opt.manual_depth_view)
     if float(getattr(opt, "manual_std_depth", 0.0) or 0.0) != 0.0:
         raise HnrError("depth_views: manual_std_depth != 0 (Gaussian depth sampling) is not implemented")
-    if int(getattr(opt, "depth_occ", 0) or 0) > 0:
-        raise HnrError("depth_views: depth_occ > 0 is not implemented")
+    if int(getattr(opt, "depth_occ", 0) or 0) > 0 and (occlusion is None or occlusion is False):
+        raise HnrError("depth_views: depth_occ > 0 is not implemented without the keyword occlusion=True (the depth maps do not depend on it; the "
+                       "embedding stage, MvsInit / init_cloud_from_mvs_depth, runs the occlusion test)")
 
 
-def depth_views(batch, net, opt):
+def depth_views(batch, net, opt, occlusion=None):
     """The `manual_depth_view == 1` branch of `MvsPointsModel.gen_points` (models/mvs/mvs_points_model.py:300-341).  batch: the dataset item on the GPU
     -- images [1,N,3,H,W] (mvs_images, when present, is what the estimator sees), proj_mats [1,N,N,3,4] (row i: every view seen from view i),
     near_fars [1,N,2], near_fars_depth [1,2], intrinsics [1,N,3,3], w2cs [1,N,4,4] and optionally c2ws.  opt: init_view_num, depth_vid.
     Returns one dict per entry of depth_vid -- cam_xyz [H,W,3], confidence [H,W], points_mask [H,W], intrinsic, w2c[, c2w], image [3,H,W], depth [h,w] --
-    the `views` of cloud_init.init_cloud_from_mvs_depth.  The feature maps are computed once, not once per entry of depth_vid."""
-    check_options(opt)
+    the `views` of cloud_init.init_cloud_from_mvs_depth.  The feature maps are computed once, not once per entry of depth_vid.
+    occlusion=True accepts opt.depth_occ > 0; nothing else changes: depth_occ does not enter this stage."""
+    check_options(opt, occlusion)
     if not isinstance(net, MVSNet):
         raise HnrError("depth_views: net must be an mvs_depth.MVSNet")
     imgs = _gpu(batch["images"], "images")

@@ -66,9 +66,10 @@ def featnet_forward(images, packed):
     return tuple(outs)
 
 
-def point_embed(xyz, w2c, c2w, cpc, intrinsic, image, x1, x2, x3, premlp, want_row=False, conf=None):
+def point_embed(xyz, w2c, c2w, cpc, intrinsic, image, x1, x2, x3, premlp, want_row=False, conf=None, visible=None):
     """hnr_point_embed for one view: (emb [n,32], color [n,3], dir [n,3], row [n,63] or None).  image [3,H,W]; x1 / x2 / x3 its pyramid, channels first.
-    conf [n] (optional): the photometric confidence premlp sees in the row's last column (hnr_point_embed_conf); None: ones."""
+    conf [n] (optional): the photometric confidence premlp sees in the row's last column (hnr_point_embed_conf); None: ones.
+    visible [n] uint8 (optional, cloud_init.point_occlusion's flags, hnr_point_embed_vis): where it is 0 the point counts as outside the frame."""
     from .cloud_init import _cf, _host_f32
     L = _lib.lib()
     xyz = _lib.require_gpu(xyz, "xyz", torch.float32).reshape(-1, 3)
@@ -90,12 +91,20 @@ def point_embed(xyz, w2c, c2w, cpc, intrinsic, image, x1, x2, x3, premlp, want_r
         conf = _lib.require_gpu(conf, "conf", torch.float32).reshape(-1)
         if conf.shape[0] != n or conf.device != dev:
             raise HnrError("point_embed: conf must hold one value per point, on xyz's device")
+    if visible is not None:
+        visible = _lib.require_gpu(visible, "visible", torch.uint8).reshape(-1)
+        if visible.shape[0] != n or visible.device != dev:
+            raise HnrError("point_embed: visible must hold one flag per point, on xyz's device")
     emb, color, pdir = (torch.empty((n, c), dtype=torch.float32, device=dev) for c in (32, 3, 3))
     row = torch.empty((n, 63), dtype=torch.float32, device=dev) if want_row else None
     if n > 0:
         a = [_host_f32(w2c, (4, 4), "w2c"), _host_f32(c2w, (4, 4), "c2w"), _host_f32(cpc, (3,), "cam_pos_cam"), _host_f32(intrinsic, (3, 3), "intrinsic")]
         with torch.cuda.device(dev):
-            if conf is None:
+            if visible is not None:
+                _lib.check(L.hnr_point_embed_vis(_lib.ptr(xyz), n, _cf(a[0]), _cf(a[1]), _cf(a[2]), _cf(a[3]), H, W, _lib.ptr(image), _lib.ptr(maps[0]),
+                                                 _lib.ptr(maps[1]), _lib.ptr(maps[2]), _lib.ptr(premlp), _lib.ptr(conf), _lib.ptr(visible), _lib.ptr(emb),
+                                                 _lib.ptr(color), _lib.ptr(pdir), _lib.ptr(row), _lib.stream()), "hnr_point_embed_vis")
+            elif conf is None:
                 _lib.check(L.hnr_point_embed(_lib.ptr(xyz), n, _cf(a[0]), _cf(a[1]), _cf(a[2]), _cf(a[3]), H, W, _lib.ptr(image), _lib.ptr(maps[0]),
                                              _lib.ptr(maps[1]), _lib.ptr(maps[2]), _lib.ptr(premlp), _lib.ptr(emb), _lib.ptr(color), _lib.ptr(pdir), _lib.ptr(row),
                                              _lib.stream()), "hnr_point_embed")
@@ -164,7 +173,22 @@ class FeatureNet(nn.Module):
         return [x] + list(featnet_forward(x, self.packed()))
 
 
-def check_options(opt):
+def occlusion_tolerance(opt, occlusion, what):
+    """The tolerance of the occlusion test (cloud_init.point_occlusion) a call runs with, or None for no test.  opt.depth_occ > 0 is accepted only
+    with the keyword: occlusion=True (the reference's 0.1, mvs_points_model.py:204) or a number; without depth_occ a number alone turns the test on."""
+    occ = int(getattr(opt, "depth_occ", 0) or 0) > 0 if opt is not None else False
+    given = occlusion is not None and occlusion is not False
+    if occ and not given:
+        raise HnrError("%s: depth_occ > 0 (occlusion-aware warps) is not implemented without the keyword occlusion=True" % what)
+    if not given or (occlusion is True and not occ):
+        return None
+    tol = 0.1 if occlusion is True else float(occlusion)
+    if not tol >= 0.0:
+        raise HnrError("%s: occlusion must be True or a tolerance >= 0" % what)
+    return tol
+
+
+def check_options(opt, occlusion=None):
     """The shipped family only: anything else would need another row layout or another network."""
     fs = getattr(opt, "appr_feature_str0", FEATURE_STR)
     fs = fs.split() if isinstance(fs, str) else list(fs)
@@ -173,8 +197,7 @@ def check_options(opt):
     for name, want in (("point_features_dim", 32), ("shading_feature_mlp_layer1", 2), ("act_type", "LeakyReLU")):
         if getattr(opt, name, want) != want:
             raise HnrError("MvsInit: %s=%r is not implemented (only %r)" % (name, getattr(opt, name), want))
-    if int(getattr(opt, "depth_occ", 0) or 0) > 0:
-        raise HnrError("MvsInit: depth_occ > 0 (occlusion-aware warps) is not implemented")
+    occlusion_tolerance(opt, occlusion, "MvsInit")
     if int(getattr(opt, "shading_feature_mlp_layer0", 1)) < 1:
         raise HnrError("MvsInit: shading_feature_mlp_layer0=0 leaves no premlp to run: use cloud_init.query_point_attributes")
 
@@ -183,10 +206,11 @@ class MvsInit(nn.Module):
     """`.FeatureNet` + `.premlp` under the names of the reference's MvsPointsModel, so that a `*_net_mvs.pth` loads with
     `load_state_dict(sd, strict=False)`: `MVSNet.*` keys and `num_batches_tracked` entries are ignored, every key this module owns must be there."""
 
-    def __init__(self, opt=None):
+    def __init__(self, opt=None, occlusion=None):
         super().__init__()
         if opt is not None:
-            check_options(opt)
+            check_options(opt, occlusion)
+        self.occlusion = occlusion_tolerance(opt, occlusion, "MvsInit")           # embed_points' default: 0.1 with occlusion=True and opt.depth_occ > 0
         self.FeatureNet = FeatureNet()
         self.premlp = nn.Sequential(nn.Linear(63, 32), nn.LeakyReLU(SLOPE, inplace=True), nn.Linear(32, 32), nn.LeakyReLU(SLOPE, inplace=True))
         self._packed = _Packed()
@@ -220,12 +244,15 @@ class MvsInit(nn.Module):
         """imgs [B,V,3,H,W] -> [x, x1, x2, x3] (MvsPointsModel.get_image_features)."""
         return self.FeatureNet(imgs)
 
-    def embed_points(self, xyz_world, image_chw, c2w, w2c, intrinsic, default_conf=-1, feats=None, want_row=False, conf=None):
+    def embed_points(self, xyz_world, image_chw, c2w, w2c, intrinsic, default_conf=-1, feats=None, want_row=False, conf=None, occlusion=None):
         """What run/train_ft.py:759-761 computes for the points of one view: (embedding [1,n,32], color [1,n,3], dir [1,n,3], conf [1,n,1]).
         image_chw [3,H,W] (or [1,3,H,W]); w2c None: the fp32 inverse of c2w, as the reference forms it.  feats: the view's [x, x1, x2, x3] from
         get_image_features when it is already there.  want_row: a fifth result, the [n,63] rows premlp saw.
         conf [n]: the points' photometric confidence (run/train_ft.py:176-180, the MVS start): premlp sees it in place of the ones and it is returned
-        as [1,n,1], untouched by default_conf (which the reference applies on the depth-frame path only); None: today's ones."""
+        as [1,n,1], untouched by default_conf (which the reference applies on the depth-frame path only); None: today's ones.
+        occlusion: a tolerance runs cloud_init.point_occlusion over these points first (`depth_occ = 1`: homo_warp_nongrid_occ for view 0 of the points'
+        own view, w2c=None in extract_2d) and the hidden points are embedded as points outside the frame; None: the module's default (0.1 for
+        MvsInit(opt, occlusion=True) with opt.depth_occ > 0, else no test); False: no test."""
         from . import cloud_init as ci
         img = _lib.require_gpu(image_chw, "image_chw", torch.float32)
         img = img.reshape(img.shape[-3:]).contiguous()
@@ -235,8 +262,12 @@ class MvsInit(nn.Module):
             feats = self.get_image_features(img[None, None])
         w2c = torch.inverse(torch.from_numpy(ci._host_f32(c2w, (4, 4), "c2w"))).numpy() if w2c is None else w2c
         cpc = ci.cam_pos_cam(c2w, w2c)
+        tol = self.occlusion if occlusion is None else (None if occlusion is False else (0.1 if occlusion is True else float(occlusion)))
+        vis = None
+        if tol is not None and int(xyz_world.numel()) > 0:
+            vis = ci.point_occlusion(xyz_world, w2c, intrinsic, int(img.shape[1]), int(img.shape[2]), tol)
         emb, color, pdir, row = point_embed(xyz_world, w2c, c2w, cpc, intrinsic, img, feats[1][0], feats[2][0], feats[3][0], self.premlp_packed(), want_row,
-                                            conf=conf)
+                                            conf=conf, visible=vis)
         out = (emb[None], color[None], pdir[None],
                ci.point_conf(emb.shape[0], default_conf, emb.device) if conf is None else conf.detach().to(torch.float32).reshape(1, -1, 1).clone())
         return out + (row,) if want_row else out

@@ -2,7 +2,8 @@
 
 SURVEY 8b asks for both op layers: the C ABI (include/hnr.h, bound by ctypes in _lib.py -- needs no torch headers) and registered torch ops.  The
 ops are the same library calls with schemas: `hnr::grid_build`, `hnr::grid_free`, `hnr::march_query`, `hnr::nearest_view`, `hnr::point_view_attrs`
-(the cloud initialisation of cloud_init.py), `hnr::featnet_forward`, `hnr::point_embed` (the init checkpoint's networks, mvs_init.py), `hnr::mvsnet_feature`,
+(the cloud initialisation of cloud_init.py), `hnr::alpha_pack`, `hnr::visual_hull_select`, `hnr::point_occlusion` (the synthetic scenes' visual-hull
+masking and occlusion test, cloud_init.py), `hnr::featnet_forward`, `hnr::point_embed` (the init checkpoint's networks, mvs_init.py), `hnr::mvsnet_feature`,
 `hnr::mvsnet_cost_volume`, `hnr::mvsnet_cost_reg`, `hnr::mvsnet_depth_head`, `hnr::mvsnet_depth_points` (the depth estimator, mvs_depth.py), `hnr::render_forward`
 (NeuralPointsRayMarching.forward + fill_invalid in eval mode, /root/reference/models/neural_points_volumetric_model.py:257-391, :87-126) and
 `hnr::render_train` (the same in train mode with the backward pass registered as its autograd formula; the reference leaves that to torch autograd,
@@ -100,8 +101,23 @@ def _register_fakes():
     def _(xyz, campos, camdir):
         return xyz.new_empty((xyz.shape[0],), dtype=i32)
 
+    @torch.library.register_fake("hnr::alpha_pack")
+    def _(alphas):
+        M, H, W = alphas.shape
+        return alphas.new_empty((M, H, (W + 31) // 32), dtype=i32)
+
+    @torch.library.register_fake("hnr::visual_hull_select")
+    def _(xyz, conf, view, bits, cams, W, near_far, range_mask, capacity):
+        n, rows, e = xyz.shape[0], max(capacity, 1), xyz.new_empty
+        return (e((n,), dtype=torch.uint8), e((rows, 3), dtype=f32), e((rows if conf is not None else 0,), dtype=f32),
+                e((rows if view is not None else 0,), dtype=i32), e((1,), dtype=torch.int64), e((1,), dtype=i32))
+
+    @torch.library.register_fake("hnr::point_occlusion")
+    def _(xyz, w2c, intrinsic, H, W, tolerate):
+        return xyz.new_empty((xyz.shape[0],), dtype=torch.uint8)
+
     @torch.library.register_fake("hnr::point_view_attrs")
-    def _(xyz, w2c, c2w, cam_pos_cam, intrinsic, H, W, feat):
+    def _(xyz, w2c, c2w, cam_pos_cam, intrinsic, H, W, feat, visible=None):
         n, e = xyz.shape[0], xyz.new_empty
         return (e((n, feat.shape[0] if feat is not None else 0), dtype=f32), e((n, 3), dtype=f32), e((n,), dtype=torch.uint8))
 
@@ -113,7 +129,7 @@ def _register_fakes():
         return (e((V, 8, H, W), dtype=f32), e((V, 16, H2, W2), dtype=f32), e((V, 32, (H2 - 1) // 2 + 1, (W2 - 1) // 2 + 1), dtype=f32))
 
     @torch.library.register_fake("hnr::point_embed")
-    def _(xyz, w2c, c2w, cam_pos_cam, intrinsic, image, x1, x2, x3, premlp, want_row):
+    def _(xyz, w2c, c2w, cam_pos_cam, intrinsic, image, x1, x2, x3, premlp, want_row, visible=None):
         n, e = xyz.shape[0], xyz.new_empty
         return (e((n, 32), dtype=f32), e((n, 3), dtype=f32), e((n, 3), dtype=f32), e((n, 63 if want_row else 0), dtype=f32))
 
@@ -232,13 +248,41 @@ def nearest_view(campos, raydir, xyz, id_list=None):
                             g(raydir, "raydir", torch.float32).reshape(-1, 3)).long().view(-1, 1)
 
 
-def point_view_attrs(xyz, w2c, c2w, cam_pos_cam, intrinsic, H, W, feat=None):
+def _flat(a, n):
+    return [float(v) for v in np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float32).reshape(n)]
+
+
+def alpha_pack(alphas):
+    """cloud_init.alpha_pack through torch.ops.hnr.alpha_pack: alphas [M,H,W] -> int32 [M,H,(W+31)//32]."""
+    return load().alpha_pack(_lib.require_gpu(alphas, "alphas", torch.float32))
+
+
+def visual_hull_select(xyz, bits, cams, W, near_far=None, range_mask=False, conf=None, view=None, capacity=None):
+    """cloud_init.visual_hull_select through torch.ops.hnr.visual_hull_select: (mask [n] uint8, xyz [cap,3], conf [cap] or [0], view [cap] or [0],
+    count [1] int64, status [1] int32).  bits / cams: AlphaMasks.bits / .cams; near_far: (near, far) or None."""
+    from .cloud_init import _near_far_pair
+    g = _lib.require_gpu
+    xyz = g(xyz, "xyz", torch.float32).reshape(-1, 3)
+    nf = _near_far_pair(near_far, "visual_hull_select")
+    return load().visual_hull_select(xyz, None if conf is None else g(conf, "conf", torch.float32), None if view is None else g(view, "view", torch.int32),
+                                     g(bits, "bits", torch.int32), g(cams, "cams", torch.float32), int(W), [] if nf is None else [float(v) for v in nf],
+                                     bool(range_mask), int(xyz.shape[0] if capacity is None else capacity))
+
+
+def point_occlusion(xyz, w2c, intrinsic, H, W, tolerate=0.1):
+    """cloud_init.point_occlusion through torch.ops.hnr.point_occlusion: uint8 [n]."""
+    return load().point_occlusion(_lib.require_gpu(xyz, "xyz", torch.float32).reshape(-1, 3), _flat(w2c, 16), _flat(intrinsic, 9), int(H), int(W),
+                                  float(np.float32(tolerate)))
+
+
+def point_view_attrs(xyz, w2c, c2w, cam_pos_cam, intrinsic, H, W, feat=None, visible=None):
     """cloud_init.point_view_attrs through torch.ops.hnr.point_view_attrs: (features [n,C], dir [n,3], mask [n] uint8); without `feat` the features are
-    [n,0].  The matrices are host arrays (fp32 values travel exactly through the op's float[] arguments)."""
+    [n,0].  The matrices are host arrays (fp32 values travel exactly through the op's float[] arguments).  visible: point_occlusion's flags."""
     ops = load()
     flat = lambda a, n: [float(v) for v in np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float32).reshape(n)]
     return ops.point_view_attrs(_lib.require_gpu(xyz, "xyz", torch.float32).reshape(-1, 3), flat(w2c, 16), flat(c2w, 16), flat(cam_pos_cam, 3), flat(intrinsic, 9),
-                                int(H), int(W), None if feat is None else _lib.require_gpu(feat, "feat", torch.float32))
+                                int(H), int(W), None if feat is None else _lib.require_gpu(feat, "feat", torch.float32),
+                                None if visible is None else _lib.require_gpu(visible, "visible", torch.uint8))
 
 
 def featnet_forward(images, packed):
@@ -248,14 +292,14 @@ def featnet_forward(images, packed):
     return ops.featnet_forward(g(images, "images", torch.float32), g(packed, "packed", torch.float32))
 
 
-def point_embed(xyz, w2c, c2w, cam_pos_cam, intrinsic, image, x1, x2, x3, premlp, want_row=False):
-    """mvs_init.point_embed through torch.ops.hnr.point_embed: (emb [n,32], color [n,3], dir [n,3], row [n,63] or [n,0])."""
+def point_embed(xyz, w2c, c2w, cam_pos_cam, intrinsic, image, x1, x2, x3, premlp, want_row=False, visible=None):
+    """mvs_init.point_embed through torch.ops.hnr.point_embed: (emb [n,32], color [n,3], dir [n,3], row [n,63] or [n,0]).  visible: point_occlusion's flags."""
     ops = load()
     g = _lib.require_gpu
     flat = lambda a, n: [float(v) for v in np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float32).reshape(n)]
     return ops.point_embed(g(xyz, "xyz", torch.float32).reshape(-1, 3), flat(w2c, 16), flat(c2w, 16), flat(cam_pos_cam, 3), flat(intrinsic, 9),
                            g(image, "image", torch.float32), g(x1, "x1", torch.float32), g(x2, "x2", torch.float32), g(x3, "x3", torch.float32),
-                           g(premlp, "premlp", torch.float32), bool(want_row))
+                           g(premlp, "premlp", torch.float32), bool(want_row), None if visible is None else g(visible, "visible", torch.uint8))
 
 
 def mvsnet_feature(images, packed):

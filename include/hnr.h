@@ -25,6 +25,7 @@
  *              hnr_shipped_loss*, hnr_composite, hnr_ray_depth, hnr_ray_march, hnr_voxel_downsample*, hnr_probe_select, hnr_blur_*,
  *              hnr_frame_metrics* (and the HNR_FM_* row layout), hnr_depth_fuse*, hnr_range_crop*, hnr_nearest_view, hnr_point_view_attrs,
  *              hnr_featnet_*, hnr_point_embed*, hnr_geo_consistency, hnr_geo_filter_select*, hnr_mvsnet_*,
+ *              hnr_alpha_pack, hnr_visual_hull_select*, hnr_point_occlusion*, hnr_point_view_attrs_vis,
  *              hnr_frame_batch*, hnr_frame_item, hnr_ray_miss_rank.
  *   STAGE   -- everything else (hnr_chain_*, hnr_mlp3_*, hnr_merge*, hnr_mixup_stage, hnr_proj_*, hnr_h2*, hnr_linear_*, hnr_gather_*, hnr_ksum*,
  *              hnr_segment_*, hnr_absmax, hnr_div_probe, hnr_image_features_bwd_bbox, ...): the individual stages the two single-call entries are built from.  They are exported so
@@ -877,6 +878,12 @@ int hnr_nearest_view(const float *d_xyz, int64_t N, const float *d_campos, const
  * outputs may be NULL (not all); d_feat / C / Hl / Wl are read only with d_out_feat. */
 int hnr_point_view_attrs(const float *d_xyz, int64_t n, const float *w2c, const float *c2w, const float *cam_pos_cam, const float *K, int H, int W,
                          const float *d_feat, int C, int Hl, int Wl, float *d_out_feat, float *d_out_dir, uint8_t *d_out_mask, void *stream);
+/* The same with the occlusion flags of hnr_point_occlusion: d_visible [n] uint8 (NULL: hnr_point_view_attrs itself, which forwards here).  Where it is
+ * 0 the point is treated as outside the frame -- mask 0, zero features, its direction -- which is what `extract_from_2d_grid` does with the mask
+ * `homo_warp_nongrid_occ` has shrunk (models/mvs/mvs_utils.py:363, :411-420). */
+int hnr_point_view_attrs_vis(const float *d_xyz, int64_t n, const float *w2c, const float *c2w, const float *cam_pos_cam, const float *K, int H, int W,
+                             const float *d_feat, int C, int Hl, int Wl, const uint8_t *d_visible, float *d_out_feat, float *d_out_dir,
+                             uint8_t *d_out_mask, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Point embeddings from the MVS init checkpoint: the last stage of the `load_points=2` start of a scene (run/train_ft.py:751-765).  Inference only.
@@ -915,6 +922,12 @@ int hnr_point_embed(const float *d_xyz, int64_t n, const float *w2c, const float
 int hnr_point_embed_conf(const float *d_xyz, int64_t n, const float *w2c, const float *c2w, const float *cam_pos_cam, const float *K, int H, int W,
                          const float *d_image, const float *d_x1, const float *d_x2, const float *d_x3, const float *d_premlp, const float *d_conf,
                          float *d_emb, float *d_color, float *d_dir, float *d_row, void *stream);
+/* ... and with the occlusion flags of hnr_point_occlusion (`depth_occ = 1`, mvs_points_model.py:203): d_visible [n] uint8 (NULL: hnr_point_embed_conf
+ * itself, which forwards here).  Where it is 0 the point is treated as outside the frame: zero features and colour, its direction, and still a row
+ * through premlp. */
+int hnr_point_embed_vis(const float *d_xyz, int64_t n, const float *w2c, const float *c2w, const float *cam_pos_cam, const float *K, int H, int W,
+                        const float *d_image, const float *d_x1, const float *d_x2, const float *d_x3, const float *d_premlp, const float *d_conf,
+                        const uint8_t *d_visible, float *d_emb, float *d_color, float *d_dir, float *d_row, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * The per-step data path: a device-resident frame bank and the ray batch drawn from it (csrc/frames.hip).  Replaces the dataset item of the
@@ -1049,6 +1062,47 @@ int hnr_geo_filter_select(const float *d_cam_xyz, const float *d_conf, const uin
                           int V, int H, int W, const float *d_Einv, float conf_thresh, int geo_cnsst_num, const float *ranges, const float *conf_table,
                           float *d_world, float *d_cam, float *d_conf_out, int32_t *d_view, int64_t capacity, int64_t *d_view_counts, int64_t *d_total,
                           int32_t *d_status, void *d_scratch, int64_t scratch_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Visual-hull masking and the occlusion test of the NeRF-synthetic start of a scene (csrc/hull.hip): `load_points=0`, `depth_occ=1`, a dataset with
+ * `alphas` (dev_scripts/w_n360/chair_hybrid.sh, lego_hybrid.sh).  fp32, every operation rounded on its own in the order written; stream-ordered, nothing is allocated,
+ * nothing is read back, no float atomics.  HNR_ERR_BADARG, before any launch, for a NULL pointer, a shape outside the limits given or a short scratch.
+ *
+ * hnr_alpha_pack -- d_alphas [M,H,W] float32 -> d_bits [M,H,Wp] uint32, Wp = (W + 31) / 32: bit (x & 31) of word x >> 5 of a row is alpha > 0.1f (a NaN:
+ *   0); the padding bits of a row's last word are 0.  This is all hnr_visual_hull_select needs of an alpha map.  PRECONDITION: alpha >= -0.9 (dataset
+ *   alphas are in [0, 1]): with the range mask on, the reference lets a point outside the frame pass because alpha + 1 > 0.1 whatever pixel the clamped
+ *   lookup hits, and the kernel does not look.  1 <= M <= 65535, 1 <= H, W <= 32768, M*H < 2^31.
+ *
+ * hnr_visual_hull_select -- `alpha_masking` (models/mvs/mvs_utils.py:573-607) and the `masking` that follows it (run/train_ft.py:152-158) in one
+ *   pass.  d_cams [M,21]: per view rows 0..2 of w2c (12 values, row-major) and K (9).  Per point (x, y, z) and view, views ascending:
+ *     cam[q] = ((x*w[q][0] + y*w[q][1]) + z*w[q][2]) + w[q][3];   p[q] = (cam0*K[q][0] + cam1*K[q][1]) + cam2*K[q][2],  q = 0..2
+ *     u = floor(p0 / p2), v = floor(p1 / p2)   (correctly rounded divides)
+ *     near_far != NULL (two host floats: near - 1 -- formed by the caller in double and rounded to fp32 -- and far):  near - 1 <= cam[2] <= far
+ *     range_mask != 0 (opt.alpha_range > 0 or opt.inall_img == 0):  a point with !(0 <= u < W && 0 <= v < H) passes this view
+ *     otherwise the bit at (min(max(u, 0), W-1), min(max(v, 0), H-1)); the clamp is done in float before the conversion to int; a u or v that is not
+ *     finite reads pixel 0 (the reference's value there is whatever the platform's float -> int64 conversion gives).
+ *   A point survives when every view passes; the loop is left at the first failing view.  d_mask [n] uint8 (optional) = survives.  The survivors, in
+ *   input order, go to d_out_xyz [capacity,3], d_out_conf [capacity] (from d_conf [n]) and d_out_view [capacity] int32 (from d_view [n]) -- each pair
+ *   optional -- by flags, one inclusive scan and a scatter.  d_count[0] = the survivors, also beyond capacity: then d_status[0] |= HNR_CLOUD_OVERFLOW
+ *   (the caller zeroes the word) and nothing is written at or past row `capacity`.  1 <= n <= 2^30, capacity >= 0;
+ *   d_scratch: hnr_visual_hull_select_scratch_bytes(n) bytes (negative: n outside the limits).
+ *
+ * hnr_point_occlusion -- the z-buffer test of `homo_warp_nongrid_occ` (models/mvs/mvs_utils.py:333-369) for the n points of ONE view (w2c [4,4], K
+ *   [3,3]: host floats).  cam, gx, gy and the frame mask 0 <= gx <= W-1 && 0 <= gy <= H-1 are those of hnr_point_view_attrs, bit for bit (the
+ *   reference's `ceil(gx) <= W-1` is the same test).  cell = ceil(gx) * H + ceil(gy), the reference's column-major index; zmin[cell] = the minimum of
+ *   cam[2] over the in-frame points of the cell (an integer atomicMin on an order-preserving key of the float: negative depths are legal, and the
+ *   result does not depend on the order of arrival);  d_visible [n] uint8 = in frame && cam[2] <= zmin[cell] + tolerate (one fp32 sum; the reference
+ *   passes tolerate = 0.1).  n > 0, 2 <= H, W <= 32768, H*W <= 2^24 (the reference forms the cell index in fp32), tolerate >= 0;
+ *   d_scratch: hnr_point_occlusion_scratch_bytes(H, W) bytes (negative: bad shape). */
+int hnr_alpha_pack(const float *d_alphas, int M, int H, int W, uint32_t *d_bits, void *stream);
+int64_t hnr_visual_hull_select_scratch_bytes(int64_t n);
+int hnr_visual_hull_select(const float *d_xyz, const float *d_conf, const int32_t *d_view, int64_t n, const uint32_t *d_alpha_bits, const float *d_cams,
+                           int M, int H, int W, const float *near_far, int range_mask, uint8_t *d_mask, float *d_out_xyz, float *d_out_conf,
+                           int32_t *d_out_view, int64_t capacity, int64_t *d_count, int32_t *d_status, void *d_scratch, int64_t scratch_bytes,
+                           void *stream);
+int64_t hnr_point_occlusion_scratch_bytes(int H, int W);
+int hnr_point_occlusion(const float *d_xyz, int64_t n, const float *w2c, const float *K, int H, int W, float tolerate, uint8_t *d_visible,
+                        void *d_scratch, int64_t scratch_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Depth maps from the pretrained MVSNet: the first stage of the `load_points=0`, `manual_depth_view=1` start of a scene (csrc/mvsnet.hip).  Replaces
