@@ -21,4 +21,10 @@ def __getattr__(name):
     if name in ("AlphaMasks", "alpha_masking", "visual_hull_select", "point_occlusion", "init_cloud_from_mvs_depth"):
         from . import cloud_init
         return getattr(cloud_init, name)
+    if name == "RAFT":
+        from . import flow
+        return flow.RAFT
+    if name in ("content_aware_weights", "weights_from_scores"):
+        from . import frame_weights
+        return getattr(frame_weights, name)
     raise AttributeError(name)

@@ -221,6 +221,23 @@ SIGNATURES = {
     "hnr_mvsnet_cost_reg": (_I, [_P, _I, _I, _I, _P, _P, _P, ctypes.c_int64, _P]),
     "hnr_mvsnet_depth_head": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "hnr_mvsnet_depth_points": (_I, [_P, _P, _I, _I, _I, _I, _F, _F, ctypes.POINTER(_F), _P, _P, _P, _P]),
+    # content-aware frame weights: RAFT flow (csrc/raft.hip) and blur scores (csrc/blur_score.hip)
+    "hnr_raft_encoder_packed_elems": (ctypes.c_int64, []),
+    "hnr_raft_update_packed_elems": (ctypes.c_int64, []),
+    "hnr_raft_encoder_scratch_elems": (ctypes.c_int64, [_I, _I, _I]),
+    "hnr_raft_encoder": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, ctypes.c_int64, _P]),
+    "hnr_raft_pyramid_elems": (ctypes.c_int64, [_I, _I]),
+    "hnr_raft_pyramid_scratch_elems": (ctypes.c_int64, [_I, _I]),
+    "hnr_raft_corr_pyramid": (_I, [_P, _P, _I, _I, _P, _P, ctypes.c_int64, _P]),
+    "hnr_raft_lookup": (_I, [_P, _P, _I, _I, _P, _P]),
+    "hnr_raft_update_scratch_elems": (ctypes.c_int64, [_I, _I]),
+    "hnr_raft_update": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P, ctypes.c_int64, _P]),
+    "hnr_raft_upsample": (_I, [_P, _P, _I, _I, _P, _P]),
+    "hnr_raft_flow_scratch_elems": (ctypes.c_int64, [_I, _I]),
+    "hnr_raft_flow": (_I, [_P, _P, _I, _I, _P, _P, _P, _I, _P, _P, _P, ctypes.c_int64, _P]),
+    "hnr_blur_edges": (_I, [_P, _I, _I, _I, _P, _P]),
+    "hnr_blur_score_pair_scratch_bytes": (ctypes.c_int64, [_I, _I]),
+    "hnr_blur_score_pair": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, ctypes.c_int64, _P]),
     # device-resident frame bank + batch sampler (csrc/frames.hip)
     "hnr_frame_batch_scratch_bytes": (ctypes.c_int64, [_I, _I]),
     "hnr_frame_batch": (_I, [ctypes.POINTER(FrameBankC), ctypes.POINTER(FrameBankC), _P, _I, ctypes.POINTER(FrameBatchParams), _P, _I, _P,

@@ -26,7 +26,8 @@
  *              hnr_frame_metrics* (and the HNR_FM_* row layout), hnr_depth_fuse*, hnr_range_crop*, hnr_nearest_view, hnr_point_view_attrs,
  *              hnr_featnet_*, hnr_point_embed*, hnr_geo_consistency, hnr_geo_filter_select*, hnr_mvsnet_*,
  *              hnr_alpha_pack, hnr_visual_hull_select*, hnr_point_occlusion*, hnr_point_view_attrs_vis,
- *              hnr_frame_batch*, hnr_frame_item, hnr_ray_miss_rank.
+ *              hnr_frame_batch*, hnr_frame_item, hnr_ray_miss_rank, hnr_raft_flow*, hnr_blur_score_pair* (hnr_blur_edges and the other hnr_raft_*
+ *              entries are STAGE).
  *   STAGE   -- everything else (hnr_chain_*, hnr_mlp3_*, hnr_merge*, hnr_mixup_stage, hnr_proj_*, hnr_h2*, hnr_linear_*, hnr_gather_*, hnr_ksum*,
  *              hnr_segment_*, hnr_absmax, hnr_div_probe, hnr_image_features_bwd_bbox, ...): the individual stages the two single-call entries are built from.  They are exported so
  *              that tests/ can compare every stage with the oracle and so that tools/ can time them alone; their signatures, workspace layouts and
@@ -1161,6 +1162,73 @@ int hnr_mvsnet_depth_head(const float *d_logits, const float *d_depth_values, in
                           void *stream);
 int hnr_mvsnet_depth_points(const float *d_depth, const float *d_conf, int h, int w, int H, int W, float near, float far, const float *Kt_inv,
                             float *d_cam_xyz, float *d_conf_out, uint8_t *d_mask, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Content-aware frame weights (`frame_weights_step5/<scene>_frame_weight_step5.npy`, read at data/scannet_ft_dataset.py:502): RAFT optical flow between
+ * consecutive training frames (csrc/raft.hip) and Laplacian-variance blur scores on the flow-aligned overlap (csrc/blur_score.hip).  Replaces
+ * raft/demo_content_aware_weights.py:78-184 with raft/core/raft.py, extractor.py, corr.py, update.py, utils/utils.py for the configuration that script
+ * runs: the basic model, fp32, eval, test_mode=True, flow_init=None, CorrBlock (radius 4, 4 levels).  Stream-ordered, nothing is allocated, nothing is
+ * read back, no float atomics, every sum in a fixed order: two runs give the same bits.  Maps are NCHW.  Every convolution is an implicit GEMM on the
+ * f32-input MFMA (a k-ordered fmaf chain per wave; four waves split the input channels of a tile and are added in wave order).
+ * Shapes: H, W multiples of 8, 128 .. 4096, h = H/8, w = W/8 with h*w <= 16384 (h, w >= 16: below it the coarsest correlation level has extent 1 and
+ * the reference divides by W-1 = 0).  HNR_ERR_BADARG, before any launch, for a NULL pointer, a shape outside these limits or a short scratch.
+ *
+ * Packed layer (whoever packs folds batch norms and constant factors): w [kh*kw][cinp][cout], cinp = cin rounded up to even (the added row zero),
+ *   then bias [cout].  hnr_raft_encoder_packed_elems(): conv1 (7x7, 3->64), then per residual block (64, 64, 96/2, 96, 128/2, 128) conv1, conv2 and, at
+ *   stride 2, downsample.0; then conv2 (1x1, 128->256).  hnr_raft_update_packed_elems(): encoder.convc1, convc2, convf1, convf2, conv;
+ *   gru.[convz1 | convr1] stacked along cout, convq1, [convz2 | convr2], convq2; flow_head.conv1, conv2; mask.0, 0.25 * mask.2.
+ *
+ * STAGE tier:
+ * hnr_raft_encoder -- `BasicEncoder` (extractor.py:118-192) on d_images [N,3,H,W] (N = 1 or 2; values 0..255: 2(x/255) - 1 is applied here) ->
+ *   d_out [N,256,h,w].  norm 0: InstanceNorm2d as constructed there (no affine, no running statistics, eps 1e-5, biased variance, per image and
+ *   channel; mean, then the squared deviations, each a strided per-thread sum and an LDS tree);  1: batch norm folded into the packed layers;
+ *   2: as 1, then tanh on channels 0..127 and relu on 128..255 (raft.py:111-114: net | inp).
+ * hnr_raft_corr_pyramid -- `CorrBlock.__init__` (corr.py:13-27, 53-60): level 0 [h*w][h][w] = fmap1^T fmap2 / 16, then three avg_pool2d(2, 2) (floor on
+ *   odd extents), the four levels one after another in d_pyramid [hnr_raft_pyramid_elems(h, w)].
+ * hnr_raft_lookup -- `CorrBlock.__call__` (corr.py:29-50) with utils.bilinear_sampler: d_coords [2,h,w] (x, y) -> d_corr [324,h,w]; window index (i, j),
+ *   i, j = 0..8: tap x = cx/2^l + (i-4), y = cy/2^l + (j-4) (the reference adds meshgrid(dy, dx) to (x, y)), channel l*81 + i*9 + j; the coordinate
+ *   goes through 2v/(W-1) - 1 and back ((g+1)/2)(W-1); bilinear with grid_sample's weight expressions, zero outside.
+ * hnr_raft_update -- one iteration of raft.py:122-131 with `BasicUpdateBlock` (update.py:79-136): lookup at d_coords, flow = coords - grid, motion
+ *   encoder, SepConvGRU (sigmoid, r*h, tanh and (1-z)h + zq in the convolutions' epilogues; h, inp and the motion features read in place), flow
+ *   head, d_coords += delta.  d_net [128,h,w] and d_coords [2,h,w] are updated in place; d_delta [2,h,w] (optional) receives delta_flow; d_mask
+ *   [576,h,w] (optional: NULL skips the mask head, which only the last iteration's up-sampling reads) receives 0.25 * mask(net).
+ * hnr_raft_upsample -- `upsample_flow` (raft.py:72-83): softmax over the 9 taps of d_mask [9][8][8][h][w], 3x3 unfold of 8 * d_flow [2,h,w] with zero
+ *   padding -> d_flow_up [2,8h,8w].
+ * hnr_blur_edges -- `detect_blurry` (demo_content_aware_weights.py:78-92) on P grey planes d_gray [P,H,W] uint8 -> d_edges [P,H,W] fp64:
+ *   cv2.blur(., (5, 5)) = the 25 taps (an exact integer) * (1/25), then cv2.Laplacian(., CV_64F) = aperture [[0,1,0],[1,-4,1],[0,1,0]], summed
+ *   ((up + left) + right) + down - 4 centre; BORDER_REFLECT_101 for both, as OpenCV documents them.  8 <= H, W <= 16384.
+ *
+ * STABLE tier:
+ * hnr_raft_flow -- `RAFT.forward(image1, image2, iters, test_mode=True)`: d_image1 [2,3,H,W] holds both images (d_image2 = d_image1 + 3*H*W),
+ *   d_fnet / d_cnet / d_update the packed images above -> d_flow_low [2,h,w] = coords1 - coords0, d_flow_up [2,H,W].  1 <= iters <= 1024.
+ * hnr_blur_score_pair -- demo_content_aware_weights.py:147-184 for one pair: d_edge1, d_edge2 [H,W] fp64, d_flow [2,H,W] (flow_up) -> d_row [3] fp64
+ *   = (population variance of edge 1, of the warped edge 2, used-pixel count).  Warp: `warp(., flow, mode='nearest')` as torch evaluates it, in
+ *   separately rounded fp32 operations: v = x + fx;  g = 2 v / max(W-1, 1) - 1;  i = ((g + 1) W - 1) / 2 (grid_sample without align_corners);
+ *   round half to even; outside the frame: 0.  Edge 2 is rounded to fp32 before the warp, as the script does.  A pixel is used where it lies inside
+ *   the frame minus `border` pixels on every side and its pick does too.  Sums in fp64: mean first, then squared deviations.  A count of 0 gives the
+ *   row (0, 0, 0).  d_pick [H,W] int32 (optional): the picked pixel's index or -1;  d_used [H,W] uint8 (optional).  d_scratch: 8-byte aligned,
+ *   hnr_blur_score_pair_scratch_bytes(H, W).  0 <= 2*border < min(H, W). */
+int64_t hnr_raft_encoder_packed_elems(void);
+int64_t hnr_raft_update_packed_elems(void);
+int64_t hnr_raft_encoder_scratch_elems(int N, int H, int W);
+int hnr_raft_encoder(const float *d_images, int N, int H, int W, const float *d_packed, int norm, float *d_out, float *d_scratch, int64_t scratch_elems,
+                     void *stream);
+int64_t hnr_raft_pyramid_elems(int h, int w);
+int64_t hnr_raft_pyramid_scratch_elems(int h, int w);
+int hnr_raft_corr_pyramid(const float *d_fmap1, const float *d_fmap2, int h, int w, float *d_pyramid, float *d_scratch, int64_t scratch_elems,
+                          void *stream);
+int hnr_raft_lookup(const float *d_pyramid, const float *d_coords, int h, int w, float *d_corr, void *stream);
+int64_t hnr_raft_update_scratch_elems(int h, int w);
+int hnr_raft_update(const float *d_packed, const float *d_pyramid, float *d_net, const float *d_inp, float *d_coords, int h, int w, float *d_delta,
+                    float *d_mask, float *d_scratch, int64_t scratch_elems, void *stream);
+int hnr_raft_upsample(const float *d_flow, const float *d_mask, int h, int w, float *d_flow_up, void *stream);
+int64_t hnr_raft_flow_scratch_elems(int H, int W);
+int hnr_raft_flow(const float *d_image1, const float *d_image2, int H, int W, const float *d_fnet, const float *d_cnet, const float *d_update, int iters,
+                  float *d_flow_low, float *d_flow_up, float *d_scratch, int64_t scratch_elems, void *stream);
+int hnr_blur_edges(const uint8_t *d_gray, int P, int H, int W, double *d_edges, void *stream);
+int64_t hnr_blur_score_pair_scratch_bytes(int H, int W);
+int hnr_blur_score_pair(const double *d_edge1, const double *d_edge2, const float *d_flow, int H, int W, int border, double *d_row, int32_t *d_pick,
+                        uint8_t *d_used, void *d_scratch, int64_t scratch_bytes, void *stream);
 
 #ifdef __cplusplus
 }
