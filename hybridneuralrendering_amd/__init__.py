@@ -24,6 +24,9 @@ def __getattr__(name):
     if name == "RAFT":
         from . import flow
         return flow.RAFT
+    if name == "LPIPS":
+        from . import perceptual
+        return perceptual.LPIPS
     if name in ("content_aware_weights", "weights_from_scores"):
         from . import frame_weights
         return getattr(frame_weights, name)

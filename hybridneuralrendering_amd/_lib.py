@@ -238,6 +238,16 @@ SIGNATURES = {
     "hnr_blur_edges": (_I, [_P, _I, _I, _I, _P, _P]),
     "hnr_blur_score_pair_scratch_bytes": (ctypes.c_int64, [_I, _I]),
     "hnr_blur_score_pair": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, ctypes.c_int64, _P]),
+    # LPIPS with the AlexNet and VGG-16 backbones (csrc/lpips.hip)
+    "hnr_lpips_packed_elems": (ctypes.c_int64, [_I]),
+    "hnr_lpips_scratch_bytes": (ctypes.c_int64, [_I, _I, _I]),
+    "hnr_lpips_tap_dims": (_I, [_I, _I, _I, ctypes.POINTER(_I)]),
+    "hnr_lpips_prepare": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
+    "hnr_lpips_prepare_f32": (_I, [_P, _P, _I, _I, _P, _P, _P]),
+    "hnr_lpips_features": (_I, [_I, _P, _I, _I, _P, ctypes.POINTER(_P), _P, ctypes.c_int64, _P]),
+    "hnr_lpips_score": (_I, [_I, ctypes.POINTER(_P), _I, _I, _P, _P, _P, ctypes.c_int64, _P]),
+    "hnr_lpips": (_I, [_I, _P, _P, _I, _I, _I, _P, _P, _P, ctypes.c_int64, _P]),
+    "hnr_lpips_f32": (_I, [_I, _P, _P, _I, _I, _P, _P, _P, ctypes.c_int64, _P]),
     # device-resident frame bank + batch sampler (csrc/frames.hip)
     "hnr_frame_batch_scratch_bytes": (ctypes.c_int64, [_I, _I]),
     "hnr_frame_batch": (_I, [ctypes.POINTER(FrameBankC), ctypes.POINTER(FrameBankC), _P, _I, ctypes.POINTER(FrameBatchParams), _P, _I, _P,

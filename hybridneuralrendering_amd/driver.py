@@ -81,11 +81,14 @@ def render_image(renderer, cloud, frame, chunk_rays=0, sharded=None, group=None,
     return res
 
 
-def evaluate_frames(renderer, cloud, frames, evaluator=None, win=11, data_range=2.0, save_images=False, chunk_rays=0, sharded=None, group=None, on_frame=None):
+def evaluate_frames(renderer, cloud, frames, evaluator=None, win=11, data_range=2.0, save_images=False, chunk_rays=0, sharded=None, group=None, on_frame=None,
+                    lpips=None):
     """The reference's test pass over a test set (run/test_ft.py:127-260): render_image + one metrics row per frame (metrics.TestSetEvaluator.add:
     one launch behind the composite, no host read), frames being dataset items with gt_image [R,3].  Returns the evaluator -- summary() is
     the one host read, write(out_dir) leaves report_metrics' files -- on rank 0 when sharded, None on the other ranks.  render_image is called
-    as it stands: the rendered frames are what a plain call gives; on_frame(index, render_out), when given, sees each of them (rank 0)."""
+    as it stands: the rendered frames are what a plain call gives; on_frame(index, render_out), when given, sees each of them (rank 0).
+    lpips: a dict such as {"lpips": LPIPS('alex'), "vgglpips": LPIPS('vgg')} (perceptual.LPIPS with weights loaded) adds those columns
+    (TestSetEvaluator(lpips=...)); the rendered frame and the existing columns do not change."""
     from .metrics import TestSetEvaluator
     frames = list(frames)
     for i, frame in enumerate(frames):
@@ -95,6 +98,6 @@ def evaluate_frames(renderer, cloud, frames, evaluator=None, win=11, data_range=
         if on_frame is not None:
             on_frame(i, out)
         if evaluator is None:
-            evaluator = TestSetEvaluator(len(frames), win=win, data_range=data_range, device=out["image"].device, save_images=save_images)
+            evaluator = TestSetEvaluator(len(frames), win=win, data_range=data_range, device=out["image"].device, save_images=save_images, lpips=lpips)
         evaluator.add(out, frame)
     return evaluator

@@ -8,7 +8,11 @@ composite (csrc/metrics.hip) that leaves one fp64 row in a device table; the tab
 
 SSIM's `data_range`: the reference hands float images to scikit-image without a data_range, and scikit-image then uses the dtype range
 of floats (-1..1, L = 2), so the SSIM the reference publishes is the L = 2 value; that is the default here.  L = 1 is the textbook
-value for images in [0, 1].  LPIPS is not computed (it needs network weights this package does not ship).
+value for images in [0, 1].
+
+LPIPS: the reference's other two columns (`lpips`, `vgglpips`) come from perceptual.LPIPS, which runs the pretrained AlexNet / VGG-16 the user
+supplies (the package ships no weights).  `TestSetEvaluator(..., lpips={"lpips": LPIPS('alex'), "vgglpips": LPIPS('vgg')})` scores the 8-bit images
+hnr_frame_metrics leaves on the device into a second device table per key; without `lpips` nothing changes.
 """
 import os
 
@@ -104,11 +108,15 @@ class TestSetEvaluator:
     """A [capacity, NCOLS] device table of per-frame rows: add() per frame (no host synchronisation), summary() = the one host read.
 
     write(out_dir) leaves psnr.txt / ssim.txt / rmse.txt (np.savetxt) and scores.txt ("key: %.6f" lines) exactly as report_metrics does
-    (run/evaluate.py:89-97); with save_images=True also step-%04d-coarse_raycolor.png / step-%04d-gt_image.png from the kernel's own
+    (run/evaluate.py:89-97).  lpips: a dict key -> perceptual.LPIPS (the reference's keys are "lpips" for alex and "vgglpips" for vgg): add() also
+    fills row n of a [capacity, 6] table per key (d, r_0 .. r_4), summary() gains the keys, write() leaves <key>.txt and lists the metrics in
+    evaluate.py's order (psnr, ssim, lpips, vgglpips, rmse).  With save_images=True also step-%04d-coarse_raycolor.png / step-%04d-gt_image.png from the kernel's own
     uint8 images, so the reference's run/evaluate.py can be pointed at the same folder."""
     __test__ = False            # (not a pytest class, whatever its name starts with)
 
-    def __init__(self, capacity, win=11, data_range=2.0, device="cuda:0", save_images=False):
+    ORDER = ("psnr", "ssim", "lpips", "vgglpips", "rmse")          # report_metrics' order; other lpips keys follow "vgglpips"
+
+    def __init__(self, capacity, win=11, data_range=2.0, device="cuda:0", save_images=False, lpips=None):
         if capacity <= 0:
             raise HnrError("TestSetEvaluator: capacity must be positive")
         self.capacity, self.win, self.data_range, self.save_images = int(capacity), int(win), float(data_range), bool(save_images)
@@ -116,16 +124,31 @@ class TestSetEvaluator:
         self.n = 0
         self.img8 = self.gt8 = None          # [capacity, h, w, 3] uint8, allocated by the first add()
         self._host = None
+        self.lpips = dict(lpips) if lpips else {}
+        for key in self.lpips:
+            if key in ("psnr", "ssim", "rmse", "mean") or not isinstance(key, str):
+                raise HnrError("TestSetEvaluator: %r cannot name an lpips column" % (key,))
+        self.lpips_tables = {k: torch.zeros((self.capacity, 6), dtype=torch.float64, device=device) for k in self.lpips}
+        self._pair8 = None                   # the scratch pair of add() when lpips is on and save_images off
+        self._lpips_host = None
 
     @classmethod
-    def from_rows(cls, rows, img8=None, gt8=None, win=11, data_range=2.0):
-        """An evaluator over rows computed elsewhere (another rank's table, an earlier run): summary() / write() only."""
+    def from_rows(cls, rows, img8=None, gt8=None, win=11, data_range=2.0, lpips_rows=None):
+        """An evaluator over rows computed elsewhere (another rank's table, an earlier run): summary() / write() only.  lpips_rows: key -> [n, 6]
+        rows of the lpips tables."""
         rows = torch.as_tensor(np.asarray(rows, dtype=np.float64).reshape(-1, NCOLS))
         ev = cls(max(int(rows.shape[0]), 1), win=win, data_range=data_range, device=rows.device, save_images=img8 is not None)
         ev.table[:rows.shape[0]] = rows
         ev.n = int(rows.shape[0])
         if img8 is not None:
             ev.img8, ev.gt8 = torch.as_tensor(img8), torch.as_tensor(gt8)
+        for key, lr in (lpips_rows or {}).items():
+            lr = torch.as_tensor(np.asarray(lr, dtype=np.float64).reshape(-1, 6))
+            if lr.shape[0] != ev.n:
+                raise HnrError("TestSetEvaluator.from_rows: %d rows of %s for %d frames" % (lr.shape[0], key, ev.n))
+            ev.lpips[key] = None
+            ev.lpips_tables[key] = torch.zeros((ev.capacity, 6), dtype=torch.float64)
+            ev.lpips_tables[key][:ev.n] = lr
         return ev
 
     def add(self, render_out, frame):
@@ -141,9 +164,19 @@ class TestSetEvaluator:
             if tuple(self.img8.shape[1:3]) != (h, w):
                 raise HnrError("TestSetEvaluator: save_images needs frames of one size")
             pair = (self.img8[self.n], self.gt8[self.n])
+        elif self.lpips:
+            h, w = int(frame["h"]), int(frame["w"])
+            if self._pair8 is None or tuple(self._pair8[0].shape[:2]) != (h, w):
+                dev = render_out["image"].device
+                self._pair8 = tuple(torch.zeros((h, w, 3), dtype=torch.uint8, device=dev) for _ in range(2))
+            pair = self._pair8
         frame_metrics(render_out, frame, win=self.win, data_range=self.data_range, out=self.table, row=self.n, images8=pair)
+        for key, model in self.lpips.items():
+            if model is None:
+                raise HnrError("TestSetEvaluator: %s has rows but no model (from_rows): add() is not available" % key)
+            model.pair8(pair[0], pair[1], out=self.lpips_tables[key], row=self.n)
         self.n += 1
-        self._host = None
+        self._host = self._lpips_host = None
         return self.n - 1
 
     def summary(self):
@@ -151,8 +184,14 @@ class TestSetEvaluator:
         if self._host is None:
             self._host = self.table[:self.n].cpu().numpy()
         res = derive(self._host)
+        if self.lpips_tables:
+            if self._lpips_host is None:
+                self._lpips_host = {k: t[:self.n].cpu().numpy() for k, t in self.lpips_tables.items()}
+            for k, rows in self._lpips_host.items():
+                res[k] = rows[:, 0].copy()
+                res[k + "_layers"] = rows[:, 1:].copy()
         with np.errstate(invalid="ignore"):
-            res["mean"] = {k: (float(np.mean(v)) if len(v) else float("nan")) for k, v in res.items()}
+            res["mean"] = {k: (float(np.mean(v)) if len(v) else float("nan")) for k, v in res.items() if not k.endswith("_layers")}
         return res
 
     def write(self, out_dir, ids=None):
@@ -160,7 +199,10 @@ class TestSetEvaluator:
         res = self.summary()
         os.makedirs(out_dir, exist_ok=True)
         text = ""
-        for key in ("psnr", "ssim", "rmse"):
+        keys = [k for k in self.ORDER if k in ("psnr", "ssim", "rmse") or k in self.lpips_tables]
+        extra = [k for k in self.lpips_tables if k not in keys]
+        at = keys.index("rmse")
+        for key in keys[:at] + extra + keys[at:]:
             np.savetxt(os.path.join(out_dir, key + ".txt"), res[key].reshape(-1))
             text += key + ": %.6f\n" % np.mean(res[key])
         with open(os.path.join(out_dir, "scores.txt"), "w") as f:

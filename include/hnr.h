@@ -1230,6 +1230,51 @@ int64_t hnr_blur_score_pair_scratch_bytes(int H, int W);
 int hnr_blur_score_pair(const double *d_edge1, const double *d_edge2, const float *d_flow, int H, int W, int border, double *d_row, int32_t *d_pick,
                         uint8_t *d_used, void *d_scratch, int64_t scratch_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * LPIPS v0.1 with the AlexNet and the VGG-16 backbone (csrc/lpips.hip): the `lpips` and `vgglpips` columns of report_metrics (run/evaluate.py:41-75,
+ * called at run/test_ft.py:260 and run/train_ft.py:437).  Replaces `lpips.LPIPS(net=..., version='0.1')` in eval mode with the package's defaults
+ * (lpips=True, spatial=False) and torchvision's `alexnet().features` / `vgg16().features[0:30]`, which evaluate.py runs on PNGs it reads back from
+ * disk.  fp32, inference only.  Stream-ordered, nothing is allocated, nothing is read back, no float atomics, every sum in a fixed order: two runs
+ * give the same bits.  net: 0 alex, 1 vgg.  Sizes: alex 31 <= h, w <= 4096, vgg 16 <= h, w <= 4096 (below the minimum the last tap has no pixel).
+ * HNR_ERR_BADARG, before any launch, for an unknown net, a NULL pointer, a size outside these limits, a d_packed or d_scratch that is not 16-byte
+ * aligned, or a short scratch.
+ *
+ * d_packed [hnr_lpips_packed_elems(net)] floats: ScalingLayer shift [3], scale [3], two zeros; the convolutions in network order, each
+ *   w [k*k][cinp][cout] (cinp = cin rounded up to even, the added row zero) then bias [cout]; then the five `lin` layers, [C_k] each.
+ *   alex: 3->64 k11 s4 p2 | 64->192 k5 p2 | 192->384 k3 p1 | 384->256 k3 p1 | 256->256 k3 p1, a 3x3/s2 max-pool after the first two; taps after each ReLU.
+ *   vgg: thirteen k3 p1 layers 64 64 | 128 128 | 256 256 256 | 512 512 512 | 512 512 512, a 2x2/s2 max-pool between the blocks; taps relu1_2 .. relu5_3.
+ * d_scratch: hnr_lpips_scratch_bytes(net, h, w) bytes (negative: bad net or size), the same for every entry below.
+ *
+ * STAGE tier:
+ * hnr_lpips_tap_dims -- dims [5][3] (host) = (C_k, h_k, w_k) of the five taps.
+ * hnr_lpips_prepare -- what evaluate.py feeds the network: two [h,w,3] uint8 RGB images -> d_x [2,3,h,w]; per channel float32(b) / 255.0, * 2 - 1.0,
+ *   then the ScalingLayer (x - shift) / scale: four separately rounded fp32 operations (a 256-entry table per channel).  bgr != 0: network channel c
+ *   reads byte 2 - c (cv2.imread hands evaluate.py BGR and nothing converts it: the published numbers are these).  hnr_lpips_prepare_f32: two float
+ *   [3,h,w] images in [-1, 1], channels as given -> the ScalingLayer alone (the package's forward(in0, in1)).
+ * hnr_lpips_features -- d_x -> the five taps, d_taps: host array of five device pointers, tap k [2,C_k,h_k,w_k].  Convolution + bias + ReLU is an
+ *   implicit GEMM on the f32-input MFMA: one k-ordered chain per output element (input-channel chunk, tap, channel pair), no split sums.
+ * hnr_lpips_score -- the five taps -> d_row [6] fp64 = (d, r_0 .. r_4): per pixel n = sqrt(sum_c f^2), g = f / (n + 1e-10),
+ *   s = sum_c lin_k[c] (g0 - g1)^2, every term the package's fp32 expression (not the expanded form), the sums over c and the mean r_k of s over
+ *   the pixels collected in fp64 in a fixed order; d = sum_k r_k.
+ *   Identical taps give exactly 0; a pixel whose features are all zero contributes 0.
+ *
+ * STABLE tier:
+ * hnr_lpips -- prepare, features, score for one pair of 8-bit images (those hnr_frame_metrics leaves) -> d_row [6] fp64.  hnr_lpips_f32: the same
+ *   from float images. */
+int64_t hnr_lpips_packed_elems(int net);
+int64_t hnr_lpips_scratch_bytes(int net, int h, int w);
+int hnr_lpips_tap_dims(int net, int h, int w, int *dims);
+int hnr_lpips_prepare(const uint8_t *d_img8, const uint8_t *d_gt8, int h, int w, int bgr, const float *d_packed, float *d_x, void *stream);
+int hnr_lpips_prepare_f32(const float *d_in0, const float *d_in1, int h, int w, const float *d_packed, float *d_x, void *stream);
+int hnr_lpips_features(int net, const float *d_x, int h, int w, const float *d_packed, float *const *d_taps, void *d_scratch, int64_t scratch_bytes,
+                       void *stream);
+int hnr_lpips_score(int net, const float *const *d_taps, int h, int w, const float *d_packed, double *d_row, void *d_scratch, int64_t scratch_bytes,
+                    void *stream);
+int hnr_lpips(int net, const uint8_t *d_img8, const uint8_t *d_gt8, int h, int w, int bgr, const float *d_packed, double *d_row, void *d_scratch,
+              int64_t scratch_bytes, void *stream);
+int hnr_lpips_f32(int net, const float *d_in0, const float *d_in1, int h, int w, const float *d_packed, double *d_row, void *d_scratch,
+                  int64_t scratch_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
