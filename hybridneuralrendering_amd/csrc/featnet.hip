@@ -3,112 +3,23 @@
 // run/train_ft.py:759-760 for `load_points=2`.  Inference only: no backward.
 //
 //   hnr_featnet_forward  eight 3x3 / 5x5 convolutions, each followed by the activated batch norm in inference form, + the 1x1 `toplayer`:
-//                        direct convolution in fp32, one output pixel per thread, COG output channels of it in registers, the input tile with its halo
-//                        staged in LDS eight input channels at a time, the weights read through wave-uniform addresses (scalar loads), the
-//                        norm + LeakyReLU epilogue and the toplayer fused.  Every sum is one chain of explicit fmaf in (input channel, ky, kx) order:
-//                        two runs give the same bits.
+//                        conv2d_direct_kernel (conv_direct.h) with the norm + LeakyReLU epilogue, the toplayer fused into the last layer's.
+//                        Every sum is one chain of explicit fmaf in (input channel, ky, kx) order: two runs give the same bits.
 //   hnr_point_embed      one view, one launch, one point per thread: projection, mask, direction and bilinear samples by the device functions of
 //                        hnr_point_view_attrs (view_attrs.h), then premlp (63 -> 32 -> 32, LeakyReLU 0.01) with its weights in LDS.
-#include "hnr_launch.h"
+#include "conv_direct.h"
 #include "view_attrs.h"
 
 namespace hnr {
 
-constexpr int FN_TW = 32, FN_TH = 8;            // output tile of one block: one pixel per thread, a wave covers two rows of 32
-constexpr int FN_CCH = 8;                       // input channels staged per round
-constexpr int FN_LAYERS = 8;
+// the packed parameters: the eight layers, each w, mean, mul, bias, then the toplayer (w [32][32], bias [32])
+constexpr int FN_TOP = conv2d_offset(CONV2D_LAYERS, 3);
+static_assert(FN_TOP + 32 * 32 + 32 == HNR_FEATNET_PACKED_ELEMS, "include/hnr.h: HNR_FEATNET_PACKED_ELEMS");
 
-struct FnLayer { int cin, cout, ks, stride; };
-constexpr FnLayer FN_LAYER[FN_LAYERS] = {{3, 8, 3, 1}, {8, 8, 3, 1}, {8, 16, 5, 2}, {16, 16, 3, 1}, {16, 16, 3, 1}, {16, 32, 5, 2}, {32, 32, 3, 1}, {32, 32, 3, 1}};
-
-// offset of layer l in the packed parameters (l = FN_LAYERS: the toplayer): per layer w [cin][ks][ks][cout], mean [cout], mul [cout], bias [cout]
-constexpr int fn_offset(int l)
-{
-    int o = 0;
-    for (int i = 0; i < l; ++i) o += FN_LAYER[i].cin * FN_LAYER[i].ks * FN_LAYER[i].ks * FN_LAYER[i].cout + 3 * FN_LAYER[i].cout;
-    return o;
-}
-static_assert(fn_offset(FN_LAYERS) + 32 * 32 + 32 == HNR_FEATNET_PACKED_ELEMS, "include/hnr.h: HNR_FEATNET_PACKED_ELEMS");
-
-template <int CIN, int KS, int STRIDE>
-constexpr int fn_lds_bytes()
-{
-    return (CIN < FN_CCH ? CIN : FN_CCH) * ((FN_TH - 1) * STRIDE + KS) * ((FN_TW - 1) * STRIDE + KS) * (int)sizeof(float);
-}
-
-// in [V,CIN,Hi,Wi] -> out [V,COUT,Ho,Wo]; blockIdx.z = view * (COUT / COG) + channel group.  TOP: the 1x1 toplayer (top = w [co][ci], bias [co]) is
-// applied to the COG = COUT activated channels of the pixel before the store.
-template <int CIN, int COUT, int KS, int STRIDE, int COG, bool TOP>
-__global__ void __launch_bounds__(256) featnet_conv_kernel(const float *__restrict__ in, int Hi, int Wi, int Ho, int Wo, const float *__restrict__ prm,
-                                                           const float *__restrict__ top, float *__restrict__ out)
-{
-    extern __shared__ float fn_tile[];
-    constexpr int PAD = KS / 2, IW = (FN_TW - 1) * STRIDE + KS, IH = (FN_TH - 1) * STRIDE + KS, CCH = CIN < FN_CCH ? CIN : FN_CCH, GROUPS = COUT / COG;
-    static_assert(CIN % CCH == 0 && COUT % COG == 0 && (!TOP || COG == COUT), "featnet_conv_kernel: channel split");
-    const int tx = threadIdx.x & (FN_TW - 1), ty = threadIdx.x / FN_TW;
-    const int g = blockIdx.z % GROUPS, v = blockIdx.z / GROUPS;
-    const int ox0 = blockIdx.x * FN_TW, oy0 = blockIdx.y * FN_TH;
-    const int ix0 = ox0 * STRIDE - PAD, iy0 = oy0 * STRIDE - PAD;
-    const float *inv = in + (size_t)v * CIN * Hi * Wi;
-    float acc[COG];
-#pragma unroll
-    for (int j = 0; j < COG; ++j) acc[j] = 0.f;
-    for (int c0 = 0; c0 < CIN; c0 += CCH) {
-        __syncthreads();                                                // the previous round's reads are done
-        for (int e = threadIdx.x; e < CCH * IH * IW; e += 256) {
-            const int ch = e / (IH * IW), r = e - ch * (IH * IW), yy = r / IW, xx = r - yy * IW;
-            const int iy = iy0 + yy, ix = ix0 + xx;
-            fn_tile[e] = (iy >= 0 && iy < Hi && ix >= 0 && ix < Wi) ? inv[((size_t)(c0 + ch) * Hi + iy) * Wi + ix] : 0.f;          // zero padding
-        }
-        __syncthreads();
-        const float *t0 = fn_tile + (ty * STRIDE) * IW + tx * STRIDE;
-#pragma unroll 1
-        for (int ch = 0; ch < CCH; ++ch) {
-            const float *t = t0 + ch * (IH * IW);
-            const float *w = prm + (size_t)((c0 + ch) * KS * KS) * COUT + g * COG;          // the same address in every lane
-#pragma unroll
-            for (int ky = 0; ky < KS; ++ky) {
-#pragma unroll
-                for (int kx = 0; kx < KS; ++kx) {
-                    const float a = t[ky * IW + kx];
-#pragma unroll
-                    for (int j = 0; j < COG; ++j) acc[j] = fmaf(a, w[(ky * KS + kx) * COUT + j], acc[j]);
-                }
-            }
-        }
-    }
-    const float *mean = prm + CIN * KS * KS * COUT + g * COG, *mul = mean + COUT, *bias = mul + COUT;
-    float y[COG];
-#pragma unroll
-    for (int j = 0; j < COG; ++j) {
-        const float u = (acc[j] - mean[j]) * mul[j] + bias[j];
-        y[j] = u >= 0.f ? u : u * 0.01f;
-    }
-    const int ox = ox0 + tx, oy = oy0 + ty;
-    if (ox >= Wo || oy >= Ho) return;
-    const size_t plane = (size_t)Ho * Wo;
-    float *o = out + ((size_t)v * COUT + g * COG) * plane + (size_t)oy * Wo + ox;
-    if (!TOP) {
-#pragma unroll
-        for (int j = 0; j < COG; ++j) o[j * plane] = y[j];
-    } else {
-#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
-        for (int co = 0; co < COUT; ++co) {                             // (one output at a time: the loop vectoriser would pair them into packed fp32)
-            float s = 0.f;
-#pragma unroll
-            for (int ci = 0; ci < COG; ++ci) s = fmaf(y[ci], top[co * COG + ci], s);
-            o[co * plane] = s + top[COUT * COUT + co];
-        }
-    }
-}
-
-template <int L, int COG, bool TOP>
+template <int L, int COG, bool TOP = false>
 static int fn_launch(const float *in, int V, int Hi, int Wi, int Ho, int Wo, const float *packed, float *out, hipStream_t st)
 {
-    constexpr FnLayer P = FN_LAYER[L];
-    const dim3 grid(cdiv(Wo, FN_TW), cdiv(Ho, FN_TH), V * (P.cout / COG));
-    return launch_lds<featnet_conv_kernel<P.cin, P.cout, P.ks, P.stride, COG, TOP>>(grid, dim3(256), fn_lds_bytes<P.cin, P.ks, P.stride>(), st, in, Hi, Wi, Ho, Wo,
-                                                                                   packed + fn_offset(L), packed + fn_offset(FN_LAYERS), out);
+    return conv2d_direct_launch<L, COG, EpiAbnLeaky<TOP>, const float *__restrict__>(in, V, Hi, Wi, Ho, Wo, packed + conv2d_offset(L, 3), out, st, packed + FN_TOP);
 }
 
 constexpr int PE_IN = 63, PE_OUT = 32;
@@ -197,10 +108,10 @@ using namespace hnr;
 extern "C" int64_t hnr_featnet_scratch_elems(int V, int H, int W)
 {
     if (!fn_shape_ok(V, H, W)) return -1;
-    const int64_t H2 = (H - 1) / 2 + 1, W2 = (W - 1) / 2 + 1, H4 = (H2 - 1) / 2 + 1, W4 = (W2 - 1) / 2 + 1;
+    const Pyramid p = pyramid_extents(H, W);
     int64_t m = 8 * (int64_t)H * W;
-    if (32 * H2 * W2 > m) m = 32 * H2 * W2;
-    if (64 * H4 * W4 > m) m = 64 * H4 * W4;
+    if (32 * (int64_t)p.H2 * p.W2 > m) m = 32 * (int64_t)p.H2 * p.W2;
+    if (64 * (int64_t)p.H4 * p.W4 > m) m = 64 * (int64_t)p.H4 * p.W4;
     return m * V;
 }
 
@@ -211,16 +122,16 @@ extern "C" int hnr_featnet_forward(const float *d_images, int V, int H, int W, c
     if (!fn_shape_ok(V, H, W)) { set_error("hnr_featnet_forward: bad argument (1 <= V <= 4096, 4 <= H, W <= 32768)"); return HNR_ERR_BADARG; }
     if (scratch_elems < hnr_featnet_scratch_elems(V, H, W)) { set_error("hnr_featnet_forward: scratch smaller than hnr_featnet_scratch_elems(V, H, W)"); return HNR_ERR_BADARG; }
     hipStream_t st = (hipStream_t)stream;
-    const int H2 = (H - 1) / 2 + 1, W2 = (W - 1) / 2 + 1, H4 = (H2 - 1) / 2 + 1, W4 = (W2 - 1) / 2 + 1;
+    const auto [H2, W2, H4, W4] = pyramid_extents(H, W);
     float *a = d_scratch, *b = d_scratch + (size_t)V * 16 * H2 * W2, *c = d_scratch + (size_t)V * 32 * H4 * W4;
-    if (int rc = fn_launch<0, 8, false>(d_images, V, H, W, H, W, d_packed, a, st)) return rc;             // conv0
-    if (int rc = fn_launch<1, 8, false>(a, V, H, W, H, W, d_packed, d_x1, st)) return rc;
-    if (int rc = fn_launch<2, 16, false>(d_x1, V, H, W, H2, W2, d_packed, a, st)) return rc;              // conv1
-    if (int rc = fn_launch<3, 16, false>(a, V, H2, W2, H2, W2, d_packed, b, st)) return rc;
-    if (int rc = fn_launch<4, 16, false>(b, V, H2, W2, H2, W2, d_packed, d_x2, st)) return rc;
-    if (int rc = fn_launch<5, 16, false>(d_x2, V, H2, W2, H4, W4, d_packed, a, st)) return rc;            // conv2
-    if (int rc = fn_launch<6, 16, false>(a, V, H4, W4, H4, W4, d_packed, c, st)) return rc;
-    return fn_launch<7, 32, true>(c, V, H4, W4, H4, W4, d_packed, d_x3, st);                               // + toplayer
+    if (int rc = fn_launch<0, 8>(d_images, V, H, W, H, W, d_packed, a, st)) return rc;                    // conv0
+    if (int rc = fn_launch<1, 8>(a, V, H, W, H, W, d_packed, d_x1, st)) return rc;
+    if (int rc = fn_launch<2, 16>(d_x1, V, H, W, H2, W2, d_packed, a, st)) return rc;                     // conv1
+    if (int rc = fn_launch<3, 16>(a, V, H2, W2, H2, W2, d_packed, b, st)) return rc;
+    if (int rc = fn_launch<4, 16>(b, V, H2, W2, H2, W2, d_packed, d_x2, st)) return rc;
+    if (int rc = fn_launch<5, 16>(d_x2, V, H2, W2, H4, W4, d_packed, a, st)) return rc;                   // conv2
+    if (int rc = fn_launch<6, 16>(a, V, H4, W4, H4, W4, d_packed, c, st)) return rc;
+    return fn_launch<7, 32, true>(c, V, H4, W4, H4, W4, d_packed, d_x3, st);                              // + toplayer
 }
 
 extern "C" int hnr_point_embed(const float *d_xyz, int64_t n, const float *w2c, const float *c2w, const float *cam_pos_cam, const float *K, int H, int W,
@@ -249,7 +160,7 @@ extern "C" int hnr_point_embed_vis(const float *d_xyz, int64_t n, const float *w
     }
     ViewCam vc;
     view_cam_fill(vc, w2c, c2w, cam_pos_cam, K);
-    const int H2 = (H - 1) / 2 + 1, W2 = (W - 1) / 2 + 1, H4 = (H2 - 1) / 2 + 1, W4 = (W2 - 1) / 2 + 1;
+    const auto [H2, W2, H4, W4] = pyramid_extents(H, W);
     point_embed_kernel<<<cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(d_xyz, (long long)n, vc, H, W, d_image, d_x1, d_x2, d_x3, H2, W2, H4, W4, d_premlp, d_emb,
                                                                       d_color, d_dir, d_row, d_conf, d_visible);
     HNR_LAUNCH_CHECK();

@@ -16,12 +16,11 @@
 // Tap score: one thread per pixel, lanes along pixels; the two channel norms first, then sum_c lin[c] (f0/(n0+eps) - f1/(n1+eps))^2 in the
 //   package's form (never the expanded one, which cancels for close images), fp32 terms collected in fp64; per-pixel values are summed in fp64:
 //   per workgroup (64 pixels) in pixel order, then per tap by strided sums and a tree, both in a fixed order.
+#include "conv_mfma.h"
 #include "hnr_launch.h"
 
 namespace hnr {
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 enum { NET_ALEX = 0, NET_VGG = 1 };
 constexpr int HEADER = 8;                        // shift [3], scale [3], two zeros: keeps every layer's weights 16-byte aligned
@@ -35,13 +34,11 @@ const int VGG_CH[13][2] = {{3, 64}, {64, 64}, {64, 128}, {128, 128}, {128, 256},
 const int VGG_TAP_AFTER[5] = {1, 3, 6, 9, 12};  // index of the convolution whose ReLU is tap k
 const int TAP_CH[2][5] = {{64, 192, 384, 256, 256}, {64, 128, 256, 512, 512}};
 
-int64_t layer_elems(int cin, int cout, int k) { return (int64_t)k * k * ((cin + 1) & ~1) * cout + cout; }
-
 int64_t packed_elems(int net)
 {
     int64_t n = HEADER;
-    if (net == NET_ALEX) for (int i = 0; i < 5; ++i) n += layer_elems(ALEX[i].cin, ALEX[i].cout, ALEX[i].k);
-    else for (int i = 0; i < 13; ++i) n += layer_elems(VGG_CH[i][0], VGG_CH[i][1], 3);
+    if (net == NET_ALEX) for (int i = 0; i < 5; ++i) n += packed_layer_elems(ALEX[i].cin, ALEX[i].cout, ALEX[i].k, ALEX[i].k);
+    else for (int i = 0; i < 13; ++i) n += packed_layer_elems(VGG_CH[i][0], VGG_CH[i][1], 3, 3);
     for (int k = 0; k < 5; ++k) n += TAP_CH[net][k];
     return n;
 }
@@ -187,7 +184,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
 #pragma unroll
                 for (int r = 0; r < 16; ++r) tot[i][j][r] += acc[i][j][r];
     }
-    // result row (channel) = (r & 3) + 8 (r >> 2) + 4 half, column (pixel) = l31: 32 consecutive floats per lane half and register
+    // result row (channel) = mfma32_row(r, half), column (pixel) = l31: 32 consecutive floats per lane half and register
     const int ox = ox0 + l31, HoWo = a.Ho * a.Wo;
     if (ox >= a.Wo) return;
 #pragma unroll
@@ -198,7 +195,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
         for (int i = 0; i < T; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int oc = co0 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * half;
+                const int oc = co0 + 32 * i + mfma32_row(r, half);
                 a.out[((size_t)n * a.cout + oc) * HoWo + oy * a.Wo + ox] = fmaxf(tot[i][j][r] + a.bias[oc], 0.f);
             }
     }
@@ -225,8 +222,8 @@ int conv(const float *&pk, const float *in, int cin, int Hi, int Wi, int cout, i
     a.in = in; a.out = out; a.cin = cin; a.cinp = (cin + 1) & ~1; a.cout = cout; a.Hi = Hi; a.Wi = Wi; a.pad = pad;
     a.Ho = (Hi + 2 * pad - k) / stride + 1; a.Wo = (Wi + 2 * pad - k) / stride + 1;
     a.tiles_x = cdiv(a.Wo, TILE_C);
-    a.w = pk; a.bias = pk + (size_t)k * k * a.cinp * cout;
-    pk = a.bias + cout;
+    const PackedLayer l = next_layer(pk, k * k, cin, cout);
+    a.w = l.w; a.bias = l.bias;
     if (cout % 64) { set_error("lpips conv: cout=%d is no multiple of 64", cout); return HNR_ERR_BADARG; }
     if (k == 3 && stride == 1) return launch_conv<3, 1, 8>(a, st);
     if (k == 5 && stride == 1) return launch_conv<5, 1, 4>(a, st);

@@ -1,100 +1,28 @@
 // Depth maps from the pretrained MVSNet, on the device: the reference's `MVSNet(refine=False)` in eval mode (models/depth_estimators/mvsnet.py,
 // module.py) and the tail of `MvsPointsModel.gen_points` (models/mvs/mvs_points_model.py:300-341) for `manual_depth_view=1`.  Inference only: no backward.
 //
-//   hnr_mvsnet_feature       seven conv + norm + ReLU and the `feature` conv: the arrangement of featnet_conv_kernel (featnet.hip) -- one output pixel per
-//                            thread, the output channels in registers, the input tile with its halo in LDS eight channels at a time, the weights read
-//                            through wave-uniform addresses -- with plain BatchNorm + ReLU, or bias alone, as the epilogue.
+//   hnr_mvsnet_feature       seven conv + norm + ReLU and the `feature` conv: conv2d_direct_kernel (conv_direct.h) with plain BatchNorm + ReLU, or bias
+//                            alone, as the epilogue.
 //   hnr_mvsnet_cost_volume   one thread per (pixel, depth): the V views' 32 channels sampled and folded into 32 sums and 32 sums of squares.
-//   hnr_mvsnet_cost_reg      the 3-D network.  Convolutions: the same arrangement in three dimensions (a block of 32 x 4 x 2 threads, ZPT outputs along z
+//   hnr_mvsnet_cost_reg      the 3-D network.  Convolutions: that kernel's arrangement in three dimensions (a block of 32 x 4 x 2 threads, ZPT outputs along z
 //                            per thread so that a staged value feeds up to ZPT * COG fmaf; both chosen per layer).  Transposed convolutions: a gather, one block per parity
 //                            class of the output, so the 1 / 2 / 4 / 8 taps and their weights are the same for every lane.
 //   hnr_mvsnet_depth_head    softmax over D, expected depth, expected index, the four-bin confidence: one thread per pixel.
 //   hnr_mvsnet_depth_points  nearest upsampling, the near / far mask, the camera-space point of every pixel.
 // Every sum is one chain of explicit fmaf in a fixed order: two runs give the same bits.
-#include "hnr_launch.h"
+#include "conv_direct.h"
 
 namespace hnr {
 
-struct MvLayer { int cin, cout, ks, stride; };
-
 // ---- the 2-D feature net -----------------------------------------------------------------------------------------------------------------------------
-constexpr int MF_TW = 32, MF_TH = 8;            // output tile of one block: one pixel per thread
-constexpr int MF_CCH = 8;                       // input channels staged per round
-constexpr int MF_LAYERS = 8;                    // the last one is `feature`: bias, no norm, no activation
-constexpr MvLayer MF_LAYER[MF_LAYERS] = {{3, 8, 3, 1}, {8, 8, 3, 1}, {8, 16, 5, 2}, {16, 16, 3, 1}, {16, 16, 3, 1}, {16, 32, 5, 2}, {32, 32, 3, 1}, {32, 32, 3, 1}};
+// conv_direct.h's eight layers; the last one is `feature`: bias, no norm, no activation
+static_assert(conv2d_offset(CONV2D_LAYERS, 1) == HNR_MVSNET_FEATURE_PACKED_ELEMS, "include/hnr.h: HNR_MVSNET_FEATURE_PACKED_ELEMS");
 
-constexpr int mf_offset(int l)
-{
-    int o = 0;
-    for (int i = 0; i < l; ++i) o += MF_LAYER[i].cin * MF_LAYER[i].ks * MF_LAYER[i].ks * MF_LAYER[i].cout + (i == MF_LAYERS - 1 ? 1 : 3) * MF_LAYER[i].cout;
-    return o;
-}
-static_assert(mf_offset(MF_LAYERS) == HNR_MVSNET_FEATURE_PACKED_ELEMS, "include/hnr.h: HNR_MVSNET_FEATURE_PACKED_ELEMS");
-
-// relu((acc - mean) * mul + bias), or acc + bias for a last layer; prm points behind the layer's weights, j is the output channel
-template <bool LAST>
-__device__ __forceinline__ float mv_epilogue(float acc, const float *__restrict__ prm, int cout, int j)
-{
-    if (LAST) return acc + prm[j];
-    const float u = (acc - prm[j]) * prm[cout + j] + prm[2 * cout + j];
-    return u < 0.f ? 0.f : u;                                           // (a NaN stays a NaN, as in torch's relu)
-}
-
-// in [V,CIN,Hi,Wi] -> out [V,COUT,Ho,Wo]; blockIdx.z = view
-template <int CIN, int COUT, int KS, int STRIDE, bool LAST>
-__global__ void __launch_bounds__(256) mvsnet_conv2d_kernel(const float *__restrict__ in, int Hi, int Wi, int Ho, int Wo, const float *__restrict__ prm,
-                                                            float *__restrict__ out)
-{
-    extern __shared__ float mv_tile[];
-    constexpr int PAD = KS / 2, IW = (MF_TW - 1) * STRIDE + KS, IH = (MF_TH - 1) * STRIDE + KS, CCH = CIN < MF_CCH ? CIN : MF_CCH;
-    static_assert(CIN % CCH == 0, "mvsnet_conv2d_kernel: channel split");
-    const int tx = threadIdx.x & (MF_TW - 1), ty = threadIdx.x / MF_TW, v = blockIdx.z;
-    const int ox0 = blockIdx.x * MF_TW, oy0 = blockIdx.y * MF_TH;
-    const int ix0 = ox0 * STRIDE - PAD, iy0 = oy0 * STRIDE - PAD;
-    const float *inv = in + (size_t)v * CIN * Hi * Wi;
-    float acc[COUT];
-#pragma unroll
-    for (int j = 0; j < COUT; ++j) acc[j] = 0.f;
-    for (int c0 = 0; c0 < CIN; c0 += CCH) {
-        __syncthreads();                                                // the previous round's reads are done
-        for (int e = threadIdx.x; e < CCH * IH * IW; e += 256) {
-            const int ch = e / (IH * IW), r = e - ch * (IH * IW), yy = r / IW, xx = r - yy * IW;
-            const int iy = iy0 + yy, ix = ix0 + xx;
-            mv_tile[e] = (iy >= 0 && iy < Hi && ix >= 0 && ix < Wi) ? inv[((size_t)(c0 + ch) * Hi + iy) * Wi + ix] : 0.f;          // zero padding
-        }
-        __syncthreads();
-        const float *t0 = mv_tile + (ty * STRIDE) * IW + tx * STRIDE;
-#pragma unroll 1
-        for (int ch = 0; ch < CCH; ++ch) {
-            const float *t = t0 + ch * (IH * IW);
-            const float *w = prm + (size_t)((c0 + ch) * KS * KS) * COUT;                    // the same address in every lane
-#pragma unroll
-            for (int ky = 0; ky < KS; ++ky) {
-#pragma unroll
-                for (int kx = 0; kx < KS; ++kx) {
-                    const float a = t[ky * IW + kx];
-#pragma unroll
-                    for (int j = 0; j < COUT; ++j) acc[j] = fmaf(a, w[(ky * KS + kx) * COUT + j], acc[j]);
-                }
-            }
-        }
-    }
-    const int ox = ox0 + tx, oy = oy0 + ty;
-    if (ox >= Wo || oy >= Ho) return;
-    const size_t plane = (size_t)Ho * Wo;
-    float *o = out + (size_t)v * COUT * plane + (size_t)oy * Wo + ox;
-#pragma unroll
-    for (int j = 0; j < COUT; ++j) o[j * plane] = mv_epilogue<LAST>(acc[j], prm + CIN * KS * KS * COUT, COUT, j);
-}
-
-template <int L>
+// every output channel of the pixel in one thread (COG = COUT)
+template <int L, class Epi = EpiBnRelu>
 static int mf_launch(const float *in, int V, int Hi, int Wi, int Ho, int Wo, const float *packed, float *out, hipStream_t st)
 {
-    constexpr MvLayer P = MF_LAYER[L];
-    constexpr int CCH = P.cin < MF_CCH ? P.cin : MF_CCH;
-    constexpr int lds = CCH * ((MF_TH - 1) * P.stride + P.ks) * ((MF_TW - 1) * P.stride + P.ks) * (int)sizeof(float);
-    return launch_lds<mvsnet_conv2d_kernel<P.cin, P.cout, P.ks, P.stride, L == MF_LAYERS - 1>>(dim3(cdiv(Wo, MF_TW), cdiv(Ho, MF_TH), V), dim3(256), lds, st, in, Hi, Wi,
-                                                                                              Ho, Wo, packed + mf_offset(L), out);
+    return conv2d_direct_launch<L, CONV2D_LAYER[L].cout, Epi>(in, V, Hi, Wi, Ho, Wo, packed + conv2d_offset(L, 1), out, st);
 }
 
 static bool mf_shape_ok(int V, int H, int W) { return V >= 1 && V <= 64 && H >= 4 && W >= 4 && H <= 32768 && W <= 32768; }
@@ -379,20 +307,14 @@ __global__ void __launch_bounds__(256) mvsnet_depth_points_kernel(const float *_
 
 using namespace hnr;
 
-static void mf_sizes(int H, int W, int64_t &H2, int64_t &W2, int64_t &H4, int64_t &W4)
-{
-    H2 = (H - 1) / 2 + 1; W2 = (W - 1) / 2 + 1; H4 = (H2 - 1) / 2 + 1; W4 = (W2 - 1) / 2 + 1;
-}
-
 // two buffers of the largest layer output
 extern "C" int64_t hnr_mvsnet_feature_scratch_elems(int V, int H, int W)
 {
     if (!mf_shape_ok(V, H, W)) return -1;
-    int64_t H2, W2, H4, W4;
-    mf_sizes(H, W, H2, W2, H4, W4);
+    const Pyramid p = pyramid_extents(H, W);
     int64_t m = 8 * (int64_t)H * W;
-    if (16 * H2 * W2 > m) m = 16 * H2 * W2;
-    if (32 * H4 * W4 > m) m = 32 * H4 * W4;
+    if (16 * (int64_t)p.H2 * p.W2 > m) m = 16 * (int64_t)p.H2 * p.W2;
+    if (32 * (int64_t)p.H4 * p.W4 > m) m = 32 * (int64_t)p.H4 * p.W4;
     return 2 * m * V;
 }
 
@@ -404,9 +326,7 @@ extern "C" int hnr_mvsnet_feature(const float *d_images, int V, int H, int W, co
     const int64_t need = hnr_mvsnet_feature_scratch_elems(V, H, W);
     if (scratch_elems < need) { set_error("hnr_mvsnet_feature: scratch smaller than hnr_mvsnet_feature_scratch_elems(V, H, W)"); return HNR_ERR_BADARG; }
     hipStream_t st = (hipStream_t)stream;
-    int64_t h2, w2, h4, w4;
-    mf_sizes(H, W, h2, w2, h4, w4);
-    const int H2 = (int)h2, W2 = (int)w2, H4 = (int)h4, W4 = (int)w4;
+    const auto [H2, W2, H4, W4] = pyramid_extents(H, W);
     float *a = d_scratch, *b = d_scratch + need / 2;
     if (int rc = mf_launch<0>(d_images, V, H, W, H, W, d_packed, a, st)) return rc;
     if (int rc = mf_launch<1>(a, V, H, W, H, W, d_packed, b, st)) return rc;
@@ -415,7 +335,7 @@ extern "C" int hnr_mvsnet_feature(const float *d_images, int V, int H, int W, co
     if (int rc = mf_launch<4>(b, V, H2, W2, H2, W2, d_packed, a, st)) return rc;
     if (int rc = mf_launch<5>(a, V, H2, W2, H4, W4, d_packed, b, st)) return rc;
     if (int rc = mf_launch<6>(b, V, H4, W4, H4, W4, d_packed, a, st)) return rc;
-    return mf_launch<7>(a, V, H4, W4, H4, W4, d_packed, d_feat, st);                         // `feature`
+    return mf_launch<7, EpiBias>(a, V, H4, W4, H4, W4, d_packed, d_feat, st);                     // `feature`
 }
 
 extern "C" int hnr_mvsnet_cost_volume(const float *d_feat, int V, int h, int w, const float *d_proj, const float *d_depth_values, int D, float *d_volume,

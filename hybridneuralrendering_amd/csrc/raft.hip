@@ -11,12 +11,11 @@
 //   Packed layer: w [kh*kw][cinp][cout] then bias [cout]; a padded channel row is zero.
 // The epilogues carry the norms that fold (batch norm, into w and bias by whoever packs), the activations and the GRU gates, so r*h, z and
 // (1-z)h + zq never make a pass of their own; h, inp and the motion features are read in place as three sources (no concatenated copy).
+#include "conv_mfma.h"
 #include "hnr_launch.h"
 
 namespace hnr {
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 enum { EPI_NONE = 0, EPI_RELU = 1, EPI_RELU_ADD_RELU = 2, EPI_ZR = 3, EPI_GRU = 4, EPI_TANH_RELU = 5 };
 
@@ -115,7 +114,7 @@ __global__ __launch_bounds__(64 * CONV_WAVES) void raft_conv_kernel(ConvArgs a)
         for (int j = 0; j < T; ++j) {
             if (i + j) __syncthreads();
 #pragma unroll
-            for (int r = 0; r < 16; ++r) part[wave][(r & 3) + 8 * (r >> 2) + 4 * half][l31] = acc[i][j][r];
+            for (int r = 0; r < 16; ++r) part[wave][mfma32_row(r, half)][l31] = acc[i][j][r];
             __syncthreads();
 #pragma unroll
             for (int q = 0; q < 16 / CONV_WAVES; ++q) {
@@ -173,13 +172,10 @@ int layer(const float *&pk, const float *s0, int c0, const float *s1, int c1, co
     a.scale = 1.0f; a.epi = epi; a.split = split; a.e0 = e0; a.e1 = e1; a.out = out; a.out2 = out2;
     int cinp = 0;
     for (int s = 0; s < a.nsrc; ++s) cinp += (a.csrc[s] + 1) & ~1;
-    a.w = pk;
-    a.bias = pk + (size_t)kh * kw * cinp * cout;
-    pk = a.bias + cout;
+    const PackedLayer l = next_layer(pk, kh * kw, cinp, cout);
+    a.w = l.w; a.bias = l.bias;
     return conv(a, st);
 }
-
-int64_t layer_elems(int cin, int cout, int kh, int kw) { return (int64_t)kh * kw * ((cin + 1) & ~1) * cout + cout; }
 
 // ---- encoder ---------------------------------------------------------------------------------------------------------------------------------
 __global__ void raft_scale_input_kernel(const float *__restrict__ in, float *__restrict__ out, int64_t n)
@@ -251,7 +247,7 @@ int encoder(const float *d_images, int N, int H, int W, const float *pk, int nor
         TRY(layer(pk, x, cin, nullptr, 0, nullptr, 0, N, h, w, co, 3, 3, s, in_ ? EPI_NONE : EPI_RELU, t1, st));
         if (in_) TRY(inorm(t1, nullptr, t1, N * co, ho * wo, 1, st));
         const float *pk2 = pk;                                       // conv2 needs the shortcut first: remember where its weights are
-        pk += layer_elems(co, co, 3, 3);
+        pk += packed_layer_elems(co, co, 3, 3);
         const float *shortcut = x;
         if (s != 1) {
             TRY(layer(pk, x, cin, nullptr, 0, nullptr, 0, N, h, w, co, 1, 1, s, EPI_NONE, t3, st));
@@ -451,12 +447,12 @@ int upsample(const float *flow, const float *mask, int h, int w, float *up, hipS
 
 int64_t encoder_packed_elems(int cout)
 {
-    int64_t n = layer_elems(3, 64, 7, 7);
+    int64_t n = packed_layer_elems(3, 64, 7, 7);
     for (int b = 0; b < 6; ++b) {
-        n += layer_elems(ENC_BLOCKS[b][0], ENC_BLOCKS[b][1], 3, 3) + layer_elems(ENC_BLOCKS[b][1], ENC_BLOCKS[b][1], 3, 3);
-        if (ENC_BLOCKS[b][2] != 1) n += layer_elems(ENC_BLOCKS[b][0], ENC_BLOCKS[b][1], 1, 1);
+        n += packed_layer_elems(ENC_BLOCKS[b][0], ENC_BLOCKS[b][1], 3, 3) + packed_layer_elems(ENC_BLOCKS[b][1], ENC_BLOCKS[b][1], 3, 3);
+        if (ENC_BLOCKS[b][2] != 1) n += packed_layer_elems(ENC_BLOCKS[b][0], ENC_BLOCKS[b][1], 1, 1);
     }
-    return n + layer_elems(128, cout, 1, 1);
+    return n + packed_layer_elems(128, cout, 1, 1);
 }
 
 int64_t encoder_scratch(int N, int H, int W) { return (int64_t)N * 3 * H * W + 4 * (int64_t)N * 64 * (H / 2) * (W / 2); }
@@ -482,9 +478,9 @@ int64_t hnr_raft_encoder_packed_elems(void) { return encoder_packed_elems(256); 
 
 int64_t hnr_raft_update_packed_elems(void)
 {
-    return layer_elems(324, 256, 1, 1) + layer_elems(256, 192, 3, 3) + layer_elems(2, 128, 7, 7) + layer_elems(128, 64, 3, 3) + layer_elems(256, 126, 3, 3) +
-           2 * (layer_elems(384, 256, 1, 5) + layer_elems(384, 128, 1, 5)) + layer_elems(128, 256, 3, 3) + layer_elems(256, 2, 3, 3) +
-           layer_elems(128, 256, 3, 3) + layer_elems(256, 576, 1, 1);
+    constexpr auto n = packed_layer_elems;
+    return n(324, 256, 1, 1) + n(256, 192, 3, 3) + n(2, 128, 7, 7) + n(128, 64, 3, 3) + n(256, 126, 3, 3) + 2 * (n(384, 256, 1, 5) + n(384, 128, 1, 5)) +
+           n(128, 256, 3, 3) + n(256, 2, 3, 3) + n(128, 256, 3, 3) + n(256, 576, 1, 1);
 }
 
 int64_t hnr_raft_encoder_scratch_elems(int N, int H, int W) { return (N >= 1 && N <= 2 && shape_ok(H, W)) ? encoder_scratch(N, H, W) : -1; }

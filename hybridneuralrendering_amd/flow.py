@@ -11,7 +11,7 @@ from torch import nn
 
 from . import _lib
 from ._lib import HnrError
-from .mvs_init import _Packed
+from ._nets import NormParams, Packed, PackedWeights, filtered_state_dict, gpu_f32, host_f32, load_checked, load_checkpoint
 
 EPS = 1e-5
 ENC_BLOCKS = (("layer1.0", 64, 64, 1), ("layer1.1", 64, 64, 1), ("layer2.0", 64, 96, 2), ("layer2.1", 96, 96, 1), ("layer3.0", 96, 128, 2),
@@ -31,17 +31,6 @@ def check_shape(H, W, what="RAFT"):
         raise HnrError("%s: H=%d, W=%d is too large (H, W <= 4096, H/8*W/8 <= 16384: the correlation volume is materialised)" % (what, H, W))
 
 
-def _gpu(t, name, shape=None):
-    t = _lib.require_gpu(t, name, torch.float32).detach()
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise HnrError("%s must be %s, got %s" % (name, tuple(shape), tuple(t.shape)))
-    return t
-
-
-def _f(t):
-    return t.detach().float().cpu()
-
-
 def pyramid_shapes(h, w):
     out = [(h, w)]
     for _ in range(CORR_LEVELS - 1):
@@ -53,12 +42,12 @@ def encoder(images, packed, norm):
     """hnr_raft_encoder: images [N,3,H,W] (0..255), N = 1 or 2 -> [N,256,H/8,W/8].  norm: 0 instance norm, 1 folded batch norm, 2 folded batch norm
     then tanh | relu on the two halves of the channels."""
     L = _lib.lib()
-    images = _gpu(images, "images")
+    images = gpu_f32(images, "images")
     if images.dim() != 4 or images.shape[1] != 3 or images.shape[0] not in (1, 2):
         raise HnrError("encoder: images must be [1 or 2,3,H,W], got %s" % (tuple(images.shape),))
     N, _, H, W = (int(s) for s in images.shape)
     check_shape(H, W, "encoder")
-    packed = _gpu(packed, "packed", (int(L.hnr_raft_encoder_packed_elems()),))
+    packed = gpu_f32(packed, "packed", (int(L.hnr_raft_encoder_packed_elems()),))
     ns = int(L.hnr_raft_encoder_scratch_elems(N, H, W))
     out = torch.empty((N, 256, H // 8, W // 8), dtype=torch.float32, device=images.device)
     scratch = torch.empty((ns,), dtype=torch.float32, device=images.device)
@@ -71,7 +60,7 @@ def encoder(images, packed, norm):
 def corr_pyramid(fmap1, fmap2):
     """hnr_raft_corr_pyramid: fmap1, fmap2 [256,h,w] -> the four levels [h*w,h_l,w_l] as views of one buffer."""
     L = _lib.lib()
-    fmap1, fmap2 = _gpu(fmap1, "fmap1"), _gpu(fmap2, "fmap2", tuple(fmap1.shape))
+    fmap1, fmap2 = gpu_f32(fmap1, "fmap1"), gpu_f32(fmap2, "fmap2", tuple(fmap1.shape))
     if fmap1.dim() != 3 or fmap1.shape[0] != 256:
         raise HnrError("corr_pyramid: fmap1 must be [256,h,w], got %s" % (tuple(fmap1.shape),))
     h, w = int(fmap1.shape[1]), int(fmap1.shape[2])
@@ -95,7 +84,7 @@ def pyramid_levels(buf, h, w):
 def lookup(pyramid, coords):
     """hnr_raft_lookup: the pyramid buffer of corr_pyramid, coords [2,h,w] (x, y) -> [324,h,w]."""
     L = _lib.lib()
-    pyramid, coords = _gpu(pyramid, "pyramid"), _gpu(coords, "coords")
+    pyramid, coords = gpu_f32(pyramid, "pyramid"), gpu_f32(coords, "coords")
     if coords.dim() != 3 or coords.shape[0] != 2:
         raise HnrError("lookup: coords must be [2,h,w], got %s" % (tuple(coords.shape),))
     h, w = int(coords.shape[1]), int(coords.shape[2])
@@ -112,12 +101,12 @@ def update(packed, pyramid, net, inp, coords, want_mask=False):
     """hnr_raft_update, one iteration: net [128,h,w], inp [128,h,w], coords [2,h,w] -> (net, coords, delta_flow [2,h,w], mask [576,h,w] or None); the
     inputs are left as they are."""
     L = _lib.lib()
-    net, inp, coords = _gpu(net, "net").clone(), _gpu(inp, "inp", tuple(net.shape)), _gpu(coords, "coords").clone()
+    net, inp, coords = gpu_f32(net, "net").clone(), gpu_f32(inp, "inp", tuple(net.shape)), gpu_f32(coords, "coords").clone()
     if net.dim() != 3 or net.shape[0] != 128 or tuple(coords.shape) != (2,) + tuple(net.shape[1:]):
         raise HnrError("update: net and inp must be [128,h,w] and coords [2,h,w]")
     h, w = int(net.shape[1]), int(net.shape[2])
     check_shape(8 * h, 8 * w, "update")
-    packed, pyramid = _gpu(packed, "packed", (int(L.hnr_raft_update_packed_elems()),)), _gpu(pyramid, "pyramid", (int(L.hnr_raft_pyramid_elems(h, w)),))
+    packed, pyramid = gpu_f32(packed, "packed", (int(L.hnr_raft_update_packed_elems()),)), gpu_f32(pyramid, "pyramid", (int(L.hnr_raft_pyramid_elems(h, w)),))
     ns = int(L.hnr_raft_update_scratch_elems(h, w))
     delta = torch.empty((2, h, w), dtype=torch.float32, device=net.device)
     mask = torch.empty((576, h, w), dtype=torch.float32, device=net.device) if want_mask else None
@@ -131,7 +120,7 @@ def update(packed, pyramid, net, inp, coords, want_mask=False):
 def upsample(flow, mask):
     """hnr_raft_upsample: flow [2,h,w], mask [576,h,w] -> [2,8h,8w]."""
     L = _lib.lib()
-    flow, mask = _gpu(flow, "flow"), _gpu(mask, "mask")
+    flow, mask = gpu_f32(flow, "flow"), gpu_f32(mask, "mask")
     if flow.dim() != 3 or flow.shape[0] != 2 or tuple(mask.shape) != (576,) + tuple(flow.shape[1:]) or flow.shape[1] * flow.shape[2] > 16384:
         raise HnrError("upsample: flow must be [2,h,w] and mask [576,h,w], h*w <= 16384")
     h, w = int(flow.shape[1]), int(flow.shape[2])
@@ -141,26 +130,16 @@ def upsample(flow, mask):
     return out
 
 
-class _Norm(nn.Module):
-    """BatchNorm2d's names; its arithmetic is folded into the packed convolution."""
-
-    def __init__(self, ch):
-        super().__init__()
-        self.weight, self.bias = nn.Parameter(torch.ones(ch)), nn.Parameter(torch.zeros(ch))
-        self.register_buffer("running_mean", torch.zeros(ch))
-        self.register_buffer("running_var", torch.ones(ch))
-
-
 class _ResidualBlock(nn.Module):
     def __init__(self, cin, cout, stride, batch_norm):
         super().__init__()
         self.conv1 = nn.Conv2d(cin, cout, 3, padding=1, stride=stride)
         self.conv2 = nn.Conv2d(cout, cout, 3, padding=1)
         if batch_norm:
-            self.norm1, self.norm2 = _Norm(cout), _Norm(cout)
+            self.norm1, self.norm2 = NormParams(cout), NormParams(cout)
         if stride != 1:
             if batch_norm:
-                self.norm3 = _Norm(cout)                           # (the reference registers it twice: as norm3 and as downsample.1)
+                self.norm3 = NormParams(cout)                           # (the reference registers it twice: as norm3 and as downsample.1)
                 self.downsample = nn.Sequential(nn.Conv2d(cin, cout, 1, stride=stride), self.norm3)
             else:
                 self.downsample = nn.Sequential(nn.Conv2d(cin, cout, 1, stride=stride))
@@ -171,7 +150,7 @@ class _BasicEncoder(nn.Module):
         super().__init__()
         self.batch_norm = batch_norm
         if batch_norm:
-            self.norm1 = _Norm(64)
+            self.norm1 = NormParams(64)
         self.conv1 = nn.Conv2d(3, 64, 7, stride=2, padding=3)
         for i in (1, 2, 3):
             a, b = ENC_BLOCKS[2 * i - 2], ENC_BLOCKS[2 * i - 1]
@@ -180,10 +159,10 @@ class _BasicEncoder(nn.Module):
 
     def _layer(self, conv, norm, scale=1.0):
         """w [kh*kw][cinp][cout], bias [cout]; an eval-mode batch norm y = (x - mean) * mul + beta, mul = weight * rsqrt(var + eps), is folded in."""
-        w, b = _f(conv.weight).double(), _f(conv.bias).double()
+        w, b = host_f32(conv.weight).double(), host_f32(conv.bias).double()
         if norm is not None:
-            mul = _f(norm.weight).double() / torch.sqrt(_f(norm.running_var).double() + EPS)
-            w, b = w * mul[:, None, None, None], (b - _f(norm.running_mean).double()) * mul + _f(norm.bias).double()
+            mul = host_f32(norm.weight).double() / torch.sqrt(host_f32(norm.running_var).double() + EPS)
+            w, b = w * mul[:, None, None, None], (b - host_f32(norm.running_mean).double()) * mul + host_f32(norm.bias).double()
         return pack_layer(w * scale, b * scale)
 
     def pack_host(self):
@@ -238,8 +217,8 @@ class _UpdateBlock(nn.Module):
 
     def pack_host(self):
         e, g, fh = self.encoder, self.gru, self.flow_head
-        p = lambda c, s=1.0: pack_layer(_f(c.weight) * s, _f(c.bias) * s)
-        zr = lambda z, r: pack_layer(torch.cat([_f(z.weight), _f(r.weight)]), torch.cat([_f(z.bias), _f(r.bias)]))
+        p = lambda c, s=1.0: pack_layer(host_f32(c.weight) * s, host_f32(c.bias) * s)
+        zr = lambda z, r: pack_layer(torch.cat([host_f32(z.weight), host_f32(r.weight)]), torch.cat([host_f32(z.bias), host_f32(r.bias)]))
         with torch.no_grad():
             return torch.cat([p(e.convc1), p(e.convc2), p(e.convf1), p(e.convf2), p(e.conv), zr(g.convz1, g.convr1), p(g.convq1), zr(g.convz2, g.convr2),
                               p(g.convq2), p(fh.conv1), p(fh.conv2), p(self.mask[0]), p(self.mask[2], 0.25)])
@@ -253,7 +232,7 @@ def _arg(args, name, default):
     return getattr(args, name, default)
 
 
-class RAFT(nn.Module):
+class RAFT(PackedWeights, nn.Module):
     """The reference's `RAFT(args)` basic model in eval mode: its parameter and buffer names, its forward signature, HIP kernels inside."""
 
     def __init__(self, args=None):
@@ -269,7 +248,7 @@ class RAFT(nn.Module):
         self.fnet = _BasicEncoder(256, batch_norm=False)
         self.cnet = _BasicEncoder(256, batch_norm=True)
         self.update_block = _UpdateBlock()
-        self._packed = _Packed()
+        self._packed = Packed()
         self.eval()
 
     def train(self, mode=True):
@@ -280,13 +259,7 @@ class RAFT(nn.Module):
     def load_pretrained(self, path_or_dict):
         """The published checkpoint as it is (demo_content_aware_weights.py:96-97 loads it into a DataParallel): `module.` is stripped,
         `num_batches_tracked` entries are ignored, a missing or an unexpected key is an HnrError."""
-        sd = torch.load(path_or_dict, map_location="cpu") if isinstance(path_or_dict, (str, bytes)) or hasattr(path_or_dict, "__fspath__") else path_or_dict
-        sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items() if not k.endswith("num_batches_tracked")}
-        res = self.load_state_dict(sd, strict=False)
-        if res.missing_keys:
-            raise HnrError("RAFT.load_pretrained: the checkpoint lacks %s" % ", ".join(sorted(res.missing_keys)))
-        if res.unexpected_keys:
-            raise HnrError("RAFT.load_pretrained: unexpected keys %s" % ", ".join(sorted(res.unexpected_keys)))
+        load_checked(self, filtered_state_dict(load_checkpoint(path_or_dict)), "RAFT.load_pretrained")
         return self
 
     def pack_host(self):
@@ -295,15 +268,6 @@ class RAFT(nn.Module):
         f, c, u = self.fnet.pack_host(), self.cnet.pack_host(), self.update_block.pack_host()
         assert f.numel() == c.numel() == int(L.hnr_raft_encoder_packed_elems()) and u.numel() == int(L.hnr_raft_update_packed_elems())
         return f, c, u
-
-    def packed(self):
-        tensors = list(self.parameters()) + list(self.buffers())
-        dev = self.fnet.conv1.weight.device
-        return self._packed.get(tensors, lambda: tuple(p.to(dev) for p in self.pack_host()))
-
-    def invalidate_packed(self):
-        """Needed only after replacing a parameter's storage with `p.data = ...` (mvs_init._Packed)."""
-        self._packed.invalidate()
 
     def forward(self, image1, image2, iters=20, flow_init=None, upsample=True, test_mode=True):
         """image1, image2 [1,3,H,W], values 0..255 -> (flow_low [1,2,H/8,W/8], flow_up [1,2,H,W])."""
@@ -323,7 +287,7 @@ class RAFT(nn.Module):
         iters = int(iters)
         if not 1 <= iters <= 1024:
             raise HnrError("RAFT: iters=%d (1 .. 1024)" % iters)
-        pair = torch.cat([_gpu(image1, "image1"), _gpu(image2, "image2")])
+        pair = torch.cat([gpu_f32(image1, "image1"), gpu_f32(image2, "image2")])
         low, up = self.flow_pair(pair, iters)
         return low[None], up[None]
 

@@ -16,7 +16,7 @@ from torch import nn
 
 from . import _lib
 from ._lib import HnrError
-from .mvs_init import _Packed
+from ._nets import NormParams, Packed, PackedWeights, filtered_state_dict, gpu_f32, host_f32, load_checked, load_checkpoint, same_device
 
 EPS = 1e-5                                                       # nn.BatchNorm's eps
 NUM_DEPTH = 192                                                  # gen_points' depth planes
@@ -30,25 +30,13 @@ def feature_shape(H, W):
     return ((H - 1) // 2 + 1 - 1) // 2 + 1, ((W - 1) // 2 + 1 - 1) // 2 + 1
 
 
-def _gpu(t, name, shape=None):
-    t = _lib.require_gpu(t, name, torch.float32).detach()
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise HnrError("%s must be %s, got %s" % (name, tuple(shape), tuple(t.shape)))
-    return t
-
-
-def _same_device(what, *ts):
-    if any(t.device != ts[0].device for t in ts):
-        raise HnrError("%s: every tensor must be on the same device" % what)
-
-
 def feature_forward(images, packed):
     """hnr_mvsnet_feature: images [V,3,H,W], packed [MVSNET_FEATURE_PACKED_ELEMS] -> [V,32,h,w]."""
     L = _lib.lib()
-    images, packed = _gpu(images, "images"), _gpu(packed, "packed", (_lib.MVSNET_FEATURE_PACKED_ELEMS,))
+    images, packed = gpu_f32(images, "images"), gpu_f32(packed, "packed", (_lib.MVSNET_FEATURE_PACKED_ELEMS,))
     if images.dim() != 4 or images.shape[1] != 3:
         raise HnrError("feature_forward: images must be [V,3,H,W], got %s" % (tuple(images.shape),))
-    _same_device("feature_forward", images, packed)
+    same_device("feature_forward", images, packed)
     V, _, H, W = (int(s) for s in images.shape)
     ns = int(L.hnr_mvsnet_feature_scratch_elems(V, H, W)) if max(V, H, W) < 2 ** 31 else -1
     if ns < 0:
@@ -63,13 +51,13 @@ def feature_forward(images, packed):
 def cost_volume(features, proj, depth_values):
     """hnr_mvsnet_cost_volume for one reference view: features [V,32,h,w], proj [V,3,4] (or [V,4,4]), depth_values [D] -> [32,D,h,w]."""
     L = _lib.lib()
-    features, proj, depth_values = _gpu(features, "features"), _gpu(proj, "proj"), _gpu(depth_values, "depth_values")
+    features, proj, depth_values = gpu_f32(features, "features"), gpu_f32(proj, "proj"), gpu_f32(depth_values, "depth_values")
     if features.dim() != 4 or features.shape[1] != 32:
         raise HnrError("cost_volume: features must be [V,32,h,w], got %s" % (tuple(features.shape),))
     V, _, h, w = (int(s) for s in features.shape)
     if proj.dim() != 3 or proj.shape[0] != V or tuple(proj.shape[1:]) not in ((3, 4), (4, 4)) or depth_values.dim() != 1:
         raise HnrError("cost_volume: proj must be [V,3,4] or [V,4,4] and depth_values [D]")
-    _same_device("cost_volume", features, proj, depth_values)
+    same_device("cost_volume", features, proj, depth_values)
     proj, D = proj[:, :3].contiguous(), int(depth_values.shape[0])
     if not (1 <= V <= 64 and 2 <= h <= 8192 and 2 <= w <= 8192 and 1 <= D <= 4096 and D * h * w <= 2 ** 26):
         raise HnrError("cost_volume: unsupported shape V=%d D=%d h=%d w=%d (V <= 64, 2 <= h, w <= 8192, D <= 4096, D*h*w <= 2^26)" % (V, D, h, w))
@@ -83,10 +71,10 @@ def cost_volume(features, proj, depth_values):
 def cost_reg(volume, packed):
     """hnr_mvsnet_cost_reg: volume [32,D,h,w], packed [MVSNET_REG_PACKED_ELEMS] -> logits [D,h,w].  D, h and w must be multiples of 8."""
     L = _lib.lib()
-    volume, packed = _gpu(volume, "volume"), _gpu(packed, "packed", (_lib.MVSNET_REG_PACKED_ELEMS,))
+    volume, packed = gpu_f32(volume, "volume"), gpu_f32(packed, "packed", (_lib.MVSNET_REG_PACKED_ELEMS,))
     if volume.dim() != 4 or volume.shape[0] != 32:
         raise HnrError("cost_reg: volume must be [32,D,h,w], got %s" % (tuple(volume.shape),))
-    _same_device("cost_reg", volume, packed)
+    same_device("cost_reg", volume, packed)
     D, h, w = (int(s) for s in volume.shape[1:])
     ns = int(L.hnr_mvsnet_cost_reg_scratch_elems(D, h, w))
     if ns < 0:
@@ -102,10 +90,10 @@ def cost_reg(volume, packed):
 def depth_head(logits, depth_values, want_prob=False):
     """hnr_mvsnet_depth_head: logits [D,h,w], depth_values [D] -> (depth [h,w], confidence [h,w], prob [D,h,w] or None)."""
     L = _lib.lib()
-    logits, depth_values = _gpu(logits, "logits"), _gpu(depth_values, "depth_values")
+    logits, depth_values = gpu_f32(logits, "logits"), gpu_f32(depth_values, "depth_values")
     if logits.dim() != 3 or tuple(depth_values.shape) != (logits.shape[0],):
         raise HnrError("depth_head: logits must be [D,h,w] and depth_values [D]")
-    _same_device("depth_head", logits, depth_values)
+    same_device("depth_head", logits, depth_values)
     D, h, w = (int(s) for s in logits.shape)
     depth, conf = (torch.empty((h, w), dtype=torch.float32, device=logits.device) for _ in range(2))
     prob = torch.empty_like(logits) if want_prob else None
@@ -125,10 +113,10 @@ def depth_points(depth, confidence, H, W, near, far, intrinsic):
     """hnr_mvsnet_depth_points: depth, confidence [h,w] -> (cam_xyz [H,W,3], confidence [H,W], points_mask [H,W] bool)."""
     from .cloud_init import _cf
     L = _lib.lib()
-    depth, confidence = _gpu(depth, "depth"), _gpu(confidence, "confidence")
+    depth, confidence = gpu_f32(depth, "depth"), gpu_f32(confidence, "confidence")
     if depth.dim() != 2 or confidence.shape != depth.shape:
         raise HnrError("depth_points: depth and confidence must be [h,w]")
-    _same_device("depth_points", depth, confidence)
+    same_device("depth_points", depth, confidence)
     h, w, H, W = int(depth.shape[0]), int(depth.shape[1]), int(H), int(W)
     M = kt_inverse(intrinsic)
     cam = torch.empty((H, W, 3), dtype=torch.float32, device=depth.device)
@@ -140,29 +128,15 @@ def depth_points(depth, confidence, H, W, near, far, intrinsic):
     return cam, conf, mask.bool()
 
 
-class _Norm(nn.Module):
-    """Parameter holder with nn.BatchNorm's names; its arithmetic lives in the convolution kernels' epilogue."""
-
-    def __init__(self, ch):
-        super().__init__()
-        self.weight, self.bias = nn.Parameter(torch.ones(ch)), nn.Parameter(torch.zeros(ch))
-        self.register_buffer("running_mean", torch.zeros(ch))
-        self.register_buffer("running_var", torch.ones(ch))
-
-
 class _ConvBnReLU(nn.Module):
     def __init__(self, conv):
         super().__init__()
-        self.conv, self.bn = conv, _Norm(conv.out_channels)
-
-
-def _f(t):
-    return t.detach().float().cpu()
+        self.conv, self.bn = conv, NormParams(conv.out_channels)
 
 
 def _normed(w, bn):
     """[w, running_mean, mul, bias] of one layer; mul = weight * rsqrt(running_var + eps) is folded here, once."""
-    return [w, _f(bn.running_mean), _f(bn.weight) * torch.rsqrt(_f(bn.running_var) + EPS), _f(bn.bias)]
+    return [w, host_f32(bn.running_mean), host_f32(bn.weight) * torch.rsqrt(host_f32(bn.running_var) + EPS), host_f32(bn.bias)]
 
 
 class _FeatureNet(nn.Module):
@@ -179,11 +153,11 @@ class _CostRegNet(nn.Module):
         for i, (cin, cout, stride) in enumerate(REG_CONVS):
             setattr(self, "conv%d" % i, _ConvBnReLU(nn.Conv3d(cin, cout, 3, stride=stride, padding=1, bias=False)))
         for name, cin, cout in REG_DECONVS:
-            setattr(self, name, nn.Sequential(nn.ConvTranspose3d(cin, cout, 3, padding=1, output_padding=1, stride=2, bias=False), _Norm(cout)))
+            setattr(self, name, nn.Sequential(nn.ConvTranspose3d(cin, cout, 3, padding=1, output_padding=1, stride=2, bias=False), NormParams(cout)))
         self.prob = nn.Conv3d(8, 1, 3, stride=1, padding=1)
 
 
-class MVSNet(nn.Module):
+class MVSNet(PackedWeights, nn.Module):
     """The reference's depth estimator `MVSNet(refine=False)` in eval mode: its parameter and buffer names (`feature.conv0.conv.weight`, ...,
     `cost_regularization.conv7.1.running_var`, `cost_regularization.prob.bias`), its forward signature, HIP kernels inside."""
 
@@ -194,19 +168,13 @@ class MVSNet(nn.Module):
         self.refine = False
         self.feature = _FeatureNet()
         self.cost_regularization = _CostRegNet()
-        self._packed = _Packed()
+        self._packed = Packed()
 
     def load_pretrained(self, path_or_dict):
         """`MvsPointsModel.load_pretrained_d_est`: the checkpoint's ['model'] with `module.` stripped.  `num_batches_tracked` entries are ignored; a
         missing key is an HnrError."""
-        ckpt = torch.load(path_or_dict, map_location="cpu") if isinstance(path_or_dict, (str, bytes)) or hasattr(path_or_dict, "__fspath__") else path_or_dict
-        sd = ckpt["model"] if "model" in ckpt else ckpt
-        sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items() if not k.endswith("num_batches_tracked")}
-        res = self.load_state_dict(sd, strict=False)
-        if res.missing_keys:
-            raise HnrError("MVSNet.load_pretrained: the checkpoint lacks %s" % ", ".join(sorted(res.missing_keys)))
-        if res.unexpected_keys:
-            raise HnrError("MVSNet.load_pretrained: unexpected keys %s" % ", ".join(sorted(res.unexpected_keys)))
+        ckpt = load_checkpoint(path_or_dict)
+        load_checked(self, filtered_state_dict(ckpt["model"] if "model" in ckpt else ckpt), "MVSNet.load_pretrained")
         return self
 
     def pack_host(self):
@@ -216,29 +184,20 @@ class MVSNet(nn.Module):
             parts = []
             for i in range(len(FEATURE_LAYERS)):
                 blk = getattr(fn, "conv%d" % i)
-                parts += _normed(_f(blk.conv.weight).permute(1, 2, 3, 0), blk.bn)
-            parts += [_f(fn.feature.weight).permute(1, 2, 3, 0), _f(fn.feature.bias)]
+                parts += _normed(host_f32(blk.conv.weight).permute(1, 2, 3, 0), blk.bn)
+            parts += [host_f32(fn.feature.weight).permute(1, 2, 3, 0), host_f32(fn.feature.bias)]
             feat = torch.cat([p.contiguous().reshape(-1) for p in parts])
             parts = []
             for i in range(len(REG_CONVS)):
                 blk = getattr(cr, "conv%d" % i)
-                parts += _normed(_f(blk.conv.weight).permute(1, 2, 3, 4, 0), blk.bn)
+                parts += _normed(host_f32(blk.conv.weight).permute(1, 2, 3, 4, 0), blk.bn)
             for name, _, _ in REG_DECONVS:
                 seq = getattr(cr, name)
-                parts += _normed(_f(seq[0].weight).permute(0, 2, 3, 4, 1), seq[1])             # ConvTranspose3d keeps [cin][cout][kz][ky][kx]
-            parts += [_f(cr.prob.weight).permute(1, 2, 3, 4, 0), _f(cr.prob.bias)]
+                parts += _normed(host_f32(seq[0].weight).permute(0, 2, 3, 4, 1), seq[1])             # ConvTranspose3d keeps [cin][cout][kz][ky][kx]
+            parts += [host_f32(cr.prob.weight).permute(1, 2, 3, 4, 0), host_f32(cr.prob.bias)]
             reg = torch.cat([p.contiguous().reshape(-1) for p in parts])
         assert feat.numel() == _lib.MVSNET_FEATURE_PACKED_ELEMS and reg.numel() == _lib.MVSNET_REG_PACKED_ELEMS
         return feat, reg
-
-    def packed(self):
-        tensors = list(self.parameters()) + list(self.buffers())
-        dev = self.feature.feature.weight.device
-        return self._packed.get(tensors, lambda: tuple(p.to(dev) for p in self.pack_host()))
-
-    def invalidate_packed(self):
-        """Needed only after replacing a parameter's storage with `p.data = ...` (mvs_init._Packed)."""
-        self._packed.invalidate()
 
     def image_features(self, imgs):
         """imgs [V,3,H,W] -> [V,32,h,w]: the feature maps of every view, computed once for all reference views."""
@@ -263,7 +222,7 @@ class MVSNet(nn.Module):
         if h % 8 or w % 8 or D % 8:
             raise HnrError("MVSNet: the depth map's height %d and width %d and the number of depth planes %d must be multiples of 8 (images of %dx%d: the "
                            "skip connections of the 3-D network do not line up otherwise, and the reference fails there too)" % (h, w, D, H, W))
-        imgs, proj_matrices, depth_values = _gpu(imgs, "imgs"), _gpu(proj_matrices, "proj_matrices"), _gpu(depth_values, "depth_values")
+        imgs, proj_matrices, depth_values = gpu_f32(imgs, "imgs"), gpu_f32(proj_matrices, "proj_matrices"), gpu_f32(depth_values, "depth_values")
         dev = self.feature.feature.weight.device
         if dev != imgs.device:
             raise HnrError("MVSNet: the module is on %s, imgs on %s" % (dev, imgs.device))
@@ -273,9 +232,9 @@ class MVSNet(nn.Module):
             per_row = self.image_features(imgs.reshape(B * V, 3, H, W)).reshape(B, V, 32, h, w)
             features = [per_row[:, v] for v in range(V)]
         elif shared:
-            features = _gpu(features, "features", (V, 32, h, w))
+            features = gpu_f32(features, "features", (V, 32, h, w))
         else:
-            per_row = torch.stack([_gpu(f, "features[v]", (B, 32, h, w)) for f in features], dim=1)
+            per_row = torch.stack([gpu_f32(f, "features[v]", (B, 32, h, w)) for f in features], dim=1)
         depths, confs, probs = [], [], []
         for b in range(B):
             vol = cost_volume(features if shared else per_row[b], proj_matrices[b], depth_values[b])
@@ -304,8 +263,8 @@ def depth_views(batch, net, opt, occlusion=None):
     check_options(opt, occlusion)
     if not isinstance(net, MVSNet):
         raise HnrError("depth_views: net must be an mvs_depth.MVSNet")
-    imgs = _gpu(batch["images"], "images")
-    dimgs = _gpu(batch["mvs_images"], "mvs_images") if "mvs_images" in batch else imgs
+    imgs = gpu_f32(batch["images"], "images")
+    dimgs = gpu_f32(batch["mvs_images"], "mvs_images") if "mvs_images" in batch else imgs
     if dimgs.dim() != 5 or dimgs.shape[0] != 1 or dimgs.shape[2] != 3:
         raise HnrError("depth_views: images must be [1,N,3,H,W], got %s" % (tuple(dimgs.shape),))
     nv = int(opt.init_view_num)
@@ -313,10 +272,10 @@ def depth_views(batch, net, opt, occlusion=None):
     if not 1 <= nv <= dimgs.shape[1] or not depth_vid or any(not 0 <= v < batch["proj_mats"].shape[1] for v in depth_vid):
         raise HnrError("depth_views: init_view_num=%d / depth_vid=%r do not fit %d views" % (nv, depth_vid, dimgs.shape[1]))
     H, W = int(dimgs.shape[-2]), int(dimgs.shape[-1])
-    nfd = _gpu(batch["near_fars_depth"], "near_fars_depth")[0]
+    nfd = gpu_f32(batch["near_fars_depth"], "near_fars_depth")[0]
     interval = (nfd[1] - nfd[0]) / 192.
     depth_values = (nfd[0] + torch.arange(0, NUM_DEPTH, device=dimgs.device, dtype=torch.float32) * interval)[None, :]
-    proj = _gpu(batch["proj_mats"], "proj_mats")[0, torch.as_tensor(depth_vid, dtype=torch.long, device=dimgs.device)][:, :nv]
+    proj = gpu_f32(batch["proj_mats"], "proj_mats")[0, torch.as_tensor(depth_vid, dtype=torch.long, device=dimgs.device)][:, :nv]
     feats = net.image_features(dimgs[0, :nv])
     depth, conf, _, _ = net(dimgs[:, :nv].expand(len(depth_vid), -1, -1, -1, -1), proj, depth_values.expand(len(depth_vid), -1), features=feats)
     near_fars = batch["near_fars"].detach().float().cpu().numpy()[0]

@@ -14,6 +14,7 @@ from torch import nn
 
 from . import _lib
 from ._lib import HnrError
+from ._nets import NormParams, Packed, PackedWeights, filtered_state_dict, host_f32, load_checked
 
 EPS = 1e-5                                                       # InPlaceABN's eps (variance and |weight|)
 SLOPE = 0.01                                                     # its activation_param, and premlp's LeakyReLU
@@ -28,21 +29,11 @@ def pyramid_shape(H, W):
     return (H, W), (H2, W2), ((H2 - 1) // 2 + 1, (W2 - 1) // 2 + 1)
 
 
-class _Abn(nn.Module):
-    """Parameter holder with InPlaceABN's names; its arithmetic lives in the convolution kernel's epilogue."""
-
-    def __init__(self, ch):
-        super().__init__()
-        self.weight, self.bias = nn.Parameter(torch.ones(ch)), nn.Parameter(torch.zeros(ch))
-        self.register_buffer("running_mean", torch.zeros(ch))
-        self.register_buffer("running_var", torch.ones(ch))
-
-
 class _ConvBnReLU(nn.Module):
     def __init__(self, cin, cout, ks, stride):
         super().__init__()
         self.conv = nn.Conv2d(cin, cout, ks, stride=stride, padding=ks // 2, bias=False)
-        self.bn = _Abn(cout)
+        self.bn = NormParams(cout)                                # InPlaceABN's names; its arithmetic: pack_host and the kernel's epilogue
 
 
 def featnet_forward(images, packed):
@@ -115,25 +106,7 @@ def point_embed(xyz, w2c, c2w, cpc, intrinsic, image, x1, x2, x3, premlp, want_r
     return emb, color, pdir, row
 
 
-class _Packed:
-    """A packed copy of a module's weights on the device, rebuilt when a parameter or buffer changes or moves.  A change is seen through the tensors'
-    addresses and in-place version counters: `load_state_dict`, optimiser steps, `.to()` and any other in-place update are covered.  A tensor swapped in
-    through `p.data = other` can, in principle, land on a recycled address with the same counter: call `invalidate()` after such an assignment."""
-
-    def __init__(self):
-        self.key, self.value = None, None
-
-    def invalidate(self):
-        self.key, self.value = None, None
-
-    def get(self, tensors, build):
-        key = tuple((t.data_ptr(), t._version, str(t.device)) for t in tensors)
-        if key != self.key:
-            self.value, self.key = build(), key
-        return self.value
-
-
-class FeatureNet(nn.Module):
+class FeatureNet(PackedWeights, nn.Module):
     """The reference's `FeatureNet(intermediate=True)` in eval mode: its parameter and buffer names, its forward signature, HIP kernels inside."""
 
     def __init__(self):
@@ -141,7 +114,7 @@ class FeatureNet(nn.Module):
         for name, layers in LAYERS:
             setattr(self, name, nn.Sequential(*[_ConvBnReLU(*l) for l in layers]))
         self.toplayer = nn.Conv2d(32, 32, 1)
-        self._packed = _Packed()
+        self._packed = Packed()
 
     def pack_host(self):
         """fp32 [FEATNET_PACKED_ELEMS] on the CPU, the layout of include/hnr.h; mul = rsqrt(running_var + eps) * (|weight| + eps) is folded here, once."""
@@ -149,18 +122,13 @@ class FeatureNet(nn.Module):
         with torch.no_grad():
             for name, _ in LAYERS:
                 for blk in getattr(self, name):
-                    w, bn = blk.conv.weight.detach().float().cpu(), blk.bn
-                    var, gamma = bn.running_var.detach().float().cpu(), bn.weight.detach().float().cpu()
-                    mul = torch.rsqrt(var + EPS) * (gamma.abs() + EPS)
-                    parts += [w.permute(1, 2, 3, 0).reshape(-1), bn.running_mean.detach().float().cpu(), mul, bn.bias.detach().float().cpu()]
-            parts += [self.toplayer.weight.detach().float().cpu().reshape(-1), self.toplayer.bias.detach().float().cpu()]
+                    w, bn = host_f32(blk.conv.weight), blk.bn
+                    mul = torch.rsqrt(host_f32(bn.running_var) + EPS) * (host_f32(bn.weight).abs() + EPS)
+                    parts += [w.permute(1, 2, 3, 0).reshape(-1), host_f32(bn.running_mean), mul, host_f32(bn.bias)]
+            parts += [host_f32(self.toplayer.weight).reshape(-1), host_f32(self.toplayer.bias)]
             out = torch.cat([p.contiguous().reshape(-1) for p in parts])
         assert out.numel() == _lib.FEATNET_PACKED_ELEMS
         return out
-
-    def packed(self):
-        tensors = list(self.parameters()) + list(self.buffers())
-        return self._packed.get(tensors, lambda: self.pack_host().to(self.toplayer.weight.device))
 
     def forward(self, imgs):
         """imgs [B,V,3,H,W] -> [x [B*V,3,H,W], x1, x2, x3] (the reference's `intermediate` return)."""
@@ -213,16 +181,11 @@ class MvsInit(nn.Module):
         self.occlusion = occlusion_tolerance(opt, occlusion, "MvsInit")           # embed_points' default: 0.1 with occlusion=True and opt.depth_occ > 0
         self.FeatureNet = FeatureNet()
         self.premlp = nn.Sequential(nn.Linear(63, 32), nn.LeakyReLU(SLOPE, inplace=True), nn.Linear(32, 32), nn.LeakyReLU(SLOPE, inplace=True))
-        self._packed = _Packed()
+        self._packed = Packed()
 
     def load_state_dict(self, state_dict, strict=True, **kw):
-        sd = {k: v for k, v in state_dict.items() if not k.startswith("MVSNet.") and not k.endswith("num_batches_tracked")}
-        res = super().load_state_dict(sd, strict=False, **kw)
-        if res.missing_keys:
-            raise HnrError("MvsInit.load_state_dict: the checkpoint lacks %s" % ", ".join(sorted(res.missing_keys)))
-        if strict and res.unexpected_keys:
-            raise HnrError("MvsInit.load_state_dict: unexpected keys %s (pass strict=False to ignore them)" % ", ".join(sorted(res.unexpected_keys)))
-        return res
+        sd = filtered_state_dict(state_dict, strip=None, drop_prefixes=("MVSNet.",))
+        return load_checked(self, sd, "MvsInit.load_state_dict", strict, " (pass strict=False to ignore them)", **kw)
 
     def premlp_packed(self):
         """[PREMLP_PACKED_ELEMS] on the device: W0^T [63][32], b0, W1^T [32][32], b1."""
@@ -238,7 +201,7 @@ class MvsInit(nn.Module):
         """Drops the packed device copies of both networks' weights; needed only after replacing a parameter's storage with `p.data = ...`
         (in-place updates and load_state_dict are noticed by themselves)."""
         self._packed.invalidate()
-        self.FeatureNet._packed.invalidate()
+        self.FeatureNet.invalidate_packed()
 
     def get_image_features(self, imgs):
         """imgs [B,V,3,H,W] -> [x, x1, x2, x3] (MvsPointsModel.get_image_features)."""

@@ -22,7 +22,7 @@ from torch import nn
 from . import _lib
 from ._lib import HnrError
 from .flow import pack_layer
-from .mvs_init import _Packed
+from ._nets import Packed, PackedWeights, host_f32, load_checkpoint
 
 NETS = {"alex": 0, "vgg": 1}
 MIN_SIZE = {"alex": 31, "vgg": 16}
@@ -51,13 +51,7 @@ def prep_table(shift=SHIFT, scale=SCALE):
     return (v[None, :] - np.asarray(shift, np.float32)[:, None]) / np.asarray(scale, np.float32)[:, None]
 
 
-def _load(obj):
-    if isinstance(obj, (str, bytes)) or hasattr(obj, "__fspath__"):
-        return torch.load(obj, map_location="cpu")
-    return obj
-
-
-class LPIPS(nn.Module):
+class LPIPS(PackedWeights, nn.Module):
     """`lpips.LPIPS(net='alex'|'vgg')` in eval mode; parameters under torchvision's and the package's names (`features.<i>.*`, `lins.<k>.weight`)."""
 
     def __init__(self, net="alex", channel_order="bgr"):
@@ -71,7 +65,7 @@ class LPIPS(nn.Module):
         self.lins = nn.ModuleList([nn.Conv2d(c, 1, 1, bias=False) for c in TAP_CHANNELS[net]])
         self.register_buffer("shift", torch.tensor(SHIFT, dtype=torch.float32))
         self.register_buffer("scale", torch.tensor(SCALE, dtype=torch.float32))
-        self._packed = _Packed()
+        self._packed = Packed()
         self._scratch = {}
         self.loaded = False
         for p in self.parameters():
@@ -89,7 +83,7 @@ class LPIPS(nn.Module):
         duplicates are ignored), `scaling_layer.shift|scale` -- or (b) a torchvision backbone (`features.<i>.weight|bias`; `classifier.*` is ignored)
         plus `lin`: the package's `weights/v0.1/<net>.pth` (`lin<k>.model.1.weight`).  Paths go through torch.load as they are.  A missing key or a
         wrong shape is an HnrError that names the key."""
-        sd = _load(state_dict_or_path)
+        sd = load_checkpoint(state_dict_or_path)
         if not hasattr(sd, "keys"):
             raise HnrError("LPIPS.load_pretrained: expected a state dict or a path to one")
         whole = any(k.startswith("net.slice") for k in sd.keys())
@@ -100,7 +94,7 @@ class LPIPS(nn.Module):
         else:
             if lin is None:
                 raise HnrError("LPIPS.load_pretrained: a torchvision backbone needs `lin`, the package's weights/v0.1/%s.pth" % self.net_name)
-            lin_sd = _load(lin)
+            lin_sd = load_checkpoint(lin)
 
         def take(d, key, shape):
             if key not in d:
@@ -131,7 +125,7 @@ class LPIPS(nn.Module):
 
     def pack_host(self):
         """fp32 [hnr_lpips_packed_elems(net)] on the CPU: the packed image of include/hnr.h."""
-        f = lambda t: t.detach().float().cpu()
+        f = host_f32
         with torch.no_grad():
             parts = [f(self.shift), f(self.scale), torch.zeros(2)]
             for i, *_ in CONVS[self.net_name]:
@@ -144,16 +138,12 @@ class LPIPS(nn.Module):
         """The packed image on the module's device: packed once on the host, again only after the weights changed (load_pretrained, .to())."""
         if not self.loaded:
             raise HnrError("LPIPS: no weights loaded (load_pretrained); the package ships none")
-        tensors = list(self.parameters()) + list(self.buffers())
-        dev = self.shift.device
+        return super().packed()
 
-        def build():
-            pk = self.pack_host()
-            if pk.numel() != int(_lib.lib().hnr_lpips_packed_elems(NETS[self.net_name])):
-                raise HnrError("LPIPS: the packed image has %d elements, the library expects %d" % (
-                    pk.numel(), int(_lib.lib().hnr_lpips_packed_elems(NETS[self.net_name]))))
-            return pk.to(dev)
-        return self._packed.get(tensors, build)
+    def check_packed(self, pk):
+        if pk.numel() != int(_lib.lib().hnr_lpips_packed_elems(NETS[self.net_name])):
+            raise HnrError("LPIPS: the packed image has %d elements, the library expects %d" % (
+                pk.numel(), int(_lib.lib().hnr_lpips_packed_elems(NETS[self.net_name]))))
 
     # ---- plumbing ----------------------------------------------------------------------------------------------------------------------------------
     def _net(self):

@@ -8,33 +8,17 @@ import pytest
 import torch
 
 from tests import cloud_init_ref as R
+from tests.bits import DEV, assert_bits_equal, t
 from tests.golden_io import GOLD
 from tests.test_cloud_init import attr_bounds, backproject_bound, centroid_bound, frame_slices
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda:0"
 
 
 @pytest.fixture(scope="module")
 def gold():
     z = np.load(os.path.join(GOLD, "cloud_init.npz"))
     return {k: z[k] for k in z.files}
-
-
-def bits(a):
-    a = np.ascontiguousarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def assert_bits_equal(got, want):
-    got, want = bits(got), bits(want)
-    assert got.shape == want.shape, (got.shape, want.shape)
-    np.testing.assert_array_equal(got, want)
-
-
-def t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def fuse_one(depth, K, c2w, res, capacity=None, **kw):

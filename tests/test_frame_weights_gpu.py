@@ -18,19 +18,14 @@ import torch
 
 from tests import frame_weights_ref as FR
 from tests import raft_ref as R
+from tests.bits import DEV, t
 from tests.test_frame_weights import fixture, params
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 MARGIN = 4.0
 SHAPES = [0, 1, 2]
 LAST = 21                                                         # the restatement runs 21 iterations: the state after iteration 19 (0-based) is the input of the 21st
-
-
-def t(a, dtype=None):
-    a = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
-    return (a if dtype is None else a.to(dtype)).to(DEV).contiguous()
 
 
 def rule(got, truth, yard, what):

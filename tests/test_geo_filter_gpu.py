@@ -8,26 +8,10 @@ import pytest
 import torch
 
 from tests import geo_filter_ref as R
+from tests.bits import DEV, assert_bits_equal, t
 from tests.test_geo_filter import compare_lists, gold, lists_of, opt_of, restated  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda:0"
-
-
-def bits(a):
-    a = np.ascontiguousarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def assert_bits_equal(got, want):
-    got, want = bits(got), bits(want)
-    assert got.shape == want.shape, (got.shape, want.shape)
-    np.testing.assert_array_equal(got, want)
-
-
-def t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def look_at_w2c(pos, target):

@@ -11,11 +11,11 @@ import pytest
 import torch
 
 from tests import hull_ref as R
+from tests.bits import DEV, assert_bits_equal, t
 from tests.golden_io import GOLD
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 H, W = 40, 56
 RECORDS = [("off_none", False, False), ("on_none", True, False), ("off_nf", False, True), ("on_nf", True, True)]
 OVERFLOW = 1
@@ -49,21 +49,6 @@ def net(gold):
 def occ_flags(gold):
     """the restatement's flags of the o_ scene, computed once"""
     return R.occlusion(gold["o_xyz"], gold["h_w2c"][0], gold["h_K"][0], H, W, float(gold["tolerate"]))
-
-
-def t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def assert_bits_equal(got, want):
-    got, want = bits(got), bits(want)
-    assert got.shape == want.shape, (got.shape, want.shape)
-    np.testing.assert_array_equal(got, want)
 
 
 @pytest.mark.parametrize("M,Hh,Ww", [(5, 40, 56), (1, 40, 56), (3, 7, 64), (1, 1, 1), (2, 3, 300)])

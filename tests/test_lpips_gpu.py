@@ -18,21 +18,16 @@ import pytest
 import torch
 
 from tests import lpips_ref as LR
+from tests.bits import DEV, t
 from tests.test_frame_weights_gpu import MARGIN, rule
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 NETS = ("alex", "vgg")
 SHAPES = {"vgg": ((16, 16), (35, 50), (19, 70)), "alex": ((31, 31), (67, 91), (75, 63))}
 PAIRS = ("ab", "ac")
 ROW = ("d", "r0", "r1", "r2", "r3", "r4")
 BLACK_SHIFT, BLACK_SCALE = (-1.0, -1.0, -1.0), (1.0, 1.0, 1.0)            # a second ScalingLayer under which a black byte is exactly 0
-
-
-def t(a, dtype=None):
-    a = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
-    return (a if dtype is None else a.to(dtype)).to(DEV).contiguous()
 
 
 @functools.lru_cache(maxsize=None)

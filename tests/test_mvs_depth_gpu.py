@@ -19,33 +19,18 @@ import pytest
 import torch
 
 from tests import mvs_depth_ref as R
+from tests.bits import DEV, assert_bits_equal, bits, t
 from tests.test_mvs_depth import load_gold
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 MARGIN = 4.0
 EXTRA = (3, 24, 96, 160)
 CASES = [0, 1, 2, 3, 4]
 
 
-def t(a):
-    return (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))).to(DEV)
-
-
 def f32(x):
     return x.to(torch.float32)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def assert_bits_equal(got, want):
-    got, want = bits(got), bits(want)
-    assert got.shape == want.shape, (got.shape, want.shape)
-    np.testing.assert_array_equal(got, want)
 
 
 def rule(got, truth, yard, what, sel=None):

@@ -12,12 +12,12 @@ import pytest
 import torch
 
 from tests import mvs_init_ref as MR
+from tests.bits import DEV, assert_bits_equal, t
 from tests.golden_io import GOLD
 from tests.test_cloud_init import attr_bounds
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 MARGIN = 4.0
 U = 2.0 ** -24
 
@@ -36,21 +36,6 @@ def net(gold):
     m = MvsInit()
     m.load_state_dict(gold["sd"], strict=False)
     return m.to(DEV)
-
-
-def t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def assert_bits_equal(got, want):
-    got, want = bits(got), bits(want)
-    assert got.shape == want.shape, (got.shape, want.shape)
-    np.testing.assert_array_equal(got, want)
 
 
 def check_levels(got, truth, yard, what):
