@@ -30,4 +30,7 @@ def __getattr__(name):
     if name in ("content_aware_weights", "weights_from_scores"):
         from . import frame_weights
         return getattr(frame_weights, name)
+    if name in ("DeviceAdam", "ShellOptimizers"):
+        from . import optim
+        return getattr(optim, name)
     raise AttributeError(name)

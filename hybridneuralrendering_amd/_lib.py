@@ -115,6 +115,14 @@ class FrameBatchOut(ctypes.Structure):
     _fields_ = [("d_" + n, _P) for n in FRAME_OUTPUTS]
 
 
+ADAM_MAX_GROUPS, ADAM_MAX_TENSORS, ADAM_CHUNK, ADAM_GROUP_DOUBLES, ADAM_ROW_DOUBLES = 4, 4096, 4096, 6, 10     # HNR_ADAM_*
+
+
+class AdamTensor(ctypes.Structure):
+    """hnr_adam_tensor"""
+    _fields_ = [("p", _P), ("g", _P), ("m", _P), ("v", _P), ("n", ctypes.c_int64), ("group", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 RENDER_STAGES = ("query", "plan_gather", "chain_gather", "chain", "mlp_colorfeat", "proj_rows", "mlp_merge", "merge", "mlp_mixup", "final_color",
                  "composite")
 
@@ -256,6 +264,9 @@ SIGNATURES = {
                             ctypes.POINTER(FrameBatchOut), _P, ctypes.c_int64, _P]),
     # growth schedule: ray-miss loss + the table of the worst frames, one launch per step (csrc/rank.hip)
     "hnr_ray_miss_rank": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _P, _P]),
+    # the optimiser step: Adam for all parameter groups in one launch + the schedule tick (csrc/adam.hip)
+    "hnr_adam_plan": (ctypes.c_int64, [ctypes.POINTER(AdamTensor), _I, _I, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64]),
+    "hnr_adam_step": (_I, [_P, _P, _I, _P, _P, _I, _P, ctypes.c_int64, _P]),
     "hnr_blur_gray_patches": (_I, [_P, _P, _I, _I, _P, _P]),
     "hnr_blur_gray_patches_bwd": (_I, [_P, _I, _I, _P, _P]),
     "hnr_blur_apply": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),

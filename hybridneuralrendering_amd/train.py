@@ -451,7 +451,7 @@ def _assign_grads(aggregator, emb, conf, pdir, color, pg, ag, accumulate=True, c
 def train_step(path, aggregator, xyz, emb, conf, pdir, color, raydir, campos, camrot, bg_color, near, far, c2w_nearest, campos_nearest,
                intrinsic_nearest, images_nearest, gt_image, zero_epsilon=1e-3, w_color=1.0, w_zero_one=1e-4, frame_weight=None, tmid=None,
                ray_drop=None, assign_grads=True, frame_weight_nearest=None, blur_kernels=None, patch_num=None, patch_size=None, patch_layout="grid",
-               w2c_nearest=None, accumulate_grads=True, device_frame_weight=None):
+               w2c_nearest=None, accumulate_grads=True, device_frame_weight=None, optimizer=None):
     """forward -> [blur module] -> shipped loss terms -> backward of one ray batch as groups of library launches queued back to back: no autograd
     graph, no masked copies, nothing read back to the host -- the body of the reference's optimize_parameters before its optimizer steps
     (models/neural_points_volumetric_model.py:202-214: self.forward(); loss_total.backward(), with compute_losses of
@@ -471,14 +471,23 @@ def train_step(path, aggregator, xyz, emb, conf, pdir, color, raydir, campos, ca
 
     emb/conf/pdir/color and the aggregator's parameters are read as they are; with assign_grads their .grad fields are set (or added to,
     as autograd does -- also under TrainPath.reuse_outputs, where a .grad is then a private copy of the step's buffer, never the buffer the next
-    step overwrites; accumulate_grads=False assigns the step's own buffers instead: no copy, valid until the next step).  Returns (outputs dict with `loss` = {total, colour MSE, zero-one mean, valid rays} on the device and `_saved` = the step's
+    step overwrites; accumulate_grads=False assigns the step's own buffers instead: no copy, valid until the next step).
+
+    optimizer (optim.DeviceAdam / optim.ShellOptimizers; None: exactly the path above): the optimiser step and the schedule tick are queued behind the
+    backward on the same stream -- two more launches that read `pg` / `ag` in place -- and .grad is NOT assigned (the reference's
+    optimizer.step() + neural_point_optimizer.step() + scheduler.step(), models/mvs_points_volumetric_model.py:111-131, models/base_model.py:148-150).
+    The parameters' `_version` is bumped, so the renderer's caches follow the new weights.  With TrainPath.reuse_outputs the gradient buffers keep
+    their addresses and the optimiser's descriptor table is uploaded once; without it, once per step.  Returns (outputs dict with `loss` = {total, colour MSE, zero-one mean, valid rays} on the device and `_saved` = the step's
     state for TrainPath.touched_points / the flat weight-gradient buffer, point grads dict, aggregator grads dict keyed by parameter name)."""
     cloud = PointCloud(xyz, emb.detach(), conf.detach(), pdir.detach(), color.detach())
     out, S, pg, ag = _queue_step(path, cloud, raydir, campos, camrot, bg_color, near, far, c2w_nearest, campos_nearest, intrinsic_nearest, images_nearest,
                                  gt_image, zero_epsilon, w_color, w_zero_one, frame_weight, tmid, ray_drop, frame_weight_nearest,
                                  _blur_arg(blur_kernels, patch_num, patch_size, patch_layout), w2c_nearest, device_frame_weight=device_frame_weight)
     out["_saved"] = S
-    if assign_grads:
+    if optimizer is not None:
+        from .optim import merge_grads
+        optimizer.step(merge_grads(pg, ag))
+    elif assign_grads:
         _assign_grads(aggregator, emb, conf, pdir, color, pg, ag, accumulate=bool(accumulate_grads), cached=bool(path.reuse_outputs))
     return out, pg, ag
 
@@ -497,12 +506,20 @@ class CapturedTrainStep:
     (torch.rand under capture advances the registered generator state on every replay: a fresh jitter per step, as at
     models/neural_points/query_point_indices_worldcoords.py:87).  The weights and the point buffers are read through the pointers they had at capture:
     optimisers that update in place are fine; after prune / grow (new buffers) build a new CapturedTrainStep.  Outputs and gradients are static
-    tensors overwritten by every replay."""
+    tensors overwritten by every replay.
+
+    optimizer (optim.DeviceAdam / optim.ShellOptimizers; None: the graph ends with the backward, as before): the optimiser step and the schedule tick
+    are captured behind the backward -- one replay = one whole iteration -- and .grad is never assigned.  The warm-up steps run WITHOUT the
+    optimiser (they must not move the parameters); its descriptor table is uploaded before the capture, which needs the gradient buffers'
+    addresses then: TrainPath.reuse_outputs is switched on for the path.  `step()` bumps the parameters' `_version` after the replay."""
 
     def __init__(self, path, aggregator, xyz, emb, conf, pdir, color, sample, near, far, zero_epsilon=1e-3, w_color=1.0, w_zero_one=1e-4,
-                 patch_num=None, patch_size=None, patch_layout="grid", warmup=2):
+                 patch_num=None, patch_size=None, patch_layout="grid", warmup=2, optimizer=None):
         """sample: dict of example input tensors (see the class docstring) that fixes shapes and optional inputs."""
         self.path, self.agg = path, aggregator
+        self.optimizer = optimizer
+        if optimizer is not None:
+            path.reuse_outputs = True
         self.leaves = (emb, conf, pdir, color)
         dev = xyz.device
         req = ("raydir", "campos", "camrot", "bg_color", "c2w_nearest", "campos_nearest", "intrinsic_nearest", "images_nearest", "gt_image")
@@ -528,12 +545,17 @@ class CapturedTrainStep:
         with torch.cuda.stream(side):
             for _ in range(max(1, int(warmup))):       # lazy one-time work of the library (kernel attributes, side streams, the grid) happens here, not under capture
                 out, _S, _pg, _ag = body()
+            if optimizer is not None:
+                from .optim import merge_grads
+                optimizer.prepare(merge_grads(_pg, _ag))   # (the table for the reused gradient buffers + the kernels' first launch: nothing of the state moves)
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         TrainPath.check_status(out)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph, stream=side, capture_error_mode="thread_local"):
             self.out, self.S, self.pg, self.ag = body()
+            if optimizer is not None:
+                optimizer.step(merge_grads(self.pg, self.ag))
         self.out["_saved"] = self.S
 
     def step(self, assign_grads=True, frame_weight=None, **tensors):
@@ -548,7 +570,9 @@ class CapturedTrainStep:
         if frame_weight is not None:
             self.inputs["frame_weight"].fill_(float(frame_weight))
         self.graph.replay()
-        if assign_grads:
+        if self.optimizer is not None:
+            self.optimizer.mark_updated()              # the replay wrote the parameters behind torch's back: the caches keyed on _version must see it
+        elif assign_grads:
             emb, conf, pdir, color = self.leaves
             _assign_grads(self.agg, emb, conf, pdir, color, self.pg, self.ag, accumulate=False)
         return self.out, self.pg, self.ag

@@ -27,7 +27,7 @@
  *              hnr_featnet_*, hnr_point_embed*, hnr_geo_consistency, hnr_geo_filter_select*, hnr_mvsnet_*,
  *              hnr_alpha_pack, hnr_visual_hull_select*, hnr_point_occlusion*, hnr_point_view_attrs_vis,
  *              hnr_frame_batch*, hnr_frame_item, hnr_ray_miss_rank, hnr_raft_flow*, hnr_blur_score_pair* (hnr_blur_edges and the other hnr_raft_*
- *              entries are STAGE).
+ *              entries are STAGE), hnr_adam_plan, hnr_adam_step.
  *   STAGE   -- everything else (hnr_chain_*, hnr_mlp3_*, hnr_merge*, hnr_mixup_stage, hnr_proj_*, hnr_h2*, hnr_linear_*, hnr_gather_*, hnr_ksum*,
  *              hnr_segment_*, hnr_absmax, hnr_div_probe, hnr_image_features_bwd_bbox, ...): the individual stages the two single-call entries are built from.  They are exported so
  *              that tests/ can compare every stage with the oracle and so that tools/ can time them alone; their signatures, workspace layouts and
@@ -1274,6 +1274,58 @@ int hnr_lpips(int net, const uint8_t *d_img8, const uint8_t *d_gt8, int h, int w
               int64_t scratch_bytes, void *stream);
 int hnr_lpips_f32(int net, const float *d_in0, const float *d_in1, int h, int w, const float *d_packed, double *d_row, void *d_scratch,
                   int64_t scratch_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The optimiser step (csrc/adam.hip): Adam for every tensor of up to HNR_ADAM_MAX_GROUPS parameter groups in ONE launch, behind one single-thread
+ * launch that advances the counters and evaluates the learning-rate schedule.  Replaces `self.optimizer.step()` and
+ * `self.neural_point_optimizer.step()` of MvsPointsVolumetricModel.backward (models/mvs_points_volumetric_model.py:111-131; both built by
+ * setup_optimizer, :94-104: torch.optim.Adam, betas (0.9, 0.999), no weight decay, no amsgrad) and `scheduler.step()` of
+ * BaseModel.update_learning_rate (models/base_model.py:148-150) for lr_policy 'iter_exponential_decay' (models/helpers/networks.py:56-61:
+ * LambdaLR, lambda_rule(it) = pow(lr_decay_exp, it / lr_decay_iters)).  Stream-ordered; no host value enters a step, nothing is allocated, nothing
+ * is read back, no atomics: the launches can be captured in a graph that serves every step, and two runs give the same bits.
+ *
+ * State the caller owns, all in device memory:
+ *   d_counters [2] int64 = {adam_step, sched_it}: Adam's bias-correction count (torch's state['step']) and the schedule's iteration (the number
+ *     of scheduler.step() calls so far: iteration n, 1-based, runs with sched_it = n - 1; init_scheduler(total_steps) sets it to total_steps).
+ *   d_groups [n_groups][HNR_ADAM_GROUP_DOUBLES] fp64 = {lr0, beta1, beta2, eps, decay_exp, decay_iters} (decay_exp 1, decay_iters 1: constant lr).
+ *   d_rows [n_groups][HNR_ADAM_ROW_DOUBLES] fp64, written by the tick = {lr_t, bc1, bc2, lr_t / bc1, sqrt(bc2), 1 - beta1, 1 - beta2, beta2, eps,
+ *     step} with lr_t = lr0 * decay_exp^(sched_it_before / decay_iters), bc1 = 1 - beta1^step, bc2 = 1 - beta2^step, step = adam_step after
+ *     the increment.
+ *   d_tensors [n_tensors] hnr_adam_tensor: parameter, gradient, first and second moment (4-byte aligned, n elements each, not overlapping) and
+ *     the tensor's group.  d_chunks [n_chunks][2] int32 = (tensor, chunk within the tensor): one workgroup per HNR_ADAM_CHUNK elements.
+ *
+ * Element arithmetic: fp32, every operation rounded on its own, divide and sqrt correctly rounded, in the order of torch's _single_tensor_adam;
+ * the six scalars are rounded to fp32 once from the fp64 row:
+ *     w1 = f32(1 - beta1)  w2 = f32(1 - beta2)  b2 = f32(beta2)  e = f32(eps)  ss = f32(lr_t / bc1)  bs = f32(sqrt(bc2))
+ *     m' = m + w1 * (g - m);   v' = (v * b2) + ((w2 * g) * g);   den = (sqrt(v') / bs) + e;   p' = p - ss * (m' / den)
+ * Every element is updated, zero gradient or not (Adam's momentum moves it); an element with m = v = g = 0 keeps its bits.  Subnormal
+ * intermediates are kept; NaN / inf gradients propagate into m, v and p, as in torch.  16 bytes per lane where p, g, m, v of a tensor are all
+ * 16-byte aligned, 4 bytes per lane otherwise.
+ *
+ * hnr_adam_plan -- HOST only: checks a host copy of the tensor table (HNR_ERR_BADARG for a NULL or misaligned pointer, a negative count, a group
+ *   outside [0, n_groups)) and returns the number of chunks; with `chunks` != NULL it also writes the table (chunk_cap entries of two int32).
+ *   Upload both tables once; they change only when a pointer does.
+ * hnr_adam_step -- the tick launch (counters and rows), then the update launch (reads the tables and d_rows only): one optimiser step; every
+ *   argument is checked before the first launch.
+ * HNR_ERR_BADARG, before any launch, for a NULL or misaligned pointer, n_groups outside 1..HNR_ADAM_MAX_GROUPS, n_tensors outside
+ * 1..HNR_ADAM_MAX_TENSORS or a negative n_chunks. */
+#define HNR_ADAM_MAX_GROUPS     4
+#define HNR_ADAM_MAX_TENSORS    4096
+#define HNR_ADAM_CHUNK          4096
+#define HNR_ADAM_GROUP_DOUBLES  6
+#define HNR_ADAM_ROW_DOUBLES    10
+typedef struct {
+    float *p;
+    const float *g;
+    float *m;
+    float *v;
+    int64_t n;
+    int32_t group;
+    int32_t reserved;
+} hnr_adam_tensor;
+int64_t hnr_adam_plan(const hnr_adam_tensor *tensors, int n_tensors, int n_groups, int32_t *chunks, int64_t chunk_cap);
+int hnr_adam_step(int64_t *d_counters, const double *d_groups, int n_groups, double *d_rows, const hnr_adam_tensor *d_tensors, int n_tensors,
+                  const int32_t *d_chunks, int64_t n_chunks, void *stream);
 
 #ifdef __cplusplus
 }
