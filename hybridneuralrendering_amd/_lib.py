@@ -123,6 +123,16 @@ class AdamTensor(ctypes.Structure):
     _fields_ = [("p", _P), ("g", _P), ("m", _P), ("v", _P), ("n", ctypes.c_int64), ("group", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class BlurLearnParams(ctypes.Structure):
+    """hnr_blur_learn_params"""
+    _fields_ = [(n, _I) for n in ("patch_num", "patch_size", "kernel_size", "kernel_mode", "kernel_norm", "boundary_mode")] + [("slope", _F)]
+
+
+class BlurLearnWeights(ctypes.Structure):
+    """hnr_blur_learn_weights: Linear l's weight [out, in] and bias; the gradient block has the same layout."""
+    _fields_ = [("w", _P * 4), ("b", _P * 4)]
+
+
 RENDER_STAGES = ("query", "plan_gather", "chain_gather", "chain", "mlp_colorfeat", "proj_rows", "mlp_merge", "merge", "mlp_mixup", "final_color",
                  "composite")
 
@@ -271,6 +281,11 @@ SIGNATURES = {
     "hnr_blur_gray_patches_bwd": (_I, [_P, _I, _I, _P, _P]),
     "hnr_blur_apply": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "hnr_blur_apply_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    # the learnable blur module as three launches (train_step(learnable_blur=...))
+    "hnr_blur_learn_workspace_bytes": (ctypes.c_int64, [_I, _I, _I, _I]),
+    "hnr_blur_learn_forward": (_I, [ctypes.POINTER(BlurLearnParams), ctypes.POINTER(BlurLearnWeights), _P, _P, _P, ctypes.c_int64, _P, _P, _P]),
+    "hnr_blur_learn_backward": (_I, [ctypes.POINTER(BlurLearnParams), ctypes.POINTER(BlurLearnWeights), _P, _P, _P, ctypes.c_int64, _P,
+                                     ctypes.POINTER(BlurLearnWeights), _P]),
     # backward
     "hnr_composite_bwd": (_I, [_P] * 8 + [_I, _I, _I, _F, _I, _P, _P, _P]),
     "hnr_composite_bwd_depth": (_I, [_P] * 8 + [_I, _I, _I, _F, _I, _P, _P, _P, _P]),

@@ -6,6 +6,8 @@ which the training shell calls between the render and the losses when `add_blur_
 active (mvs_points_volumetric_model.py:145-146).  One HIP block per patch replaces the two F.conv2d calls, the 5-D
 tile/abs/sum, the fancy indexing and the Python re-assembly loop; the backward goes through the selected kernel only.
 """
+import ctypes
+
 import torch
 
 from . import _lib
@@ -177,3 +179,141 @@ def learnable_blur_update_output(coarse_raycolor, gt_image, blur_predictor, opt,
         raise HnrError("boundary_mode %d is not implemented by the reference either (:924-932)" % bm)
     out = _BlurApply.apply(coarse_raycolor, k, pn, ps, bm)
     return (out, k) if return_kernels else out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The same module as three launches for the training step that builds no autograd graph (train.train_step(learnable_blur=...))
+# ----------------------------------------------------------------------------------------------------------------------
+BLUR_PARAM_PREFIX = "learn_blur_kernel_block."
+
+
+class LearnableBlur:
+    """learnable_blur_update_output and its backward as three library launches (hnr_blur_learn_forward: grey patches, the predictor's four layers
+    and sigmoid, normalisation, identity blend, per-patch convolution; hnr_blur_learn_backward: the way back per patch, then the weight and bias
+    gradients), with no autograd graph, no .grad and every buffer allocated once -- what train.train_step / train.CapturedTrainStep take as
+    `learnable_blur=`.
+
+    aggregator_or_mlp: the PointAggregator (its `learn_blur_kernel_block`) or the predictor itself: nn.Sequential(Linear(2 ps^2, 128), LeakyReLU,
+    Linear(128, 128), LeakyReLU, Linear(128, 128), LeakyReLU, Linear(128, ks^2 + e), Sigmoid), e = 1 for learnable_blur_kernel_mode 4 and 0 for mode 0.
+    opt fields read: learnable_blur_kernel_size (odd, <= 15), learnable_blur_kernel_norm (0 / 1), learnable_blur_kernel_mode (0 / 4), boundary_mode
+    (0 / 1 / 2), learnable_blur_kernel_conv.  patch_num / patch_size (<= 16) / layout as for learnable_blur_update_output: layout="patch_major" takes
+    `patch_num` whole patches packed (patch, y, x).  Everything is checked on the host before any device memory is asked for; an unsupported option
+    raises HnrError.
+
+    The weights are read through the parameters' own pointers on every call (no packed copy): an optimiser that updates them in place, and a captured
+    graph that replays these launches, need no notification.  The output, kernel, gradient and workspace buffers are allocated at the first forward
+    and overwritten by every later one (one step in flight at a time).
+
+    Out of scope:
+      * the conv-block predictor (learnable_blur_kernel_conv=1): learnable_blur_update_output stays the path for it;
+      * sharded training: parallel.allreduce_weight_grads' flat buffer does not contain the predictor's eight gradients -- a caller that shards the
+        batch by patches (layout="patch_major") all-reduces the eight tensors `backward` returns itself;
+      * bench.py / hnr_bench do not time this module."""
+
+    def __init__(self, aggregator_or_mlp, opt, patch_num, patch_size, layout="grid"):
+        mlp = aggregator_or_mlp
+        if not isinstance(mlp, torch.nn.Sequential):
+            mlp = getattr(mlp, "learn_blur_kernel_block", mlp)             # the aggregator: its predictor (None when learnable_blur_kernel=0)
+        if getattr(opt, "learnable_blur_kernel_conv", 0):
+            raise HnrError("LearnableBlur: the conv-block predictor (learnable_blur_kernel_conv=1) is not covered; use "
+                           "blur.learnable_blur_update_output, which stays the path for that option")
+        ks, ps = int(opt.learnable_blur_kernel_size), int(patch_size)
+        mode, norm, bm = (int(getattr(opt, k, 0)) for k in ("learnable_blur_kernel_mode", "learnable_blur_kernel_norm", "boundary_mode"))
+        if mode not in (0, 4):
+            raise HnrError("LearnableBlur: learnable_blur_kernel_mode %d is not implemented (0 and 4 are; the reference has no other either, :911-912)" % mode)
+        if norm not in (0, 1):
+            raise HnrError("LearnableBlur: learnable_blur_kernel_norm %d is not implemented (0: divide by the sum, 1: softmax)" % norm)
+        if bm not in (0, 1, 2):
+            raise HnrError("LearnableBlur: boundary_mode %d is not implemented by the reference either (:924-932)" % bm)
+        if not (1 <= ps <= 16) or ks < 1 or ks > 15 or ks % 2 == 0:
+            raise HnrError("LearnableBlur: patch_size must be 1..16 and learnable_blur_kernel_size odd and <= 15 (got %d, %d)" % (ps, ks))
+        self.pn = _pn(patch_num, layout)
+        if int(patch_num) < 1:
+            raise HnrError("LearnableBlur: patch_num must be >= 1")
+        n_in, n_out = 2 * ps * ps, ks * ks + (1 if mode == 4 else 0)
+        nn = torch.nn
+        want = [(n_in, 128), (128, 128), (128, 128), (128, n_out)]
+        ok = isinstance(mlp, nn.Sequential) and len(mlp) == 8 and isinstance(mlp[7], nn.Sigmoid)
+        ok = ok and all(isinstance(mlp[2 * l], nn.Linear) and mlp[2 * l].bias is not None and
+                        (mlp[2 * l].in_features, mlp[2 * l].out_features) == want[l] for l in range(4))
+        ok = ok and all(isinstance(mlp[2 * l + 1], nn.LeakyReLU) for l in range(3))
+        ok = ok and len({float(mlp[2 * l + 1].negative_slope) for l in range(3)}) == 1
+        if not ok:
+            raise HnrError("LearnableBlur: the predictor must be Linear(%d, 128), LeakyReLU, Linear(128, 128), LeakyReLU, Linear(128, 128), LeakyReLU, "
+                           "Linear(128, %d), Sigmoid (patch_size %d, kernel size %d, mode %d); got %s"
+                           % (n_in, n_out, ps, ks, mode, type(mlp).__name__ if not isinstance(mlp, nn.Sequential) else [type(m).__name__ for m in mlp]))
+        self.mlp, self.ps, self.ks, self.mode, self.n_in, self.n_out = mlp, ps, ks, mode, n_in, n_out
+        self.n_patches = -self.pn if self.pn < 0 else self.pn * self.pn
+        self.rays = self.n_patches * ps * ps
+        self.prm = _lib.BlurLearnParams(self.pn, ps, ks, mode, norm, bm, float(mlp[1].negative_slope))
+        self.names = [BLUR_PARAM_PREFIX + "%d.%s" % (2 * l, k) for l in range(4) for k in ("weight", "bias")]
+        self._buf = None
+        self._wkey = None
+        self._color = None
+
+    def parameters(self):
+        """{parameter name under the aggregator: tensor}, in layer order."""
+        return {BLUR_PARAM_PREFIX + "%d.%s" % (2 * l, k): getattr(self.mlp[2 * l], k) for l in range(4) for k in ("weight", "bias")}
+
+    def _weights(self):
+        ps = [getattr(self.mlp[2 * l], k) for l in range(4) for k in ("weight", "bias")]
+        key = tuple(q.data_ptr() for q in ps)
+        if key != self._wkey:
+            for q in ps:
+                if not (q.is_cuda and q.dtype == torch.float32 and q.is_contiguous()):
+                    raise HnrError("LearnableBlur: the predictor's parameters must be contiguous float32 tensors on the GPU (no CPU fallback)")
+            w = _lib.BlurLearnWeights()
+            for l in range(4):
+                w.w[l], w.b[l] = ps[2 * l].data_ptr(), ps[2 * l + 1].data_ptr()
+            self._w, self._wkey = w, key
+        return self._w
+
+    def _buffers(self, dev):
+        if self._buf is None or self._buf["dev"] != dev:
+            L = _lib.lib()
+            nbytes = int(L.hnr_blur_learn_workspace_bytes(self.n_patches, self.ps, self.ks, self.mode))
+            if nbytes < 0:
+                _lib.check(nbytes, "hnr_blur_learn_workspace_bytes")
+            f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+            grads = {n: f(*q.shape) for n, q in self.parameters().items()}
+            gw = _lib.BlurLearnWeights()
+            for l in range(4):
+                gw.w[l] = grads[BLUR_PARAM_PREFIX + "%d.weight" % (2 * l)].data_ptr()
+                gw.b[l] = grads[BLUR_PARAM_PREFIX + "%d.bias" % (2 * l)].data_ptr()
+            self._buf = dict(dev=dev, ws=torch.empty((nbytes,), dtype=torch.uint8, device=dev), nbytes=nbytes, out=f(self.rays, 3),
+                             kernels=f(self.n_patches, self.ks, self.ks), g_color=f(self.rays, 3), grads=grads, gw=gw)
+        return self._buf
+
+    def _rays(self, t, name):
+        t = _lib.require_gpu(t.detach(), name, torch.float32).reshape(-1, 3)
+        if t.shape[0] != self.rays:
+            raise HnrError("LearnableBlur: expected %d patches of %dx%d rays, got %d rays in %s" % (self.n_patches, self.ps, self.ps, t.shape[0], name))
+        return t
+
+    def forward(self, color, gt):
+        """New colours [rays, 3] (a buffer the next forward overwrites); `self.kernels` [n_patches, ks, ks] then holds the final kernels."""
+        L = _lib.lib()
+        c, g = self._rays(color, "coarse_raycolor"), self._rays(gt, "gt_image")
+        w, b = self._weights(), self._buffers(c.device)
+        with torch.cuda.device(c.device):
+            _lib.check(L.hnr_blur_learn_forward(ctypes.byref(self.prm), ctypes.byref(w), _lib.ptr(c), _lib.ptr(g), _lib.ptr(b["ws"]), b["nbytes"],
+                                                _lib.ptr(b["out"]), _lib.ptr(b["kernels"]), _lib.stream()), "hnr_blur_learn_forward")
+        self._color = c
+        return b["out"]
+
+    @property
+    def kernels(self):
+        return None if self._buf is None else self._buf["kernels"]
+
+    def backward(self, g_out):
+        """(d loss / d rendered colours [rays, 3] = convolution path + grey-patch path, {aggregator parameter name: gradient}) for the last forward;
+        the gradients are written (not accumulated) into the same eight buffers every time."""
+        L = _lib.lib()
+        if self._color is None:
+            raise HnrError("LearnableBlur.backward: no forward to go back through")
+        g = self._rays(g_out, "grad")
+        w, b = self._weights(), self._buffers(g.device)
+        with torch.cuda.device(g.device):
+            _lib.check(L.hnr_blur_learn_backward(ctypes.byref(self.prm), ctypes.byref(w), _lib.ptr(self._color), _lib.ptr(g), _lib.ptr(b["ws"]),
+                                                 b["nbytes"], _lib.ptr(b["g_color"]), ctypes.byref(b["gw"]), _lib.stream()), "hnr_blur_learn_backward")
+        return b["g_color"], b["grads"]

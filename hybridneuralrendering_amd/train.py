@@ -391,9 +391,11 @@ def render_train(path, aggregator, xyz, emb, conf, pdir, color, raydir, campos, 
 
 
 def _queue_step(path, cloud, raydir, campos, camrot, bg_color, near, far, c2w_nearest, campos_nearest, intrinsic_nearest, images_nearest, gt_image,
-                zero_epsilon, w_color, w_zero_one, frame_weight, tmid, ray_drop, frame_weight_nearest, blur, w2c_nearest, device_frame_weight=None):
+                zero_epsilon, w_color, w_zero_one, frame_weight, tmid, ray_drop, frame_weight_nearest, blur, w2c_nearest, device_frame_weight=None,
+                learnable_blur=None):
     """The launches of one step, queued back to back on the current stream: forward -> [blur module] -> loss kernels -> [blur module backward] ->
-    backward.  Nothing is read back; shared by train_step (eager) and CapturedTrainStep (inside a hipGraph capture)."""
+    backward.  Nothing is read back; shared by train_step (eager) and CapturedTrainStep (inside a hipGraph capture).  learnable_blur
+    (blur.LearnableBlur): the learnable-kernel form of the blur module in the same two places; its eight gradients join `ag`."""
     from .losses import shipped_loss_grads
     from .blur import blur_select, blur_select_bwd
     out, S = path.forward(cloud, raydir, campos, camrot, bg_color, near, far, c2w_nearest, campos_nearest, intrinsic_nearest, images_nearest,
@@ -405,16 +407,37 @@ def _queue_step(path, cloud, raydir, campos, camrot, bg_color, near, far, c2w_ne
         # blurred render is closest to the ground truth replaces the render before the losses
         kernels, pn, ps = blur
         col, sel, kk = blur_select(col, gt_image, kernels, pn, ps)
+    elif learnable_blur is not None:
+        # learnable_blur_kernel=1 (models/mvs_points_volumetric_model.py:143-144 -> base_rendering_model.py:827-1020): one launch
+        col = learnable_blur.forward(col, gt_image)
     parts, g_col, g_cc = shipped_loss_grads(col, out["conf_coefficient"], gt_image, out["ray_mask"], zero_epsilon, w_color, w_zero_one, frame_weight,
                                             conf_rows=True, device_frame_weight=device_frame_weight)
     if blur is not None:
         g_col = blur_select_bwd(g_col, kk, sel, pn, ps)
+    elif learnable_blur is not None:
+        g_col, g_blur = learnable_blur.backward(g_col)        # two launches: per patch, then the weight / bias gradients
     pg, ag = path.backward(S, g_col, g_cc)
     out = dict(out)
     out["loss"] = parts
     if blur is not None:
         out["blurred_raycolor"], out["blur_select"] = col, sel
+    elif learnable_blur is not None:
+        ag = dict(ag)
+        ag.update(g_blur)                                     # under the aggregator's parameter names: merge_grads / _assign_grads need no special case
+        out["blurred_raycolor"], out["blur_kernels_pred"] = col, learnable_blur.kernels
     return out, S, pg, ag
+
+
+def _learnable_arg(who, blur_kernels, learnable_blur):
+    if learnable_blur is None:
+        return None
+    if blur_kernels is not None:
+        raise HnrError("%s: blur_kernels (add_blur_sim=1) and learnable_blur (learnable_blur_kernel=1) are two branches of one step "
+                       "(models/mvs_points_volumetric_model.py:143-147); give one of them" % who)
+    from .blur import LearnableBlur
+    if not isinstance(learnable_blur, LearnableBlur):
+        raise HnrError("%s: learnable_blur must be a blur.LearnableBlur" % who)
+    return learnable_blur
 
 
 def _blur_arg(blur_kernels, patch_num, patch_size, patch_layout):
@@ -451,7 +474,7 @@ def _assign_grads(aggregator, emb, conf, pdir, color, pg, ag, accumulate=True, c
 def train_step(path, aggregator, xyz, emb, conf, pdir, color, raydir, campos, camrot, bg_color, near, far, c2w_nearest, campos_nearest,
                intrinsic_nearest, images_nearest, gt_image, zero_epsilon=1e-3, w_color=1.0, w_zero_one=1e-4, frame_weight=None, tmid=None,
                ray_drop=None, assign_grads=True, frame_weight_nearest=None, blur_kernels=None, patch_num=None, patch_size=None, patch_layout="grid",
-               w2c_nearest=None, accumulate_grads=True, device_frame_weight=None, optimizer=None):
+               w2c_nearest=None, accumulate_grads=True, device_frame_weight=None, optimizer=None, learnable_blur=None):
     """forward -> [blur module] -> shipped loss terms -> backward of one ray batch as groups of library launches queued back to back: no autograd
     graph, no masked copies, nothing read back to the host -- the body of the reference's optimize_parameters before its optimizer steps
     (models/neural_points_volumetric_model.py:202-214: self.forward(); loss_total.backward(), with compute_losses of
@@ -473,16 +496,30 @@ def train_step(path, aggregator, xyz, emb, conf, pdir, color, raydir, campos, ca
     as autograd does -- also under TrainPath.reuse_outputs, where a .grad is then a private copy of the step's buffer, never the buffer the next
     step overwrites; accumulate_grads=False assigns the step's own buffers instead: no copy, valid until the next step).
 
+    learnable_blur (a blur.LearnableBlur; not together with blur_kernels -- the reference's shell takes one of the two branches,
+    models/mvs_points_volumetric_model.py:143-147): the learnable-kernel blur module (learnable_blur_kernel=1, base_rendering_model.py:827-1020) in the
+    same two places -- hnr_blur_learn_forward before the loss kernels, hnr_blur_learn_backward (two launches) behind them.  Its eight gradients join the
+    aggregator's under their parameter names (`learn_blur_kernel_block.0.weight` ...), so .grad or the optimiser sees them like every other one; the
+    outputs gain `blurred_raycolor` and `blur_kernels_pred` [n_patches, ks, ks] (the module's static buffers, overwritten by its next forward; the eight
+    gradients are the module's static buffers too under TrainPath.reuse_outputs and copies otherwise).  Same arithmetic as render_train + blur.learnable_blur_update_output +
+    the loss + loss.backward() up to summation order.  Not covered: the conv-block predictor; and in sharded training the predictor's gradients are
+    not part of parallel.allreduce_weight_grads' flat buffer -- the caller all-reduces those eight tensors.  None: exactly the launches above.
+
     optimizer (optim.DeviceAdam / optim.ShellOptimizers; None: exactly the path above): the optimiser step and the schedule tick are queued behind the
     backward on the same stream -- two more launches that read `pg` / `ag` in place -- and .grad is NOT assigned (the reference's
     optimizer.step() + neural_point_optimizer.step() + scheduler.step(), models/mvs_points_volumetric_model.py:111-131, models/base_model.py:148-150).
     The parameters' `_version` is bumped, so the renderer's caches follow the new weights.  With TrainPath.reuse_outputs the gradient buffers keep
     their addresses and the optimiser's descriptor table is uploaded once; without it, once per step.  Returns (outputs dict with `loss` = {total, colour MSE, zero-one mean, valid rays} on the device and `_saved` = the step's
     state for TrainPath.touched_points / the flat weight-gradient buffer, point grads dict, aggregator grads dict keyed by parameter name)."""
+    learnable_blur = _learnable_arg("train_step", blur_kernels, learnable_blur)
     cloud = PointCloud(xyz, emb.detach(), conf.detach(), pdir.detach(), color.detach())
     out, S, pg, ag = _queue_step(path, cloud, raydir, campos, camrot, bg_color, near, far, c2w_nearest, campos_nearest, intrinsic_nearest, images_nearest,
                                  gt_image, zero_epsilon, w_color, w_zero_one, frame_weight, tmid, ray_drop, frame_weight_nearest,
-                                 _blur_arg(blur_kernels, patch_num, patch_size, patch_layout), w2c_nearest, device_frame_weight=device_frame_weight)
+                                 _blur_arg(blur_kernels, patch_num, patch_size, patch_layout), w2c_nearest, device_frame_weight=device_frame_weight,
+                                 learnable_blur=learnable_blur)
+    if learnable_blur is not None and not path.reuse_outputs:
+        # LearnableBlur writes into its own static buffers; without reuse_outputs a step hands out gradient tensors of its own (240 KB)
+        ag.update({n: ag[n].clone() for n in learnable_blur.names})
     out["_saved"] = S
     if optimizer is not None:
         from .optim import merge_grads
@@ -514,8 +551,10 @@ class CapturedTrainStep:
     addresses then: TrainPath.reuse_outputs is switched on for the path.  `step()` bumps the parameters' `_version` after the replay."""
 
     def __init__(self, path, aggregator, xyz, emb, conf, pdir, color, sample, near, far, zero_epsilon=1e-3, w_color=1.0, w_zero_one=1e-4,
-                 patch_num=None, patch_size=None, patch_layout="grid", warmup=2, optimizer=None):
-        """sample: dict of example input tensors (see the class docstring) that fixes shapes and optional inputs."""
+                 patch_num=None, patch_size=None, patch_layout="grid", warmup=2, optimizer=None, learnable_blur=None):
+        """sample: dict of example input tensors (see the class docstring) that fixes shapes and optional inputs.  learnable_blur: as for
+        train_step (not together with a `blur_kernels` sample input); its buffers are static, so `blur_kernels_pred` follows every replay."""
+        learnable_blur = _learnable_arg("CapturedTrainStep", sample.get("blur_kernels"), learnable_blur)
         self.path, self.agg = path, aggregator
         self.optimizer = optimizer
         if optimizer is not None:
@@ -539,7 +578,8 @@ class CapturedTrainStep:
         def body():
             return _queue_step(path, cloud, st["raydir"], st["campos"], st["camrot"], st["bg_color"], near, far, st["c2w_nearest"], st["campos_nearest"],
                                st["intrinsic_nearest"], st["images_nearest"], st["gt_image"], zero_epsilon, w_color, w_zero_one, None, st.get("tmid"),
-                               st.get("ray_drop"), st.get("frame_weight_nearest"), blur, st["w2c_nearest"], device_frame_weight=st["frame_weight"])
+                               st.get("ray_drop"), st.get("frame_weight_nearest"), blur, st["w2c_nearest"], device_frame_weight=st["frame_weight"],
+                               learnable_blur=learnable_blur)
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):

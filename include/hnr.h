@@ -754,6 +754,40 @@ int hnr_blur_apply(const float *d_color, const float *d_kernels, int kernel_size
 int hnr_blur_apply_bwd(const float *d_g_out, const float *d_color, const float *d_kernels, int kernel_size, int patch_num, int patch_size,
                        int boundary_mode, float *d_g_color, float *d_g_kernels, void *stream);
 
+/* The whole learnable blur module as three launches, for the training step without an autograd graph (train.train_step(learnable_blur=...)):
+ * grey patches -> predictor Linear(2 ps^2, 128) LeakyReLU Linear(128, 128) LeakyReLU Linear(128, 128) LeakyReLU Linear(128, ks^2 + e) Sigmoid
+ * (point_aggregators.py:1339-1344 without the conv block; e = 1 for kernel_mode 4, 0 for kernel_mode 0) -> normalisation (kernel_norm 0: divide by the
+ * sum, 1: softmax, :895-899) -> kernel_mode 4: blend with the identity kernel by the last output and renormalise (:904-909) -> every patch convolved
+ * with its kernel under boundary_mode 0 / 1 / 2 (:915-923).  All fp32, plain FMAs in a fixed order, no atomics: two runs give the same bits.
+ *   hnr_blur_learn_weights   w[l] [out_l, in_l] row-major and b[l] [out_l] of Linear l = 0..3, nn.Linear's own layout, read through the
+ *                            parameters' own pointers (no packed copy: an optimiser that updates in place needs no notification).  The gradient
+ *                            block has the same layout and is written, not accumulated.
+ *   hnr_blur_learn_forward   one launch.  d_color / d_gt / d_out [rays, 3], ray layout and the patch_num < 0 (patch-major) convention as for
+ *                            hnr_blur_select.  d_ws (hnr_blur_learn_workspace_bytes, 16-byte aligned) receives what the backward reads: the grey
+ *                            patches, the three hidden activations, the prediction and the final kernels.  d_kernels [n_patches, ks, ks]: optional
+ *                            copy of the final kernels (NULL: none).
+ *   hnr_blur_learn_backward  two launches.  (a) per patch: d_g_out [rays, 3] through the convolution (gradients w.r.t. the colours and the
+ *                            kernel; boundary_mode 2 sends none through the mask term), the kernel gradient through the renormalisation, the
+ *                            blend, the normalisation, the sigmoid and the four layers (LeakyReLU's derivative from the sign of its stored output)
+ *                            down to the grey rendered patch; d_g_color [rays, 3] = convolution path + grey-patch path; every layer's delta rows
+ *                            go to the workspace.  (b) dW_l[o][i] = sum_p delta_l[p][o] a_(l-1)[p][i], db_l[o] = sum_p delta_l[p][o], p ascending,
+ *                            one fp32 FMA chain per element.  d_color and the workspace must be what the forward call saw / left.
+ * slope: LeakyReLU's negative slope.  kernel_size odd, <= 15; patch_size <= 16.  Not covered: the conv-block predictor
+ * (learnable_blur_kernel_conv), which stays with hnr_blur_gray_patches / hnr_blur_apply and torch in between. */
+typedef struct {
+    int patch_num, patch_size, kernel_size, kernel_mode, kernel_norm, boundary_mode;
+    float slope;
+} hnr_blur_learn_params;
+typedef struct {
+    float *w[4];
+    float *b[4];
+} hnr_blur_learn_weights;
+int64_t hnr_blur_learn_workspace_bytes(int n_patches, int patch_size, int kernel_size, int kernel_mode);
+int hnr_blur_learn_forward(const hnr_blur_learn_params *prm, const hnr_blur_learn_weights *weights, const float *d_color, const float *d_gt,
+                           void *d_ws, int64_t ws_bytes, float *d_out, float *d_kernels, void *stream);
+int hnr_blur_learn_backward(const hnr_blur_learn_params *prm, const hnr_blur_learn_weights *weights, const float *d_color, const float *d_g_out,
+                            void *d_ws, int64_t ws_bytes, float *d_g_color, const hnr_blur_learn_weights *grads, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * "Next" row (second half): the loss terms of the shipped training configurations, value + gradients.
  * BaseRenderingModel.compute_losses, models/base_rendering_model.py: colour item `ray_masked_coarse_raycolor` (:1113-1118:
