@@ -300,6 +300,19 @@ SIGNATURES = {
     "hnr_gather_rows_bwd_rows": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
     "hnr_segment_sum_rows_det": (_I, [_P, _I, _P, _P, ctypes.c_int64, _I, _I, _P, _P, ctypes.c_int64, _I, _P]),
     "hnr_segment_sum_rows_csr": (_I, [_P, _I, _P, _P, _P, _I, _I, _P, ctypes.c_int64, _P, _I, _I, _P, ctypes.c_int64, _P, _P]),
+    # the glue kernels of the training backward, each alone (tests/test_backward_glue_gpu.py)
+    "hnr_final_color_bwd_max": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P]),
+    "hnr_ksum_bwd_rows8": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _F, _I, _P, _P, _P, _P, _P, _P]),
+    "hnr_extras_dgrad": (_I, [_P, _P, _P, ctypes.c_int64, _P, _P]),
+    "hnr_point_small_grads": (_I, [_P, _P, _I, _P, _P, _P, _P, _P]),
+    "hnr_point_rows_bwd": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P]),
+    "hnr_dleaky_add": (_I, [_P, _I, _P, _I, _I, _P, _I, ctypes.c_int64, _P, _I, _F, _P, _P]),
+    "hnr_sum_views": (_I, [_P, _I, _I, _I, _P, _I, _P, _I, _P, _P]),
+    "hnr_unique_points_scratch_elems": (ctypes.c_int64, [_I]),
+    "hnr_unique_points": (_I, [_P, ctypes.c_int64, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "hnr_conf0_grad": (_I, [_P, _P, ctypes.c_int64, _P, _P, _P]),
+    "hnr_w0fd_grad": (_I, [_P, _P, _P]),
+    "hnr_ray_drop_flags": (_I, [_P, _I, _P, _P, _P, _P]),
     "hnr_probe_select": (_I, [_P, _P, _P, _P, ctypes.POINTER(_F), _P, _P, _I, _I, _I, _F, _F, _P, _P, _P]),
     # training-step dense layers on the 16-bit matrix pipe (csrc/h2gemm.hip)
     "hnr_h2lin_packed_bytes": (ctypes.c_int64, [_I]),

@@ -1232,3 +1232,65 @@ int sum_views_dc(const float *d_in, int ldi, int V, int cap, const long long *d_
     return HNR_OK;
 }
 }  // namespace hnr
+
+// ------------------------------------------------------------------------------------------------ STAGE exports of the glue kernels
+// (include/hnr.h; tests/test_backward_glue_gpu.py drives each alone).  Thin wrappers: the argument checks of the header's convention, then the function the
+// training step calls, with the step's grid.
+static inline bool mis16(const void *p) { return ((uintptr_t)p & 15) != 0; }
+
+extern "C" int hnr_final_color_bwd_max(const float *d_Y, int ldy, const float *d_CF, int ldcf, const float *d_w_fin, const float *d_b_fin,
+                                       const int32_t *d_vs_item, const int64_t *d_counts, int cap_samples, const float *d_g_decoded,
+                                       float *d_gY, int ldgy, float *d_gCF, int ldgcf, float *d_g_sigma, float *d_g_w_fin, float *d_g_b_fin,
+                                       uint32_t *d_gY_max, void *stream)
+{
+    if (!d_gY_max || cap_samples < 0 || mis16(d_g_decoded)) { set_error("hnr_final_color_bwd_max: bad argument (NULL d_gY_max: hnr_final_color_bwd is the form without it)"); return HNR_ERR_BADARG; }
+    return hnr::final_color_bwd_max(d_Y, ldy, d_CF, ldcf, d_w_fin, d_b_fin, d_vs_item, d_counts, cap_samples, d_g_decoded, d_gY, ldgy, d_gCF, ldgcf, d_g_sigma, d_g_w_fin,
+                                    d_g_b_fin, d_gY_max, stream);
+}
+
+extern "C" int hnr_point_small_grads(const float *d_P8, const int32_t *d_ulist, int U_cap, const int64_t *d_u, float *d_g_conf, float *d_g_dir, float *d_g_color,
+                                     void *stream)
+{
+    if (!d_P8 || !d_ulist || !d_g_conf || !d_g_dir || !d_g_color || U_cap < 0 || mis16(d_P8)) { set_error("hnr_point_small_grads: bad argument"); return HNR_ERR_BADARG; }
+    return point_small_grads_dc(d_P8, d_ulist, U_cap, reinterpret_cast<const long long *>(d_u), d_g_conf, d_g_dir, d_g_color, (hipStream_t)stream);
+}
+
+extern "C" int hnr_point_rows_bwd(const float *d_gE, int ldg, const float *d_E, int lde, const int32_t *d_ids, int n_cap, const int64_t *d_n, float *d_g_emb,
+                                  void *stream)
+{
+    if (!d_gE || !d_E || !d_g_emb || n_cap < 0 || ldg < 224 || lde < 224) { set_error("hnr_point_rows_bwd: bad argument (rows of 224 columns)"); return HNR_ERR_BADARG; }
+    return point_rows_bwd_dc(d_gE, ldg, d_E, lde, d_ids, n_cap, reinterpret_cast<const long long *>(d_n), d_g_emb, (hipStream_t)stream);
+}
+
+extern "C" int hnr_dleaky_add(float *d_g, int ldg, const float *d_add, int lda, int n_add, const float *d_y, int ldy, int64_t M_cap, const int64_t *d_m, int N,
+                              float slope, uint32_t *d_absmax, void *stream)
+{
+    // (the kernel reads whole float4s of the addend below n_add: its rows must hold n_add rounded up to 4)
+    if (!d_g || !d_y || M_cap < 0 || N <= 0 || (N & 3) || ldg < N || ldy < N || (ldg & 3) || (ldy & 3) || mis16(d_g) || mis16(d_y) ||
+        (d_add && (n_add < 0 || n_add > N || lda < ((n_add + 3) & ~3) || (lda & 3) || mis16(d_add)))) {
+        set_error("hnr_dleaky_add: bad argument (N > 0, N and the row strides multiples of 4, 16-byte aligned rows)"); return HNR_ERR_BADARG;
+    }
+    return dleaky_add_dc(d_g, ldg, d_add, lda, n_add, d_y, ldy, M_cap, reinterpret_cast<const long long *>(d_m), N, slope, d_absmax, (hipStream_t)stream);
+}
+
+extern "C" int hnr_sum_views(const float *d_in, int ldi, int V, int cap, const int64_t *d_n, int N, float *d_out, int ldo, uint32_t *d_absmax, void *stream)
+{
+    if (!d_in || !d_out || V <= 0 || cap < 0 || N <= 0 || (N & 3) || ldi < N || ldo < N || (ldi & 3) || (ldo & 3) || mis16(d_in) || mis16(d_out)) {
+        set_error("hnr_sum_views: bad argument (V > 0, N > 0, N and the row strides multiples of 4, 16-byte aligned rows)"); return HNR_ERR_BADARG;
+    }
+    return sum_views_dc(d_in, ldi, V, cap, reinterpret_cast<const long long *>(d_n), N, d_out, ldo, d_absmax, (hipStream_t)stream);
+}
+
+extern "C" int64_t hnr_unique_points_scratch_elems(int n_points) { return n_points > 0 ? 2 * (int64_t)cdiv(n_points, 1024) : -1; }
+
+extern "C" int hnr_unique_points(const int32_t *d_row_pid, int64_t M_cap, const int64_t *d_m, int n_points, int32_t *d_uidx, int32_t *d_ulist, int cap,
+                                 int32_t *d_row_u, int32_t *d_count, int32_t *d_scratch, int32_t *d_seg_start, int32_t *d_seg_count, int32_t *d_row_list,
+                                 void *stream)
+{
+    if (!d_row_pid || !d_m || !d_uidx || !d_ulist || !d_row_u || !d_count || !d_scratch || !d_seg_start || !d_seg_count || !d_row_list || M_cap < 0 ||
+        M_cap > INT32_MAX || n_points <= 0 || cap <= 0) {
+        set_error("hnr_unique_points: bad argument"); return HNR_ERR_BADARG;
+    }
+    return unique_points_dc(d_row_pid, M_cap, reinterpret_cast<const long long *>(d_m), n_points, d_uidx, d_ulist, cap, d_row_u, d_count, d_scratch, d_seg_start,
+                            d_seg_count, d_row_list, (hipStream_t)stream);
+}

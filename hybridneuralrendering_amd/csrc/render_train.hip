@@ -877,3 +877,65 @@ extern "C" int hnr_render_train_backward_depth(const hnr_train_params *p, const 
     return train_backward("hnr_render_train_backward_depth", p, cl, w, cam, vw, d_workspace, workspace_bytes, o, d_g_raycolor, d_g_conf_coefficient, d_g_depth,
                           gc, gw_, stream);
 }
+
+// ------------------------------------------------------------------------------------------------ STAGE exports of the step's small kernels
+// (include/hnr.h; tests/test_backward_glue_gpu.py drives each alone): the argument checks of the header's convention, then the launch of the step.
+static inline bool mis16(const void *p) { return ((uintptr_t)p & 15) != 0; }
+
+extern "C" int hnr_ksum_bwd_rows8(const float *d_H4, const void *d_aux, const float *d_alpha_w, const float *d_alpha_b, const int64_t *d_counts,
+                                  const float *d_gX5, int ldg5, const float *d_g_sigma, float slope, int cap_samples, float *d_gZ4, float *d_g_wagg,
+                                  float *d_g_alpha_w, float *d_g_alpha_b, uint32_t *d_absmax, void *stream)
+{
+    if (!d_H4 || !d_aux || !d_alpha_w || !d_alpha_b || !d_counts || !d_gX5 || !d_g_sigma || !d_gZ4 || !d_g_wagg || !d_g_alpha_w || !d_g_alpha_b || !d_absmax ||
+        cap_samples < 0 || ldg5 < 256 || (ldg5 & 3) || mis16(d_H4) || mis16(d_alpha_w) || mis16(d_gX5) || mis16(d_gZ4) || ((uintptr_t)d_aux & 3)) {
+        set_error("hnr_ksum_bwd_rows8: bad argument (ldg5 >= 256, a multiple of 4; 16-byte aligned rows)"); return HNR_ERR_BADARG;
+    }
+    if (cap_samples == 0) return HNR_OK;
+    KsumPadArgs a;
+    a.H4 = d_H4; a.aux = (const char *)d_aux; a.alpha_w = d_alpha_w; a.alpha_b = d_alpha_b;
+    a.counts = reinterpret_cast<const unsigned long long *>(d_counts); a.gX5 = d_gX5; a.ldg5 = ldg5; a.g_sigma = d_g_sigma; a.slope = slope;
+    a.gZ4 = d_gZ4; a.g_wagg = d_g_wagg; a.g_alpha_w = d_g_alpha_w; a.g_alpha_b = d_g_alpha_b; a.absmax = d_absmax;
+    int nb = cdiv(cap_samples, 16); if (nb > 512) nb = 512; if (nb < 1) nb = 1;
+    train_ksum_bwd_kernel<<<nb, 1024, 0, (hipStream_t)stream>>>(a);
+    HNR_LAUNCH_CHECK();
+    return HNR_OK;
+}
+
+extern "C" int hnr_extras_dgrad(const float *d_dZ3, const float *d_w30, const int64_t *d_m, int64_t rows_cap, float *d_gX3, void *stream)
+{
+    if (!d_dZ3 || !d_w30 || !d_m || !d_gX3 || rows_cap < 0 || rows_cap > INT32_MAX || mis16(d_dZ3) || mis16(d_gX3)) {
+        set_error("hnr_extras_dgrad: bad argument (16-byte aligned rows)"); return HNR_ERR_BADARG;
+    }
+    if (rows_cap == 0) return HNR_OK;
+    int nb = cdiv(rows_cap, 16); if (nb > 2048) nb = 2048;
+    train_extras_dgrad_kernel<<<nb, 256, 0, (hipStream_t)stream>>>(d_dZ3, d_w30, reinterpret_cast<const long long *>(d_m), d_gX3);
+    HNR_LAUNCH_CHECK();
+    return HNR_OK;
+}
+
+extern "C" int hnr_conf0_grad(const float *d_g_conf_out, const int32_t *d_sample_pidx, int64_t n, float *d_scratch512, float *d_g_conf, void *stream)
+{
+    if (!d_g_conf_out || !d_sample_pidx || !d_scratch512 || !d_g_conf || n < 0) { set_error("hnr_conf0_grad: bad argument"); return HNR_ERR_BADARG; }
+    if (n == 0) return HNR_OK;
+    train_conf0_partial_kernel<<<512, 256, 0, (hipStream_t)stream>>>(d_g_conf_out, d_sample_pidx, (long long)n, d_scratch512);
+    train_conf0_final_kernel<<<1, 256, 0, (hipStream_t)stream>>>(d_scratch512, 512, d_g_conf);
+    HNR_LAUNCH_CHECK();
+    return HNR_OK;
+}
+
+extern "C" int hnr_w0fd_grad(const float *d_g, float *d_gw0, void *stream)
+{
+    if (!d_g || !d_gw0) { set_error("hnr_w0fd_grad: NULL argument"); return HNR_ERR_BADARG; }
+    train_w0fd_grad_kernel<<<(64 * 48 + 255) / 256, 256, 0, (hipStream_t)stream>>>(d_g, d_gw0);
+    HNR_LAUNCH_CHECK();
+    return HNR_OK;
+}
+
+extern "C" int hnr_ray_drop_flags(const int8_t *d_ray_mask, int R, const uint8_t *d_lut, const uint8_t *d_explicit_flags, uint8_t *d_out, void *stream)
+{
+    if (!d_ray_mask || !d_out || R < 0) { set_error("hnr_ray_drop_flags: bad argument"); return HNR_ERR_BADARG; }
+    if (R == 0) return HNR_OK;
+    train_ray_drop_kernel<<<1, 1024, 0, (hipStream_t)stream>>>(d_ray_mask, R, d_lut, d_explicit_flags, d_out);
+    HNR_LAUNCH_CHECK();
+    return HNR_OK;
+}

@@ -29,7 +29,9 @@
  *              hnr_frame_batch*, hnr_frame_item, hnr_ray_miss_rank, hnr_raft_flow*, hnr_blur_score_pair* (hnr_blur_edges and the other hnr_raft_*
  *              entries are STAGE), hnr_adam_plan, hnr_adam_step.
  *   STAGE   -- everything else (hnr_chain_*, hnr_mlp3_*, hnr_merge*, hnr_mixup_stage, hnr_proj_*, hnr_h2*, hnr_linear_*, hnr_gather_*, hnr_ksum*,
- *              hnr_segment_*, hnr_absmax, hnr_div_probe, hnr_image_features_bwd_bbox, ...): the individual stages the two single-call entries are built from.  They are exported so
+ *              hnr_segment_*, hnr_absmax, hnr_div_probe, hnr_image_features_bwd_bbox, the glue kernels of the training backward -- hnr_final_color_bwd*,
+ *              hnr_ksum_bwd_rows8, hnr_extras_dgrad, hnr_point_small_grads, hnr_point_rows_bwd, hnr_dleaky_add, hnr_sum_views, hnr_unique_points*,
+ *              hnr_conf0_grad, hnr_w0fd_grad, hnr_ray_drop_flags -- ...): the individual stages the two single-call entries are built from.  They are exported so
  *              that tests/ can compare every stage with the oracle and so that tools/ can time them alone; their signatures, workspace layouts and
  *              packed-image formats follow the kernels and MAY CHANGE from one version to the next (round 4 changed what hnr_chain_forward leaves
  *              in the workspace's row scalars, for example).  Do not bind to them from outside this repository.
@@ -555,6 +557,54 @@ int hnr_segment_sum_rows_det(const float *d_A, int lda, const int32_t *d_keys_so
 int hnr_segment_sum_rows_csr(const float *d_A, int lda, const int32_t *d_row_list, const int32_t *d_seg_start, const int32_t *d_seg_count,
                              int n_cols, int n_keys, float *d_dst, int64_t dst_stride, const float *d_A2, int lda2, int n_cols2,
                              float *d_dst2, int64_t dst_stride2, uint32_t *d_absmax, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Test hooks: the small kernels BETWEEN the heavy stages of hnr_render_train_backward, each alone with the grid the step gives it
+ * (tests/test_backward_glue_gpu.py compares every one with float64).  "d_n / d_m / d_u" are device-side int64 counts, clamped to the
+ * capacity argument (NULL where marked optional: the capacity is the count).  A capacity of 0 launches nothing.
+ */
+/* hnr_final_color_bwd, and *d_gY_max = max(*d_gY_max, max |d_gY[s < n_valid, 0:45]|) as a bit pattern (exponent-exact, csrc/hnr_common.h absmax_publish). */
+int hnr_final_color_bwd_max(const float *d_Y, int ldy, const float *d_CF, int ldcf, const float *d_w_fin, const float *d_b_fin,
+                            const int32_t *d_vs_item, const int64_t *d_counts, int cap_samples, const float *d_g_decoded,
+                            float *d_gY, int ldgy, float *d_gCF, int ldgcf, float *d_g_sigma, float *d_g_w_fin, float *d_g_b_fin,
+                            uint32_t *d_gY_max, void *stream);
+/* Alpha branch + K-weighted sums transposed, 8 row slots per sample (row = 8 s + k, s < d_counts[HNR_CNT_SAMPLES_VALID] <= cap_samples).  d_aux: per 32-row group
+ * 1280 bytes {int32 pid[32]; float w[32]; 1024 bytes unused here}.  Slot with pid >= 0, h = d_H4[row, 0:256]:  y = h . alpha_w + alpha_b - 1;
+ * da = w g_sigma[s] sigmoid(y);  d_gZ4[row] = (w gX5[s] + da alpha_w) * (h > 0 ? 1 : slope);  d_g_wagg[row] = softplus(y) g_sigma[s] + h . gX5[s];
+ * d_g_alpha_w += da h, d_g_alpha_b += da (atomics).  Empty slots: zeros.  *d_absmax = max(*d_absmax, max |d_gZ4|) (required). */
+int hnr_ksum_bwd_rows8(const float *d_H4, const void *d_aux, const float *d_alpha_w, const float *d_alpha_b, const int64_t *d_counts,
+                       const float *d_gX5, int ldg5, const float *d_g_sigma, float slope, int cap_samples, float *d_gZ4, float *d_g_wagg,
+                       float *d_g_alpha_w, float *d_g_alpha_b, uint32_t *d_absmax, void *stream);
+/* d_gX3[row, 256 + e] = sum_n d_dZ3[row, n] d_w30[n, 256 + e] for e < 7, d_gX3[row, 263] = 0, rows < *d_m <= rows_cap; d_dZ3 [rows,256], d_w30 [256,263],
+ * d_gX3 [rows,264] (columns 0..255 untouched). */
+int hnr_extras_dgrad(const float *d_dZ3, const float *d_w30, const int64_t *d_m, int64_t rows_cap, float *d_gX3, void *stream);
+/* p = d_ulist[u], u < *d_u (optional) <= U_cap:  g_color[p] += P8[u, 0:3], g_dir[p] += P8[u, 3:6], g_conf[p] += P8[u, 6]. */
+int hnr_point_small_grads(const float *d_P8, const int32_t *d_ulist, int U_cap, const int64_t *d_u, float *d_g_conf, float *d_g_dir, float *d_g_color,
+                          void *stream);
+/* hnr_point_rows transposed (F = 32), p = d_ids ? d_ids[u] : u, u < *d_n (optional) <= n_cap, E = the forward's row:
+ * d_g_emb[p, d] += gE[u, d] + sum_{f<3} 2^f (E[u, c + 1] gE[u, c] - E[u, c] gE[u, c + 1]),  c = 32 + 2 (3 d + f)  (E[c] = sin, E[c + 1] = cos). */
+int hnr_point_rows_bwd(const float *d_gE, int ldg, const float *d_E, int lde, const int32_t *d_ids, int n_cap, const int64_t *d_n, float *d_g_emb,
+                       void *stream);
+/* g[m, n] = (g[m, n] + (d_add && n < n_add ? add[m, n] : 0)) * (y[m, n] > 0 ? 1 : slope), m < *d_m (optional) <= M_cap, n < N; optional
+ * *d_absmax = max(*d_absmax, max |g|).  N and the strides multiples of 4; lda >= n_add rounded up to 4. */
+int hnr_dleaky_add(float *d_g, int ldg, const float *d_add, int lda, int n_add, const float *d_y, int ldy, int64_t M_cap, const int64_t *d_m, int N,
+                   float slope, uint32_t *d_absmax, void *stream);
+/* out[s, 0:N] = sum_{v < V} in[v cap + s, 0:N] (added in view order), s < *d_n (optional) <= cap; optional *d_absmax = max(*d_absmax, max |out|). */
+int hnr_sum_views(const float *d_in, int ldi, int V, int cap, const int64_t *d_n, int N, float *d_out, int ldo, uint32_t *d_absmax, void *stream);
+/* The touched points of the rows m < *d_m <= M_cap with d_row_pid[m] >= 0, without a sort: d_uidx[n_points] = compact index (ascending by point id) or -1;
+ * d_ulist[u] = point id and d_seg_start[u] = first entry of its rows in d_row_list, for u < cap (d_seg_start[count] closes the list when count <= cap);
+ * *d_count = number of touched points (may exceed cap); d_seg_count[u < cap] = rows of point u; d_row_u[m < M_cap] = compact index of the row's point,
+ * `cap` for skipped rows; d_row_list: each point's rows, in any order within its segment.  d_scratch: hnr_unique_points_scratch_elems(n_points) int32. */
+int64_t hnr_unique_points_scratch_elems(int n_points);
+int hnr_unique_points(const int32_t *d_row_pid, int64_t M_cap, const int64_t *d_m, int n_points, int32_t *d_uidx, int32_t *d_ulist, int cap,
+                      int32_t *d_row_u, int32_t *d_count, int32_t *d_scratch, int32_t *d_seg_start, int32_t *d_seg_count, int32_t *d_row_list,
+                      void *stream);
+/* d_g_conf[0] += sum of d_g_conf_out[i] over the i < n with d_sample_pidx[i] < 0, in a fixed order; d_scratch512: 512 floats. */
+int hnr_conf0_grad(const float *d_g_conf_out, const int32_t *d_sample_pidx, int64_t n, float *d_scratch512, float *d_g_conf, void *stream);
+/* d_gw0[n, k < 45 ? k : k + 128] = d_g[n, k], n < 64, k < 48: d_g [64,48] -> columns 0..44 and 173..175 of d_gw0 [64,176]. */
+int hnr_w0fd_grad(const float *d_g, float *d_gw0, void *stream);
+/* d_out[r] = mask[r] > 0 && (d_explicit_flags ? d_explicit_flags[r] : d_lut && d_lut[number of r' < r with mask[r'] > 0]), r < R (one workgroup). */
+int hnr_ray_drop_flags(const int8_t *d_ray_mask, int R, const uint8_t *d_lut, const uint8_t *d_explicit_flags, uint8_t *d_out, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Dense layers of the TRAINING step on the 16-bit matrix pipe (csrc/h2gemm.hip), fp32 in / fp32 out, the chain's two-term fp16 split

@@ -385,6 +385,59 @@ def test_c_abi_rejects_bad_arguments_without_touching_the_gpu():
     assert L.hnr_mixup_stage(one16, 92, one16, one16, 128, one, one, one, one, one, 0, ctypes.c_float(0.01), null, 0, one16, null) == 0       # nothing to do
     assert L.hnr_voxel_downsample(one, 10, None, ctypes.c_float(0.1), one, one, one, null, one, one, 1 << 20, null) == bad     # no space_min
     assert L.hnr_voxel_downsample(one, 10, (ctypes.c_float * 3)(0, 0, 0), ctypes.c_float(0.0), one, one, one, null, one, one, 1 << 20, null) == bad
+    # the glue kernels of the training backward (STAGE test hooks): NULL, sizes the kernel divides by, float4 alignment; capacity 0 = nothing to do
+    odd = ctypes.c_void_p(0x1004)                               # 4-byte but not 16-byte aligned
+    sl = ctypes.c_float(0.01)
+
+    def refused(name, rc):
+        assert rc == bad, name
+        assert name.encode() in L.hnr_last_error(), (name, L.hnr_last_error())
+
+    fc = [one16, 48, one16, 128, one, one, one, one, 10, one16, one16, 48, one16, 128, one, one, one]
+    refused("hnr_final_color_bwd", L.hnr_final_color_bwd_max(*(fc + [null, null])))                       # the word is what this entry is for
+    refused("hnr_final_color_bwd", L.hnr_final_color_bwd_max(*(fc[:1] + [44] + fc[2:] + [one, null])))    # ldy < 45
+    refused("hnr_final_color_bwd", L.hnr_final_color_bwd_max(*(fc[:9] + [odd] + fc[10:] + [one, null])))  # float4 reads of g_decoded
+    assert L.hnr_final_color_bwd_max(*(fc[:8] + [0] + fc[9:] + [one, null])) == 0
+    ks = [one16, one, one16, one, one, one16, 256, one, sl, 10, one16, one, one, one, one, null]
+    refused("hnr_ksum_bwd_rows8", L.hnr_ksum_bwd_rows8(*(ks[:1] + [null] + ks[2:])))                      # no aux
+    refused("hnr_ksum_bwd_rows8", L.hnr_ksum_bwd_rows8(*(ks[:6] + [255] + ks[7:])))                       # ldg5
+    refused("hnr_ksum_bwd_rows8", L.hnr_ksum_bwd_rows8(*(ks[:10] + [odd] + ks[11:])))                     # gZ4 rows are float4 stores
+    refused("hnr_ksum_bwd_rows8", L.hnr_ksum_bwd_rows8(*(ks[:14] + [null, null])))                        # the maximum's word is not optional
+    assert L.hnr_ksum_bwd_rows8(*(ks[:9] + [0] + ks[10:])) == 0
+    refused("hnr_extras_dgrad", L.hnr_extras_dgrad(one16, one, null, 32, one16, null))                     # the row count lives on the device
+    refused("hnr_extras_dgrad", L.hnr_extras_dgrad(odd, one, one, 32, one16, null))
+    refused("hnr_extras_dgrad", L.hnr_extras_dgrad(one16, one, one, -1, one16, null))
+    assert L.hnr_extras_dgrad(one16, one, one, 0, one16, null) == 0
+    refused("hnr_point_small_grads", L.hnr_point_small_grads(one16, null, 5, null, one, one, one, null))
+    refused("hnr_point_small_grads", L.hnr_point_small_grads(odd, one, 5, null, one, one, one, null))
+    assert L.hnr_point_small_grads(one16, one, 0, null, one, one, one, null) == 0
+    refused("hnr_point_rows_bwd", L.hnr_point_rows_bwd(one, 223, one, 224, null, 5, null, one, null))
+    refused("hnr_point_rows_bwd", L.hnr_point_rows_bwd(one, 224, one, 224, null, 5, null, null, null))
+    assert L.hnr_point_rows_bwd(one, 224, one, 224, null, 0, null, one, null) == 0
+    refused("hnr_dleaky_add", L.hnr_dleaky_add(one16, 128, null, 0, 0, one16, 128, 8, null, 0, sl, null, null))          # N = 0: 256 % (N / 4)
+    refused("hnr_dleaky_add", L.hnr_dleaky_add(one16, 128, null, 0, 0, one16, 128, 8, null, 126, sl, null, null))        # N % 4
+    refused("hnr_dleaky_add", L.hnr_dleaky_add(one16, 128, one16, 44, 45, one16, 128, 8, null, 128, sl, null, null))     # addend rows shorter than its last float4
+    refused("hnr_dleaky_add", L.hnr_dleaky_add(one16, 128, odd, 128, 128, one16, 128, 8, null, 128, sl, null, null))
+    refused("hnr_dleaky_add", L.hnr_dleaky_add(null, 128, null, 0, 0, one16, 128, 8, null, 128, sl, null, null))
+    assert L.hnr_dleaky_add(one16, 128, null, 0, 0, one16, 128, 0, null, 128, sl, null, null) == 0
+    refused("hnr_sum_views", L.hnr_sum_views(one16, 64, 0, 10, null, 64, one16, 64, null, null))                         # V
+    refused("hnr_sum_views", L.hnr_sum_views(one16, 64, 4, 10, null, 0, one16, 64, null, null))                          # N = 0
+    refused("hnr_sum_views", L.hnr_sum_views(one16, 62, 4, 10, null, 64, one16, 64, null, null))
+    refused("hnr_sum_views", L.hnr_sum_views(one16, 64, 4, 10, null, 64, odd, 64, null, null))
+    assert L.hnr_sum_views(one16, 64, 4, 0, null, 64, one16, 64, null, null) == 0
+    up = [one, 8, one, 100, one, one, 8, one, one, one, one, one, one, null]
+    refused("hnr_unique_points", L.hnr_unique_points(*(up[:2] + [null] + up[3:])))                        # the device-count form only
+    refused("hnr_unique_points", L.hnr_unique_points(*(up[:3] + [0] + up[4:])))                           # n_points sizes the scan's grid
+    refused("hnr_unique_points", L.hnr_unique_points(*(up[:6] + [0] + up[7:])))
+    refused("hnr_unique_points", L.hnr_unique_points(*(up[:12] + [null, null])))
+    assert L.hnr_unique_points_scratch_elems(1025) == 4 and L.hnr_unique_points_scratch_elems(0) == -1
+    refused("hnr_conf0_grad", L.hnr_conf0_grad(one, one, 10, null, one, null))
+    refused("hnr_conf0_grad", L.hnr_conf0_grad(one, one, -1, one, one, null))
+    assert L.hnr_conf0_grad(one, one, 0, one, one, null) == 0
+    refused("hnr_w0fd_grad", L.hnr_w0fd_grad(one, null, null))
+    refused("hnr_ray_drop_flags", L.hnr_ray_drop_flags(null, 10, one, null, one, null))
+    refused("hnr_ray_drop_flags", L.hnr_ray_drop_flags(one, -1, one, null, one, null))
+    assert L.hnr_ray_drop_flags(one, 0, one, null, one, null) == 0
     assert L.hnr_query_work_elems(285200, 24) > 285200 * 24
     assert L.hnr_image_features_scratch_elems(4, 480, 640) == 2 * 4 * (6 * 240 * 320 + 12 * 120 * 160 + 24 * 60 * 80)
 
