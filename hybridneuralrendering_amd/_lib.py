@@ -50,7 +50,8 @@ class RenderParams(ctypes.Structure):
 
 
 class RenderCloud(ctypes.Structure):
-    _fields_ = [("d_xyz", _P), ("d_conf", _P), ("d_dir", _P), ("d_color", _P), ("d_point_table", _P), ("ldt", _I), ("d_rec", _P)]
+    _fields_ = [("d_xyz", _P), ("d_conf", _P), ("d_dir", _P), ("d_color", _P), ("d_point_table", _P), ("ldt", _I), ("d_rec", _P),
+                ("d_part", _P), ("d_part_rot", _P), ("n_parts", _I), ("rec_parts", _I)]        # per-point rotations (an edited scene); zero: none
 
 
 class RenderWeights(ctypes.Structure):
@@ -181,6 +182,9 @@ SIGNATURES = {
     "hnr_chain_plan": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _P, _P]),
     "hnr_point_records": (_I, [_P, _P, _P, _P, _I, _P, _P]),
     "hnr_chain_gather_rec": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
+    "hnr_point_records_parts": (_I, [_P, _P, _P, _P, _P, _I, _P, _P]),
+    "hnr_chain_gather_rec_parts": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
+    "hnr_chain_gather_parts": (_I, [_P] * 6 + [_I] + [_P] * 7 + [_I, _I, _I, _P, _P, _I, _P, _P, _P]),
     "hnr_chain_forward": (_I, [_P, _P, _I, _P, _P, _I, _F, _P, _I, _P, _P, _I, _P]),
     "hnr_mlp3_packed_bytes": (ctypes.c_int64, [_I, ctypes.POINTER(_I)]),
     "hnr_mlp3_pack": (_I, [_I, ctypes.POINTER(_P), ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_P), _P, _P]),

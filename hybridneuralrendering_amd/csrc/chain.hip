@@ -401,7 +401,19 @@ struct ChainGatherArgs {
     float *weight_out, *conf_out;
     float *Xd;                                           // training: [rows, 64] fp32 PE5(dists6) (60 columns + 4 zeros): block1.0's distance inputs, for its weight gradient
     int32_t *row_pid;                                    // training: [rows] point id of every row (-1: empty slot)
+    // ROT kernels: per-point rotations Rw2c as a part table (neural_points.py:720, point_aggregators.py:894-898): Rw2c of point p = part_rot[part of p],
+    // the part index from the record's first spare float (hnr_point_records_parts) or from `part`
+    const int32_t *part;                                 // [N] (ROT, not REC)
+    const float *part_rot;                               // [P][9] row-major
 };
+
+// y = R x with every product and sum rounded on its own, left to right: R = identity returns x bit for bit
+__device__ __forceinline__ void chain_rot3(const float *__restrict__ R, float x0, float x1, float x2, float y[3])
+{
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+        y[i] = __fadd_rn(__fadd_rn(__fmul_rn(R[3 * i], x0), __fmul_rn(R[3 * i + 1], x1)), __fmul_rn(R[3 * i + 2], x2));
+}
 
 __device__ __forceinline__ void chain_w2pers(const float *p, const float *campos, const float *camrot, float out[3])
 {
@@ -415,7 +427,10 @@ __device__ __forceinline__ void chain_w2pers(const float *p, const float *campos
 
 typedef float f32x4g __attribute__((ext_vector_type(4)));
 
-template <bool REC>
+// ROT (an edited scene, point_aggregators.py:894-971): dists[0:3] and the stored direction of a neighbour are turned by ITS point's rotation, the
+// sample's view direction -- the 24 encoding columns and the `ori_viewdirs` of every neighbour row -- by the rotation of the point in slot 0
+// (sampled_Rw2c[:,:,:,0], :897); weight and conf_coefficient come from the un-rotated offset.  ROT = false is the kernel without any of it.
+template <bool REC, bool ROT>
 __global__ __launch_bounds__(256) void chain_gather_kernel(ChainGatherArgs a)
 {
     __shared__ float s_d[128][7];                        // dists6 per row (odd stride: rows of consecutive lanes on distinct banks)
@@ -437,6 +452,8 @@ __global__ __launch_bounds__(256) void chain_gather_kernel(ChainGatherArgs a)
         int pid = -1, item = 0;
         if (s < s_end) { item = a.vs_item[s]; pid = a.pidx[(size_t)item * 8 + kk]; }
         float wraw = 0.f, confc = 0.f, ext[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, d6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        int part = 0;                                    // ROT: this neighbour's part
+        float rdir[3] = {0.f, 0.f, 0.f}, rv[3] = {0.f, 0.f, 0.f};      // ROT: the stored direction turned by its own point, the ray direction
         if (pid >= 0) {
             const float *lw = a.loc_w + (size_t)item * 3;
             float sp[3], pp[3];
@@ -465,8 +482,31 @@ __global__ __launch_bounds__(256) void chain_gather_kernel(ChainGatherArgs a)
             const float vx = a.raydir[3 * (size_t)ray], vy = a.raydir[3 * (size_t)ray + 1], vz = a.raydir[3 * (size_t)ray + 2];
             const float ddx = r1.x, ddy = r1.y, ddz = r1.z;
             ext[0] = r1.w; ext[1] = r2.x; ext[2] = r2.y;
-            ext[3] = __fsub_rn(ddx, vx); ext[4] = __fsub_rn(ddy, vy); ext[5] = __fsub_rn(ddz, vz);
-            ext[6] = __fadd_rn(__fadd_rn(__fmul_rn(ddx, vx), __fmul_rn(ddy, vy)), __fmul_rn(ddz, vz));
+            if constexpr (ROT) {
+                if constexpr (REC) part = (int)r2.z; else part = a.part[pid];
+                float Rm[9];
+#pragma unroll
+                for (int i = 0; i < 9; ++i) Rm[i] = a.part_rot[9 * (size_t)part + i];
+                chain_rot3(Rm, dx, dy, dz, d6);                       // (after the norm: the weight is the un-rotated offset's)
+                chain_rot3(Rm, ddx, ddy, ddz, rdir);
+                rv[0] = vx; rv[1] = vy; rv[2] = vz;
+            } else {
+                ext[3] = __fsub_rn(ddx, vx); ext[4] = __fsub_rn(ddy, vy); ext[5] = __fsub_rn(ddz, vz);
+                ext[6] = __fadd_rn(__fadd_rn(__fmul_rn(ddx, vx), __fmul_rn(ddy, vy)), __fmul_rn(ddz, vz));
+            }
+        }
+        if constexpr (ROT) {
+            // the sample's view direction is turned by the point in slot 0: that lane's part, from the first lane of the sample (a valid sample's
+            // slot 0 is never empty, hnr_chain_plan)
+            const int part0 = __shfl(part, (tid & 63) & ~((8 >> kc) - 1));
+            if (pid >= 0) {
+                float R0[9], v[3];
+#pragma unroll
+                for (int i = 0; i < 9; ++i) R0[i] = a.part_rot[9 * (size_t)part0 + i];
+                chain_rot3(R0, rv[0], rv[1], rv[2], v);
+                ext[3] = __fsub_rn(rdir[0], v[0]); ext[4] = __fsub_rn(rdir[1], v[1]); ext[5] = __fsub_rn(rdir[2], v[2]);
+                ext[6] = __fadd_rn(__fadd_rn(__fmul_rn(rdir[0], v[0]), __fmul_rn(rdir[1], v[1])), __fmul_rn(rdir[2], v[2]));
+            }
         }
         float sum = wraw;
         sum += __shfl_xor(sum, 1);
@@ -487,12 +527,24 @@ __global__ __launch_bounds__(256) void chain_gather_kernel(ChainGatherArgs a)
         const int ls = t >> 2, part = t & 3;
         const int s = s_base + ls;
         if (s < s_end) {
-            const int ray = a.vs_item[s] / a.SR;
+            const int item = a.vs_item[s], ray = item / a.SR;
             float *o = a.X5 + (size_t)s * a.ld5 + 256;
+            [[maybe_unused]] float v[3];
+            if constexpr (ROT) {
+                const int p0 = a.pidx[(size_t)item * 8];                 // slot 0's point (never empty for a valid sample)
+                int pt = 0;
+                if (p0 >= 0) { if constexpr (REC) pt = (int)a.rec[3 * (size_t)p0 + 2].z; else pt = a.part[p0]; }
+                float R0[9];
+#pragma unroll
+                for (int i = 0; i < 9; ++i) R0[i] = a.part_rot[9 * (size_t)pt + i];
+                chain_rot3(R0, a.raydir[3 * (size_t)ray], a.raydir[3 * (size_t)ray + 1], a.raydir[3 * (size_t)ray + 2], v);
+            }
 #pragma unroll
             for (int i = 0; i < 6; ++i) {
                 const int l = part * 6 + i, jj = l % 12, d = jj >> 2, f = jj & 3;
-                const float x = __fmul_rn(a.raydir[3 * (size_t)ray + d], (float)(1 << f));
+                float vd;
+                if constexpr (ROT) vd = d == 0 ? v[0] : (d == 1 ? v[1] : v[2]); else vd = a.raydir[3 * (size_t)ray + d];
+                const float x = __fmul_rn(vd, (float)(1 << f));
                 o[l] = l < 12 ? sinf(x) : cosf(x);
             }
         }
@@ -773,6 +825,12 @@ __global__ void point_records_kernel(const float *__restrict__ xyz, const float 
         rec[3 * (size_t)i + 2] = make_float4(color[3 * (size_t)i + 1], color[3 * (size_t)i + 2], 0.f, 0.f);
     }
 }
+
+__global__ void point_records_parts_kernel(const int32_t *__restrict__ part, int N, float4 *__restrict__ rec)
+{
+    // the part index in the record's first spare float (exact: at most 65536 parts)
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N; i += gridDim.x * blockDim.x) rec[3 * (size_t)i + 2].z = (float)part[i];
+}
 }  // namespace hnr
 
 extern "C" int hnr_point_records(const float *d_xyz, const float *d_conf, const float *d_dir, const float *d_color, int N, float *d_rec,
@@ -791,7 +849,54 @@ extern "C" int hnr_point_records(const float *d_xyz, const float *d_conf, const 
 static int chain_gather_impl(const float *d_rec, const float *d_xyz, const float *d_conf, const float *d_dir, const float *d_color,
                              const int32_t *d_sample_pidx, const float *d_sample_loc_w, const float *d_raydir, const float *d_campos,
                              const float *d_camrot, const int32_t *d_vs_item, const int64_t *d_counts, int SR, int K, int cap_samples,
-                             void *d_workspace, float *d_X5, int ld5, float *d_weight_out, float *d_conf_out, float *d_Xd, int32_t *d_row_pid, void *stream);
+                             void *d_workspace, float *d_X5, int ld5, float *d_weight_out, float *d_conf_out, float *d_Xd, int32_t *d_row_pid, void *stream,
+                             const int32_t *d_part, const float *d_part_rot);
+
+// The part-table forms (an edited scene).  n_parts = 0: no rotations, the call is the plain one.
+static bool chain_parts_ok(const char *who, const float *d_part_rot, int n_parts)
+{
+    if (n_parts < 0 || n_parts > HNR_MAX_PARTS) { set_error("%s: n_parts = %d is outside 0 .. %d", who, n_parts, HNR_MAX_PARTS); return false; }
+    if (n_parts > 0 && !d_part_rot) { set_error("%s: n_parts = %d but d_part_rot is NULL", who, n_parts); return false; }
+    return true;
+}
+
+extern "C" int hnr_point_records_parts(const float *d_xyz, const float *d_conf, const float *d_dir, const float *d_color, const int32_t *d_part, int N,
+                                       float *d_rec, void *stream)
+{
+    if (N > 0 && !d_part) { set_error("hnr_point_records_parts: the part index array is NULL"); return HNR_ERR_BADARG; }
+    const int rc = hnr_point_records(d_xyz, d_conf, d_dir, d_color, N, d_rec, stream);
+    if (rc != HNR_OK || N == 0) return rc;
+    const int blocks = cdiv(N, 256);
+    point_records_parts_kernel<<<blocks < 8192 ? blocks : 8192, 256, 0, (hipStream_t)stream>>>(d_part, N, reinterpret_cast<float4 *>(d_rec));
+    HNR_LAUNCH_CHECK();
+    return HNR_OK;
+}
+
+extern "C" int hnr_chain_gather_rec_parts(const float *d_rec, const float *d_part_rot, int n_parts, const int32_t *d_sample_pidx,
+                                          const float *d_sample_loc_w, const float *d_raydir, const float *d_campos, const float *d_camrot,
+                                          const int32_t *d_vs_item, const int64_t *d_counts, int SR, int K, int cap_samples, void *d_workspace,
+                                          float *d_X5, int ld5, float *d_weight_out, float *d_conf_out, void *stream)
+{
+    if (!chain_parts_ok("hnr_chain_gather_rec_parts", d_part_rot, n_parts)) return HNR_ERR_BADARG;
+    if (cap_samples > 0 && (!d_rec || ((uintptr_t)d_rec & 15))) { set_error("hnr_chain_gather_rec_parts: NULL / unaligned point records"); return HNR_ERR_BADARG; }
+    return chain_gather_impl(d_rec, nullptr, nullptr, nullptr, nullptr, d_sample_pidx, d_sample_loc_w, d_raydir, d_campos, d_camrot, d_vs_item, d_counts,
+                             SR, K, cap_samples, d_workspace, d_X5, ld5, d_weight_out, d_conf_out, nullptr, nullptr, stream, nullptr,
+                             n_parts > 0 ? d_part_rot : nullptr);
+}
+
+extern "C" int hnr_chain_gather_parts(const float *d_xyz, const float *d_conf, const float *d_dir, const float *d_color, const int32_t *d_part,
+                                      const float *d_part_rot, int n_parts, const int32_t *d_sample_pidx, const float *d_sample_loc_w,
+                                      const float *d_raydir, const float *d_campos, const float *d_camrot, const int32_t *d_vs_item,
+                                      const int64_t *d_counts, int SR, int K, int cap_samples, void *d_workspace, float *d_X5, int ld5,
+                                      float *d_weight_out, float *d_conf_out, void *stream)
+{
+    if (!chain_parts_ok("hnr_chain_gather_parts", d_part_rot, n_parts)) return HNR_ERR_BADARG;
+    if (n_parts > 0 && !d_part) { set_error("hnr_chain_gather_parts: n_parts = %d but the part index array is NULL", n_parts); return HNR_ERR_BADARG; }
+    if (cap_samples > 0 && (!d_xyz || !d_conf || !d_dir || !d_color)) { set_error("hnr_chain_gather_parts: NULL / unaligned pointer"); return HNR_ERR_BADARG; }
+    return chain_gather_impl(nullptr, d_xyz, d_conf, d_dir, d_color, d_sample_pidx, d_sample_loc_w, d_raydir, d_campos, d_camrot, d_vs_item, d_counts,
+                             SR, K, cap_samples, d_workspace, d_X5, ld5, d_weight_out, d_conf_out, nullptr, nullptr, stream,
+                             n_parts > 0 ? d_part : nullptr, n_parts > 0 ? d_part_rot : nullptr);
+}
 
 extern "C" int hnr_chain_gather_rec(const float *d_rec, const int32_t *d_sample_pidx, const float *d_sample_loc_w, const float *d_raydir,
                                     const float *d_campos, const float *d_camrot, const int32_t *d_vs_item, const int64_t *d_counts, int SR,
@@ -800,7 +905,7 @@ extern "C" int hnr_chain_gather_rec(const float *d_rec, const int32_t *d_sample_
 {
     if (cap_samples > 0 && (!d_rec || ((uintptr_t)d_rec & 15))) { set_error("hnr_chain_gather_rec: NULL / unaligned point records"); return HNR_ERR_BADARG; }
     return chain_gather_impl(d_rec, nullptr, nullptr, nullptr, nullptr, d_sample_pidx, d_sample_loc_w, d_raydir, d_campos, d_camrot, d_vs_item, d_counts,
-                             SR, K, cap_samples, d_workspace, d_X5, ld5, d_weight_out, d_conf_out, nullptr, nullptr, stream);
+                             SR, K, cap_samples, d_workspace, d_X5, ld5, d_weight_out, d_conf_out, nullptr, nullptr, stream, nullptr, nullptr);
 }
 
 extern "C" int hnr_chain_gather(const float *d_xyz, const float *d_conf, const float *d_dir, const float *d_color,
@@ -810,13 +915,14 @@ extern "C" int hnr_chain_gather(const float *d_xyz, const float *d_conf, const f
 {
     if (cap_samples > 0 && (!d_xyz || !d_conf || !d_dir || !d_color)) { set_error("hnr_chain_gather: NULL / unaligned pointer"); return HNR_ERR_BADARG; }
     return chain_gather_impl(nullptr, d_xyz, d_conf, d_dir, d_color, d_sample_pidx, d_sample_loc_w, d_raydir, d_campos, d_camrot, d_vs_item, d_counts,
-                             SR, K, cap_samples, d_workspace, d_X5, ld5, d_weight_out, d_conf_out, nullptr, nullptr, stream);
+                             SR, K, cap_samples, d_workspace, d_X5, ld5, d_weight_out, d_conf_out, nullptr, nullptr, stream, nullptr, nullptr);
 }
 
 static int chain_gather_impl(const float *d_rec, const float *d_xyz, const float *d_conf, const float *d_dir, const float *d_color,
                              const int32_t *d_sample_pidx, const float *d_sample_loc_w, const float *d_raydir, const float *d_campos,
                              const float *d_camrot, const int32_t *d_vs_item, const int64_t *d_counts, int SR, int K, int cap_samples,
-                             void *d_workspace, float *d_X5, int ld5, float *d_weight_out, float *d_conf_out, float *d_Xd, int32_t *d_row_pid, void *stream)
+                             void *d_workspace, float *d_X5, int ld5, float *d_weight_out, float *d_conf_out, float *d_Xd, int32_t *d_row_pid, void *stream,
+                             const int32_t *d_part, const float *d_part_rot)
 {
     if (K != 8) { set_error("hnr_chain_gather: the fused chain is built for K = 8 (got %d); use the per-layer path", K); return HNR_ERR_BADARG; }
     if (cap_samples < 0 || SR <= 0 || ld5 < 280 || (ld5 & 3)) { set_error("hnr_chain_gather: bad sizes (cap_samples=%d SR=%d ld5=%d)", cap_samples, SR, ld5); return HNR_ERR_BADARG; }
@@ -833,8 +939,14 @@ static int chain_gather_impl(const float *d_rec, const float *d_xyz, const float
     a.counts = reinterpret_cast<const unsigned long long *>(d_counts); a.SR = SR; a.cap_samples = cap_samples;
     a.xp = (char *)d_workspace; a.aux = (char *)d_workspace + (size_t)blocks * 4 * CH_XP_GROUP;
     a.X5 = d_X5; a.ld5 = ld5; a.weight_out = d_weight_out; a.conf_out = d_conf_out; a.Xd = d_Xd; a.row_pid = d_row_pid;
-    if (d_rec) chain_gather_kernel<true><<<blocks < 16384 ? blocks : 16384, 256, 0, (hipStream_t)stream>>>(a);
-    else chain_gather_kernel<false><<<blocks < 16384 ? blocks : 16384, 256, 0, (hipStream_t)stream>>>(a);
+    a.part = d_part; a.part_rot = d_part_rot;
+    const int grid = blocks < 16384 ? blocks : 16384;
+    hipStream_t st = (hipStream_t)stream;
+    if (d_part_rot) {                                    // an edited scene: per-point rotations from the part table
+        if (d_rec) chain_gather_kernel<true, true><<<grid, 256, 0, st>>>(a);
+        else chain_gather_kernel<false, true><<<grid, 256, 0, st>>>(a);
+    } else if (d_rec) chain_gather_kernel<true, false><<<grid, 256, 0, st>>>(a);
+    else chain_gather_kernel<false, false><<<grid, 256, 0, st>>>(a);
     HNR_LAUNCH_CHECK();
     return HNR_OK;
 }
@@ -882,7 +994,7 @@ int chain_gather_train(const float *d_xyz, const float *d_conf, const float *d_d
                        float *d_conf_out, float *d_Xd, int32_t *d_row_pid, void *stream)
 {
     return chain_gather_impl(nullptr, d_xyz, d_conf, d_dir, d_color, d_sample_pidx, d_sample_loc_w, d_raydir, d_campos, d_camrot, d_vs_item, d_counts,
-                             SR, K, cap_samples, d_workspace, d_X5, ld5, d_weight_out, d_conf_out, d_Xd, d_row_pid, stream);
+                             SR, K, cap_samples, d_workspace, d_X5, ld5, d_weight_out, d_conf_out, d_Xd, d_row_pid, stream, nullptr, nullptr);
 }
 
 int chain_forward_train(const void *d_workspace, const float *d_point_table, int ldt, const int32_t *d_uidx, const void *d_packed, const int64_t *d_counts,

@@ -92,6 +92,17 @@ extern "C" int hnr_render_forward(const hnr_grid *grid, const hnr_render_params 
     HNR_HIP_CHECK(hipMemsetAsync(o->d_decoded, 0, (size_t)R * SR * 4 * sizeof(float), st));
     HNR_MARK();
     // ---- per-neighbour chain
+    if (cl->n_parts != 0) {
+        // an edited scene: per-point rotations from the part table (n_parts out of range and a missing table are refused by the stage calls)
+        if (cl->d_rec && cl->rec_parts)
+            rc = hnr_chain_gather_rec_parts(cl->d_rec, cl->d_part_rot, cl->n_parts, o->d_sample_pidx, o->d_sample_loc_w, cam->d_raydir, cam->d_campos, cam->d_camrot,
+                                            L.vs_item, o->d_counts, SR, K, cap, L.chain_ws, L.X5, 280, o->d_weight, o->d_conf_coefficient, stream);
+        else if (cl->n_parts > 0 && !cl->d_part) { set_error("hnr_render_forward: n_parts = %d but neither d_part nor records with part indices (rec_parts) are given", cl->n_parts); return HNR_ERR_BADARG; }
+        else
+            rc = hnr_chain_gather_parts(cl->d_xyz, cl->d_conf, cl->d_dir, cl->d_color, cl->d_part, cl->d_part_rot, cl->n_parts, o->d_sample_pidx, o->d_sample_loc_w,
+                                        cam->d_raydir, cam->d_campos, cam->d_camrot, L.vs_item, o->d_counts, SR, K, cap, L.chain_ws, L.X5, 280, o->d_weight,
+                                        o->d_conf_coefficient, stream);
+    } else
     rc = cl->d_rec ? hnr_chain_gather_rec(cl->d_rec, o->d_sample_pidx, o->d_sample_loc_w, cam->d_raydir, cam->d_campos, cam->d_camrot, L.vs_item, o->d_counts,
                                           SR, K, cap, L.chain_ws, L.X5, 280, o->d_weight, o->d_conf_coefficient, stream)
                    : hnr_chain_gather(cl->d_xyz, cl->d_conf, cl->d_dir, cl->d_color, o->d_sample_pidx, o->d_sample_loc_w, cam->d_raydir, cam->d_campos, cam->d_camrot,

@@ -18,7 +18,7 @@ from . import _lib
 from ._lib import HnrError
 from . import querier as Q
 from .aggregator import PointAggregator
-from .render import HybridRenderer, PointCloud
+from .render import HybridRenderer, PartTable, PointCloud
 
 
 # ------------------------------------------------------------------------------------------------ rendering
@@ -90,6 +90,7 @@ class NeuralPoints(nn.Module):
         assert isinstance(size, int), "size must be int"
         self.opt = opt
         self.grid_vox_sz = 0
+        self._parts = None                                                 # per-point rotations as a part table (render.PartTable); None: identity
         self.points_conf, self.points_dir, self.points_color, self.eulers, self.Rw2c = None, None, None, None, None
         self.device = device
         if getattr(opt, "wcoord_query", 1) <= 0:
@@ -127,13 +128,34 @@ class NeuralPoints(nn.Module):
                 self.points_conf = par("neural_points.points_conf", opt.conf_grad > 0)
             self.points_dir = par("neural_points.points_dir", opt.dir_grad > 0)
             self.points_color = par("neural_points.points_color", opt.color_grad > 0)
-            self.Rw2c = torch.eye(3, device=self.xyz.device, dtype=self.xyz.dtype)
-            if "neural_points.Rw2c" in saved or "neural_points.eulers" in saved:
-                raise HnrError("per-point rotations (Rw2c / eulers) are never produced by a shipped config and are unsupported")
+            if "neural_points.eulers" in saved:
+                raise HnrError("per-point `eulers` are never produced by a shipped config and are unsupported (Rw2c is supported)")
+            self.Rw2c = saved.get("neural_points.Rw2c")                    # (:289) [3,3] or [N,3,3]: an edited scene
         self.reg_weight = reg_weight
         self.opt.query_size = self.opt.kernel_size if self.opt.query_size[0] == 0 else self.opt.query_size   # :329
         self.lighting_fast_querier = Q.lighting_fast_querier
         self.querier = self.lighting_fast_querier(device, self.opt)
+
+    # Rw2c reads as the reference's tensor -- eye(3), a [3,3] matrix or [N,3,3] -- and is KEPT as a part table (render.PartTable: a handful of
+    # 3x3 matrices + one index per point, what the gather kernel reads; converted and validated once, when it is set).  Assign None, [3,3],
+    # [N,3,3], (part [N], part_rot [P,3,3]) or a PartTable.
+    @property
+    def Rw2c(self):
+        if self._parts is None:
+            ref = getattr(self, "xyz", None)
+            return torch.eye(3) if ref is None else torch.eye(3, device=ref.device, dtype=ref.dtype)
+        return self._parts.expand()
+
+    @Rw2c.setter
+    def Rw2c(self, value):
+        self._parts = None if value is None else PartTable.make(value, int(self.xyz.shape[0]), self.xyz.device)
+
+    def _apply(self, fn, *args, **kwargs):
+        # .to(device) / .cuda(): the table follows the parameters (the index stays int32: Module.to casts floating tensors only)
+        super()._apply(fn, *args, **kwargs)
+        if self._parts is not None:
+            self._parts = PartTable(fn(self._parts.part), fn(self._parts.part_rot), self._parts.uniform)
+        return self
 
     def reset_querier(self):
         self.querier.clean_up()
@@ -160,10 +182,21 @@ class NeuralPoints(nn.Module):
             t = getattr(self, name)
             if t is not None:
                 self._set(name, t[:, mask, :], flag)
+        if self._parts is not None:                                    # (:370-372)
+            self._parts = self._parts.select(mask)
         print("@@@@@@@@@  pruned {}/{}".format(torch.sum(mask == 0), mask.shape[0]))
 
     def grow_points(self, add_xyz, add_embedding, add_color, add_dir, add_conf, add_eulers=None, add_Rw2c=None):   # :376-402
         n_old = int(self.xyz.shape[0])
+        if add_eulers is not None:
+            raise HnrError("grow_points: per-point `eulers` are unsupported (Rw2c is supported)")
+        # (:400-402) the new points' rotations join the table; a cloud without rotations that grows by rotated points gets one
+        n_add, parts = int(add_xyz.shape[0]), self._parts
+        if parts is None and add_Rw2c is not None and PartTable.make(add_Rw2c, n_add, self.xyz.device) is not None:
+            parts = PartTable(torch.zeros(n_old, dtype=torch.int32, device=self.xyz.device), torch.eye(3, dtype=torch.float32, device=self.xyz.device)[None])
+        if parts is not None:
+            parts = parts.grown(add_Rw2c, n_add)
+        self._parts = parts
         self.xyz = nn.Parameter(torch.cat([self.xyz, add_xyz], dim=0), requires_grad=self.opt.xyz_grad > 0)
         # points were APPENDED: the cached voxel grid is extended in place when the grown cloud keeps the grid geometry (SURVEY 8f-3;
         # querier.grow -> hnr_grid_grow), dropped and rebuilt by the next query otherwise
@@ -177,8 +210,8 @@ class NeuralPoints(nn.Module):
 
     def set_points(self, points_xyz, points_embeding, points_color=None, points_dir=None, points_conf=None, parameter=False,
                    Rw2c=None, eulers=None):                            # :404-470, modes "1" only
-        if Rw2c is not None:
-            raise HnrError("per-point Rw2c is unsupported")
+        if eulers is not None:
+            raise HnrError("set_points: per-point `eulers` are unsupported (Rw2c is supported)")
         if points_embeding.shape[-1] > self.opt.point_features_dim:
             points_embeding = points_embeding[..., :self.opt.point_features_dim]
         if self.opt.default_conf > 0.0 and self.opt.default_conf <= 1.0 and points_conf is not None:
@@ -189,16 +222,22 @@ class NeuralPoints(nn.Module):
         self.points_dir = None if points_dir is None else wrap(points_dir, self.opt.dir_grad)
         self.points_color = None if points_color is None else wrap(points_color, self.opt.color_grad)
         self.points_embeding = wrap(points_embeding, self.opt.feat_grad)
-        self.Rw2c = torch.eye(3, device=points_xyz.device, dtype=points_xyz.dtype)
+        self.Rw2c = Rw2c                                                   # (:466-470)
         self._points_changed()
 
     def editing_set_points(self, points_xyz, points_embeding, points_color=None, points_dir=None, points_conf=None,
                            parameter=False, Rw2c=None, eulers=None):   # :473-487
+        if eulers is not None:
+            raise HnrError("editing_set_points: per-point `eulers` are unsupported (Rw2c is supported)")
         if self.opt.default_conf > 0.0 and self.opt.default_conf <= 1.0 and points_conf is not None:
             points_conf = torch.ones_like(points_conf) * self.opt.default_conf
+        # plain tensors, as in the reference; a cloud loaded from a checkpoint holds nn.Parameters under these names, which nn.Module would not
+        # let a tensor replace: drop the registrations first
+        for name in ("xyz", "points_embeding", "points_dir", "points_conf", "points_color"):
+            self._parameters.pop(name, None)
         self.xyz, self.points_embeding, self.points_dir = points_xyz, points_embeding, points_dir
         self.points_conf, self.points_color = points_conf, points_color
-        self.Rw2c = torch.eye(3, device=points_xyz.device, dtype=points_xyz.dtype)
+        self.Rw2c = Rw2c                                                   # (:484-487) also (part, part_rot): edit.compose's table as it is
         self._points_changed()
 
     def null_grad(self):
@@ -209,7 +248,7 @@ class NeuralPoints(nn.Module):
         return self.reg_weight * torch.mean(torch.pow(self.points_embeding, 2))
 
     def cloud(self):
-        return PointCloud(self.xyz, self.points_embeding, self.points_conf, self.points_dir, self.points_color)
+        return PointCloud(self.xyz, self.points_embeding, self.points_conf, self.points_dir, self.points_color, Rw2c=self._parts)
 
     def w2pers(self, point_xyz, camrotc2w, campos):                    # :607-613 (kept; the kernels fuse it)
         shift = point_xyz[None, ...] - campos[:, None, :]
@@ -238,7 +277,10 @@ class NeuralPoints(nn.Module):
                                            p(campos.reshape(3).contiguous()), p(camrot.reshape(3, 3).contiguous()), p(o_color),
                                            p(o_dir), p(o_conf), p(o_emb), p(o_pers), p(o_xyz), p(o_mask), _lib.stream()),
                        "hnr_gather_points")
-        return (o_color, self.Rw2c, o_dir, o_conf, o_emb, o_pers, o_xyz, o_mask.bool(), loc, loc_w, dirs, ray_mask, vsize,
+        sampled_Rw2c = self.Rw2c                                           # (:720) 2-D as it is, 3-D gathered per neighbour (empty slots read point 0)
+        if self._parts is not None and not self._parts.uniform:
+            sampled_Rw2c = self._parts.part_rot[self._parts.part[pidx.reshape(-1).clamp(min=0).long()].long()].view(B, R, SR, K, 3, 3)
+        return (o_color, sampled_Rw2c, o_dir, o_conf, o_emb, o_pers, o_xyz, o_mask.bool(), loc, loc_w, dirs, ray_mask, vsize,
                 self.grid_vox_sz)
 
 
@@ -285,6 +327,8 @@ class NeuralPointsRayMarching(nn.Module):
             # training: same HIP forward with the activations kept + the hand-written backward (train.py); coarse_raycolor and
             # conf_coefficient stay attached to the autograd graph of the point buffers and the aggregator parameters
             from .train import TrainPath, render_train
+            if self.neural_points._parts is not None:
+                raise HnrError("neural_points.Rw2c (per-point rotations of an edited scene) is not supported by the training path (is_train=1)")
             if self._train_path is None:
                 self._train_path = TrainPath(rnd)
             npnt = self.neural_points
@@ -315,6 +359,8 @@ class NeuralPointsRayMarching(nn.Module):
         out["conf_coefficient"] = sel(full["conf_coefficient"])
         if self.return_depth:
             out["coarse_depth"] = sel(full["coarse_depth"])               # [1,R'] (:385; not among fill_invalid's keys)
+        if getattr(self.opt, "prob", 0) == 1 and self.neural_points._parts is not None:
+            raise HnrError("prob=1 (hole probing) is not implemented for a cloud with Rw2c (per-point rotations of an edited scene)")
         if getattr(self.opt, "prob", 0) == 1 and rows.numel() > 0:
             out.update(self._probe_outputs(full, rows))
         return out

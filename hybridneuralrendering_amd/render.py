@@ -58,10 +58,91 @@ class _Stage:
         return False
 
 
-class PointCloud:
-    """The neural point buffers in the kernels' layouts (views of the NeuralPoints parameters)."""
+MAX_PARTS = 65536                     # HNR_MAX_PARTS (include/hnr.h)
 
-    def __init__(self, xyz, emb, conf, pdir, color):
+
+class PartTable:
+    """Per-point rotations `Rw2c` (neural_points.py:720) as the gather kernel reads them: part_rot [P,3,3] float32 and one int32 part index per
+    point, Rw2c of point i = part_rot[part[i]].  An edit has a handful of parts; 36 bytes per neighbour would nearly double the gather's random
+    traffic.  Built and validated ONCE (PartTable.make, one host read); a PointCloud takes it as it is.
+    uniform: made from a 2-D [3,3] Rw2c -- one matrix for every point, also for points that are added later (the reference keeps a 2-D Rw2c
+    2-D in grow_points, :400)."""
+
+    def __init__(self, part, part_rot, uniform=False):
+        self.part, self.part_rot, self.uniform = part, part_rot, uniform
+
+    @property
+    def n_parts(self):
+        return int(self.part_rot.shape[0])
+
+    @staticmethod
+    def make(Rw2c, n, device):
+        """Rw2c: None, a PartTable, [3,3], [N,3,3] or (part [N] integer, part_rot [P,3,3]).  Returns a PartTable, or None when every point's
+        rotation is the identity (the renderer then runs the kernels without rotations)."""
+        if Rw2c is None or isinstance(Rw2c, PartTable):
+            if Rw2c is not None and int(Rw2c.part.shape[0]) != n:
+                raise HnrError("Rw2c: the part table has %d entries, the cloud %d points" % (int(Rw2c.part.shape[0]), n))
+            return Rw2c
+        uniform = False
+        if isinstance(Rw2c, (tuple, list)):
+            part, rot = Rw2c
+            part = torch.as_tensor(part).detach().to(device).reshape(-1)
+            rot = torch.as_tensor(rot).detach().to(device=device, dtype=torch.float32)
+            if rot.dim() != 3 or tuple(rot.shape[1:]) != (3, 3) or part.shape[0] != n or part.dtype.is_floating_point or rot.shape[0] == 0:
+                raise HnrError("Rw2c=(part, part_rot): part must be an integer tensor [N = %d], part_rot [P,3,3] (got %s %s, %s)" % (
+                    n, tuple(part.shape), part.dtype, tuple(rot.shape)))
+            if rot.shape[0] > MAX_PARTS:
+                raise HnrError("Rw2c: %d parts, the part table holds at most %d" % (rot.shape[0], MAX_PARTS))
+            if n > 0:
+                lo, hi = int(part.min()), int(part.max())                      # (the one host read)
+                if lo < 0 or hi >= rot.shape[0]:
+                    raise HnrError("Rw2c=(part, part_rot): part indices span %d .. %d, the table has %d parts" % (lo, hi, rot.shape[0]))
+        else:
+            R = torch.as_tensor(Rw2c).detach().to(device=device, dtype=torch.float32)
+            if R.dim() == 2 and tuple(R.shape) == (3, 3):
+                rot, part, uniform = R[None], torch.zeros(n, dtype=torch.int32, device=device), True
+            elif R.dim() == 3 and tuple(R.shape) == (n, 3, 3):
+                rot, part = torch.unique(R.reshape(n, 9), dim=0, return_inverse=True)
+                if rot.shape[0] > MAX_PARTS:
+                    raise HnrError("Rw2c: %d distinct matrices; the part table holds at most %d (an edit has one rotation per part)" % (
+                        rot.shape[0], MAX_PARTS))
+                rot = rot.reshape(-1, 3, 3)
+            else:
+                raise HnrError("Rw2c must be [3,3] or [N = %d,3,3] (got %s)" % (n, tuple(R.shape)))
+        rot = rot.contiguous()
+        if bool(torch.equal(rot, torch.eye(3, dtype=torch.float32, device=device).expand_as(rot))):
+            return None
+        return PartTable(part.to(torch.int32).contiguous(), rot, uniform)
+
+    def expand(self):
+        """The reference's tensor: [3,3] (uniform) or [N,3,3]."""
+        return self.part_rot[0] if self.uniform else self.part_rot[self.part.long()]
+
+    def select(self, mask):
+        """The table of the points kept by a bool mask (prune, :370-372)."""
+        return PartTable(self.part[mask].contiguous(), self.part_rot, self.uniform)
+
+    def grown(self, add, n_add):
+        """The table after n_add points were appended (grow_points, :400-402); add: their Rw2c in any form of make (ignored for a uniform table)."""
+        dev = self.part.device
+        if self.uniform:
+            return PartTable(torch.zeros(self.part.shape[0] + n_add, dtype=torch.int32, device=dev), self.part_rot, True)
+        if add is None:
+            raise HnrError("grow_points: the cloud has per-point Rw2c; add_Rw2c is needed for the new points")
+        t = PartTable.make(add, n_add, dev)
+        if t is None:
+            t = PartTable(torch.zeros(n_add, dtype=torch.int32, device=dev), torch.eye(3, dtype=torch.float32, device=dev)[None])
+        if self.n_parts + t.n_parts > MAX_PARTS:
+            raise HnrError("Rw2c: more than %d parts" % MAX_PARTS)
+        return PartTable(torch.cat([self.part, t.part + self.n_parts]), torch.cat([self.part_rot, t.part_rot]).contiguous())
+
+
+class PointCloud:
+    """The neural point buffers in the kernels' layouts (views of the NeuralPoints parameters).
+    Rw2c: per-point rotations of an edited scene -- None, [3,3], [N,3,3], (part [N], part_rot [P,3,3]) or a PartTable (PartTable.make);
+    `parts` is the table, None when there is no rotation (or only identities)."""
+
+    def __init__(self, xyz, emb, conf, pdir, color, Rw2c=None):
         g = _lib.require_gpu
         self.xyz = g(xyz.detach(), "xyz", torch.float32).reshape(-1, 3)
         n = self.xyz.shape[0]
@@ -70,6 +151,7 @@ class PointCloud:
         self.dir = g(pdir.detach(), "points_dir", torch.float32).reshape(n, 3)
         self.color = g(color.detach(), "points_color", torch.float32).reshape(n, 3)
         self.F = self.emb.shape[1]
+        self.parts = PartTable.make(Rw2c, n, self.xyz.device)
 
 
 class HybridRenderer:
@@ -167,15 +249,21 @@ class HybridRenderer:
 
     def point_records(self, cloud):
         """hnr_point_records image of the cloud's xyz / conf / dir / colour buffers (48 B per point: what the fused gather reads per
-        neighbour), rebuilt when any of them changes."""
-        src = (cloud.xyz, cloud.conf, cloud.dir, cloud.color)
+        neighbour), rebuilt when any of them changes.  A cloud with per-point rotations: hnr_point_records_parts, the part index of every
+        point in the record's first spare float (the part data is part of the key)."""
+        parts = getattr(cloud, "parts", None)
+        src = (cloud.xyz, cloud.conf, cloud.dir, cloud.color) + (() if parts is None else (parts.part, parts.part_rot))
         key = tuple((t.data_ptr(), tuple(t.shape), t._version) for t in src)
         if key != getattr(self, "_rec_key", None):
             n = int(cloud.xyz.reshape(-1, 3).shape[0])
             rec = torch.empty((n, 12), dtype=torch.float32, device=cloud.xyz.device)
             with torch.cuda.device(cloud.xyz.device):
-                _lib.check(_lib.lib().hnr_point_records(_lib.ptr(cloud.xyz), _lib.ptr(cloud.conf), _lib.ptr(cloud.dir), _lib.ptr(cloud.color), n,
-                                                        _lib.ptr(rec), _lib.stream()), "hnr_point_records")
+                if parts is None:
+                    _lib.check(_lib.lib().hnr_point_records(_lib.ptr(cloud.xyz), _lib.ptr(cloud.conf), _lib.ptr(cloud.dir), _lib.ptr(cloud.color), n,
+                                                            _lib.ptr(rec), _lib.stream()), "hnr_point_records")
+                else:
+                    _lib.check(_lib.lib().hnr_point_records_parts(_lib.ptr(cloud.xyz), _lib.ptr(cloud.conf), _lib.ptr(cloud.dir), _lib.ptr(cloud.color),
+                                                                  _lib.ptr(parts.part), n, _lib.ptr(rec), _lib.stream()), "hnr_point_records_parts")
             self._rec, self._rec_key, self._rec_src = rec, key, src      # the sources stay referenced: a recycled address is not a stale hit
         return self._rec
 
@@ -206,6 +294,10 @@ class HybridRenderer:
         T = lambda name: _Stage(timers, name)
         with torch.cuda.device(dev):
           fused = self.dense == "f16x2" and K == 8
+          parts = getattr(cloud, "parts", None)
+          if parts is not None and not fused:
+              raise HnrError("Rw2c (per-point rotations of an edited scene) is implemented in the fused chain only: HNR_DENSE=f32 and K != 8 "
+                             "(got HNR_DENSE=%s, K=%d) cannot render this cloud" % (self.dense, K))
           with T("plan_gather"):
             if fused:
                 # valid samples with more than four neighbours first, then the small ones (4 row slots each in the chain's row tiles)
@@ -233,10 +325,16 @@ class HybridRenderer:
                 c_out = cloud.conf[0].clamp(0.0001, 1.0).expand(R, SR, K).contiguous()
             ptab = self.point_table(cloud)
             with T("chain_gather"):
+              if parts is None:
                 _lib.check(L.hnr_chain_gather_rec(p(self.point_records(cloud)), p(pidx), p(loc_w), p(raydir),
                                                   p(campos), p(camrot), p(vs_item), p(counts), SR, K, n_valid, p(ws), p(X5), 280,
                                                   p(w_out) if want_weights else None, p(c_out) if want_weights else None, st()),
                            "hnr_chain_gather_rec")
+              else:
+                _lib.check(L.hnr_chain_gather_rec_parts(p(self.point_records(cloud)), p(parts.part_rot), parts.n_parts, p(pidx), p(loc_w), p(raydir),
+                                                        p(campos), p(camrot), p(vs_item), p(counts), SR, K, n_valid, p(ws), p(X5), 280,
+                                                        p(w_out) if want_weights else None, p(c_out) if want_weights else None, st()),
+                           "hnr_chain_gather_rec_parts")
             with T("chain"):
                 _lib.check(L.hnr_chain_forward(p(ws), p(ptab), int(ptab.stride(0)), p(self.agg.packed_chain()), p(counts), n_valid,
                                                float(pk["slope"]), p(X5), 280, p(sigma), None, 0, st()), "hnr_chain_forward")
@@ -411,6 +509,9 @@ class HybridRenderer:
         m3 = agg.packed_mlp3()
         ptab = self.point_table(cloud)
         cl = _lib.RenderCloud(p(cloud.xyz), p(cloud.conf), p(cloud.dir), p(cloud.color), p(ptab), int(ptab.stride(0)), p(self.point_records(cloud)))
+        parts = getattr(cloud, "parts", None)
+        if parts is not None:                         # an edited scene: the records hold the part indices
+            cl.d_part, cl.d_part_rot, cl.n_parts, cl.rec_parts = p(parts.part), p(parts.part_rot), parts.n_parts, 1
         wt = _lib.RenderWeights(p(agg.packed_chain()), p(m3["cf"].packed), p(m3["mw"].packed), p(m3["mx"].packed),
                                 p(pk["mw_last_w"]), p(pk["mw_last_b"]), p(pk["fin_w"]), p(pk["fin_b"]), float(pk["slope"]))
         cam = _lib.RenderCamera(p(campos), p(camrot), p(raydir), p(tmid), p(bg_color))

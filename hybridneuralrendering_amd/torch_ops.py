@@ -188,6 +188,8 @@ def render_forward(renderer, cloud, raydir, campos, camrot, bg_color, near, far,
     renderer), one registered op instead of the ctypes call.  Returns the output dict of render_rays."""
     ops = load()
     opt, agg = renderer.opt, renderer.agg
+    if getattr(cloud, "parts", None) is not None:
+        raise _lib.HnrError("torch.ops.hnr.render_forward takes no Rw2c (per-point rotations of an edited scene); use HybridRenderer.render_rays")
     g = _lib.require_gpu
     raydir = g(raydir, "raydir", torch.float32).reshape(-1, 3)
     campos, camrot, bg_color = g(campos, "campos", torch.float32).reshape(3), g(camrot, "camrotc2w", torch.float32).reshape(3, 3), g(bg_color, "bg_color", torch.float32).reshape(3)

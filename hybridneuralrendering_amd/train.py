@@ -113,6 +113,15 @@ class _Saved:
     pass
 
 
+def _no_rotation(who, Rw2c, xyz):
+    """The training kernels (forward with kept activations, backward) carry no per-point rotations: an edited scene is rendered, not trained.
+    A non-identity Rw2c raises instead of training against an un-rotated picture."""
+    from .render import PartTable
+    if Rw2c is not None and PartTable.make(Rw2c, int(xyz.reshape(-1, 3).shape[0]), xyz.device) is not None:
+        raise HnrError("%s: Rw2c (per-point rotations of an edited scene) is not supported by the training path; render edited scenes with "
+                       "HybridRenderer.render_rays / driver.render_image" % who)
+
+
 class TrainPath:
     """Forward (activations kept in the library's workspace) and backward of one ray batch.  `renderer` is a HybridRenderer (grid cache)."""
 
@@ -148,6 +157,8 @@ class TrainPath:
         campos_nearest = g(campos_nearest, "campos_nearest", torch.float32).reshape(-1, 3)
         intrinsic_nearest = g(intrinsic_nearest, "intrinsic_nearest", torch.float32).reshape(3, 3)
         dev = raydir.device
+        if getattr(cloud, "parts", None) is not None:
+            raise HnrError("TrainPath: the cloud carries Rw2c (per-point rotations of an edited scene), which the training path does not support")
         if int(opt.K) != 8 or cloud.F != 32:
             raise HnrError("the training path is built for K = 8 neighbours and 32 point features (got K=%d, F=%d)" % (opt.K, cloud.F))
         R, SR, K = raydir.shape[0], int(opt.SR), 8
@@ -373,10 +384,11 @@ class _RenderFn(torch.autograd.Function):
 
 
 def render_train(path, aggregator, xyz, emb, conf, pdir, color, raydir, campos, camrot, bg_color, near, far, c2w_nearest,
-                 campos_nearest, intrinsic_nearest, images_nearest, frame_weight=None, tmid=None, ray_drop=None, want_depth=False):
+                 campos_nearest, intrinsic_nearest, images_nearest, frame_weight=None, tmid=None, ray_drop=None, want_depth=False, Rw2c=None):
     """Differentiable render of one ray batch.  emb/conf/pdir/color may be nn.Parameters (reference shapes [1,N,32], [1,N,1],
     [1,N,3], [1,N,3]); aggregator parameters receive gradients through the returned tensors.  Returns the output dict of
     TrainPath.forward with `coarse_raycolor` and `conf_coefficient` (and with want_depth `coarse_depth` [R]) attached to the autograd graph."""
+    _no_rotation("render_train", Rw2c, xyz)
     names = [n for n, _ in aggregator.named_parameters()]
     params = [q for _, q in aggregator.named_parameters()]
     static = dict(xyz=xyz, raydir=raydir, campos=campos, camrot=camrot, bg_color=bg_color, near=near, far=far,
@@ -474,7 +486,7 @@ def _assign_grads(aggregator, emb, conf, pdir, color, pg, ag, accumulate=True, c
 def train_step(path, aggregator, xyz, emb, conf, pdir, color, raydir, campos, camrot, bg_color, near, far, c2w_nearest, campos_nearest,
                intrinsic_nearest, images_nearest, gt_image, zero_epsilon=1e-3, w_color=1.0, w_zero_one=1e-4, frame_weight=None, tmid=None,
                ray_drop=None, assign_grads=True, frame_weight_nearest=None, blur_kernels=None, patch_num=None, patch_size=None, patch_layout="grid",
-               w2c_nearest=None, accumulate_grads=True, device_frame_weight=None, optimizer=None, learnable_blur=None):
+               w2c_nearest=None, accumulate_grads=True, device_frame_weight=None, optimizer=None, learnable_blur=None, Rw2c=None):
     """forward -> [blur module] -> shipped loss terms -> backward of one ray batch as groups of library launches queued back to back: no autograd
     graph, no masked copies, nothing read back to the host -- the body of the reference's optimize_parameters before its optimizer steps
     (models/neural_points_volumetric_model.py:202-214: self.forward(); loss_total.backward(), with compute_losses of
@@ -511,6 +523,7 @@ def train_step(path, aggregator, xyz, emb, conf, pdir, color, raydir, campos, ca
     The parameters' `_version` is bumped, so the renderer's caches follow the new weights.  With TrainPath.reuse_outputs the gradient buffers keep
     their addresses and the optimiser's descriptor table is uploaded once; without it, once per step.  Returns (outputs dict with `loss` = {total, colour MSE, zero-one mean, valid rays} on the device and `_saved` = the step's
     state for TrainPath.touched_points / the flat weight-gradient buffer, point grads dict, aggregator grads dict keyed by parameter name)."""
+    _no_rotation("train_step", Rw2c, xyz)           # (Rw2c: only so that a non-identity one raises; see _no_rotation)
     learnable_blur = _learnable_arg("train_step", blur_kernels, learnable_blur)
     cloud = PointCloud(xyz, emb.detach(), conf.detach(), pdir.detach(), color.detach())
     out, S, pg, ag = _queue_step(path, cloud, raydir, campos, camrot, bg_color, near, far, c2w_nearest, campos_nearest, intrinsic_nearest, images_nearest,
@@ -551,9 +564,10 @@ class CapturedTrainStep:
     addresses then: TrainPath.reuse_outputs is switched on for the path.  `step()` bumps the parameters' `_version` after the replay."""
 
     def __init__(self, path, aggregator, xyz, emb, conf, pdir, color, sample, near, far, zero_epsilon=1e-3, w_color=1.0, w_zero_one=1e-4,
-                 patch_num=None, patch_size=None, patch_layout="grid", warmup=2, optimizer=None, learnable_blur=None):
+                 patch_num=None, patch_size=None, patch_layout="grid", warmup=2, optimizer=None, learnable_blur=None, Rw2c=None):
         """sample: dict of example input tensors (see the class docstring) that fixes shapes and optional inputs.  learnable_blur: as for
         train_step (not together with a `blur_kernels` sample input); its buffers are static, so `blur_kernels_pred` follows every replay."""
+        _no_rotation("CapturedTrainStep", Rw2c, xyz)
         learnable_blur = _learnable_arg("CapturedTrainStep", sample.get("blur_kernels"), learnable_blur)
         self.path, self.agg = path, aggregator
         self.optimizer = optimizer

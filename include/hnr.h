@@ -20,7 +20,7 @@
  *
  * STABILITY.  Two tiers:
  *   STABLE  -- what a reference-side binding needs and what later versions keep source- and binary-compatible: hnr_version,
- *              hnr_last_error, hnr_points_bounds, hnr_grid_* (build / destroy / stats / bytes), hnr_march_query, hnr_ray_compact*, hnr_point_records,
+ *              hnr_last_error, hnr_points_bounds, hnr_grid_* (build / destroy / stats / bytes), hnr_march_query, hnr_ray_compact*, hnr_point_records (+ _parts),
  *              hnr_image_features*, hnr_render_forward* (+ workspace sizing), hnr_render_train_forward / _backward / _backward_depth (+ sizing),
  *              hnr_shipped_loss*, hnr_composite, hnr_ray_depth, hnr_ray_march, hnr_voxel_downsample*, hnr_probe_select, hnr_blur_*,
  *              hnr_frame_metrics* (and the HNR_FM_* row layout), hnr_depth_fuse*, hnr_range_crop*, hnr_nearest_view, hnr_point_view_attrs,
@@ -378,6 +378,29 @@ int hnr_point_records(const float *d_xyz, const float *d_conf, const float *d_di
 int hnr_chain_gather_rec(const float *d_rec, const int32_t *d_sample_pidx, const float *d_sample_loc_w, const float *d_raydir,
                          const float *d_campos, const float *d_camrot, const int32_t *d_vs_item, const int64_t *d_counts, int SR, int K,
                          int cap_samples, void *d_workspace, float *d_X5, int ld5, float *d_weight_out, float *d_conf_out, void *stream);
+/* Edited scenes: per-point rotations `neural_points.Rw2c` (models/neural_points/neural_points.py:720; run/editiing.py:196-209) as a PART TABLE:
+ *   d_part_rot [n_parts][9] f32 row-major and one part index per point, Rw2c of point p = d_part_rot[part of p]; n_parts <= HNR_MAX_PARTS.  For a
+ *   valid sample with neighbours p_0 .. p_7 on a ray of direction v (models/aggregators/point_aggregators.py:894-971):
+ *     dists[k, 0:3] = R_{p_k} (xyz_{p_k} - sample_loc_w)   (columns 3..5, the weight and conf_coefficient are those of the un-rotated offset),
+ *     v' = R_{p_0} v  (the point in SLOT 0, :897) feeds the view-direction encoding X5[s, 256:280] and every neighbour row's extras,
+ *     dir'_k = R_{p_k} points_dir[p_k]; extras dir'_k - v', dir'_k . v'.
+ *   y = R x is y_i = (R[i][0] x_0 + R[i][1] x_1) + R[i][2] x_2, every product and sum rounded on its own: the identity returns x bit for bit.
+ *   Nothing else sees the rotation (colour extras, the per-point table, the image branch, ray_dist, the composite).
+ * hnr_point_records_parts = hnr_point_records + the part index d_part[i] (int32, 0 .. n_parts - 1) as a float in the record's first spare slot
+ *   (rec[i][10]); hnr_chain_gather_rec_parts reads it from there, hnr_chain_gather_parts from d_part [N].  n_parts = 0: no rotation, the call
+ *   is hnr_chain_gather_rec / hnr_chain_gather.  A part index >= n_parts is the caller's error (not checked on the device). */
+#define HNR_MAX_PARTS 65536
+int hnr_point_records_parts(const float *d_xyz, const float *d_conf, const float *d_dir, const float *d_color, const int32_t *d_part, int N,
+                            float *d_rec, void *stream);
+int hnr_chain_gather_rec_parts(const float *d_rec, const float *d_part_rot, int n_parts, const int32_t *d_sample_pidx,
+                               const float *d_sample_loc_w, const float *d_raydir, const float *d_campos, const float *d_camrot,
+                               const int32_t *d_vs_item, const int64_t *d_counts, int SR, int K, int cap_samples, void *d_workspace,
+                               float *d_X5, int ld5, float *d_weight_out, float *d_conf_out, void *stream);
+int hnr_chain_gather_parts(const float *d_xyz, const float *d_conf, const float *d_dir, const float *d_color, const int32_t *d_part,
+                           const float *d_part_rot, int n_parts, const int32_t *d_sample_pidx, const float *d_sample_loc_w,
+                           const float *d_raydir, const float *d_campos, const float *d_camrot, const int32_t *d_vs_item,
+                           const int64_t *d_counts, int SR, int K, int cap_samples, void *d_workspace, float *d_X5, int ld5,
+                           float *d_weight_out, float *d_conf_out, void *stream);
 int hnr_chain_forward(const void *d_workspace, const float *d_point_table, int ldt, const void *d_packed, const int64_t *d_counts,
                       int cap_samples, float slope, float *d_X5, int ld5, float *d_sigma, float *d_dbg, int dbg_layer, void *stream);
 
@@ -666,6 +689,11 @@ typedef struct {
     const float *d_point_table; int ldt;                /* [N, ldt >= 256] per-point addend of block1.0                 */
     const float *d_rec;                                 /* optional hnr_point_records image of the four buffers above ([N,12]); NULL: the
                                                            gather reads the four buffers                                */
+    /* per-point rotations of an edited scene (hnr_chain_gather_parts); all zero: none                                   */
+    const int32_t *d_part;                              /* [N] part index of every point: read when d_rec is NULL, or when rec_parts = 0  */
+    const float *d_part_rot;                            /* [n_parts, 9]                                                  */
+    int n_parts;                                        /* 0 .. HNR_MAX_PARTS                                            */
+    int rec_parts;                                      /* != 0: d_rec was written by hnr_point_records_parts (it holds the part indices) */
 } hnr_render_cloud;
 typedef struct {
     const void  *d_chain;                               /* hnr_chain_pack                                               */
