@@ -116,6 +116,12 @@ class FrameBatchOut(ctypes.Structure):
     _fields_ = [("d_" + n, _P) for n in FRAME_OUTPUTS]
 
 
+class DepthBankC(ctypes.Structure):
+    """hnr_depth_bank"""
+    _fields_ = [("d_depth", _P), ("d_depth_intrinsic", _P), ("depth_f32", _I), ("F", _I), ("Hd", _I), ("Wd", _I), ("depth_div", _F), ("depth_min", _F),
+                ("depth_max", _F)]
+
+
 ADAM_MAX_GROUPS, ADAM_MAX_TENSORS, ADAM_CHUNK, ADAM_GROUP_DOUBLES, ADAM_ROW_DOUBLES = 4, 4096, 4096, 6, 10     # HNR_ADAM_*
 
 
@@ -276,6 +282,10 @@ SIGNATURES = {
                              ctypes.POINTER(FrameBatchOut), _P, ctypes.c_int64, _P]),
     "hnr_frame_item": (_I, [ctypes.POINTER(FrameBankC), ctypes.POINTER(FrameBankC), _P, _I, _I, _P, ctypes.c_int64, _I, _I, ctypes.POINTER(_F), _I,
                             ctypes.POINTER(FrameBatchOut), _P, ctypes.c_int64, _P]),
+    # depth supervision from resident depth frames: per-ray gt_depth, the loss term, the depth metrics row (csrc/depth_sup.hip)
+    "hnr_frame_depth_rays": (_I, [ctypes.POINTER(DepthBankC), _P, _P, _P, _I, _P, _P]),
+    "hnr_depth_loss": (_I, [_P, _P, _P, _I, _F, _P, _P, _P, _P, _P]),
+    "hnr_depth_metrics": (_I, [_P, _P, _P, _I, _P, _P]),
     # growth schedule: ray-miss loss + the table of the worst frames, one launch per step (csrc/rank.hip)
     "hnr_ray_miss_rank": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _P, _P]),
     # the optimiser step: Adam for all parameter groups in one launch + the schedule tick (csrc/adam.hip)

@@ -82,22 +82,28 @@ def render_image(renderer, cloud, frame, chunk_rays=0, sharded=None, group=None,
 
 
 def evaluate_frames(renderer, cloud, frames, evaluator=None, win=11, data_range=2.0, save_images=False, chunk_rays=0, sharded=None, group=None, on_frame=None,
-                    lpips=None):
+                    lpips=None, depth=False):
     """The reference's test pass over a test set (run/test_ft.py:127-260): render_image + one metrics row per frame (metrics.TestSetEvaluator.add:
     one launch behind the composite, no host read), frames being dataset items with gt_image [R,3].  Returns the evaluator -- summary() is
     the one host read, write(out_dir) leaves report_metrics' files -- on rank 0 when sharded, None on the other ranks.  render_image is called
     as it stands: the rendered frames are what a plain call gives; on_frame(index, render_out), when given, sees each of them (rank 0).
     lpips: a dict such as {"lpips": LPIPS('alex'), "vgglpips": LPIPS('vgg')} (perceptual.LPIPS with weights loaded) adds those columns
-    (TestSetEvaluator(lpips=...)); the rendered frame and the existing columns do not change."""
+    (TestSetEvaluator(lpips=...)); the rendered frame and the existing columns do not change.  depth=True: the frames carry gt_depth [R] (metres,
+    0 = no measurement: frames.BatchSampler.item of a bank with depth frames), render_image also forms the depth map (depth=True) and the
+    evaluator keeps one depth-error row per frame (TestSetEvaluator(depth=True): depth_abs / depth_rmse / depth_absrel / depth_d1); colours and
+    the existing columns do not change."""
     from .metrics import TestSetEvaluator
     frames = list(frames)
+    if depth and any("gt_depth" not in f for f in frames):
+        raise HnrError("evaluate_frames: depth=True needs gt_depth in every frame")
     for i, frame in enumerate(frames):
-        out = render_image(renderer, cloud, frame, chunk_rays=chunk_rays, sharded=sharded, group=group)
+        out = render_image(renderer, cloud, frame, chunk_rays=chunk_rays, sharded=sharded, group=group, depth=bool(depth))
         if out is None:
             continue
         if on_frame is not None:
             on_frame(i, out)
         if evaluator is None:
-            evaluator = TestSetEvaluator(len(frames), win=win, data_range=data_range, device=out["image"].device, save_images=save_images, lpips=lpips)
+            evaluator = TestSetEvaluator(len(frames), win=win, data_range=data_range, device=out["image"].device, save_images=save_images, lpips=lpips,
+                                         depth=bool(depth))
         evaluator.add(out, frame)
     return evaluator

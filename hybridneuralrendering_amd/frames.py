@@ -5,6 +5,8 @@ and its nearest frames, draws pixel coordinates with numpy, builds `raydir` with
 reference images.  A train split is 200 - 1000 frames of 480 x 640 x 3 bytes: it fits on the device as it is.  `FrameBank` holds it there,
 `BatchSampler.next()` writes the dataset item of the next step with at most three launches that read the frame number and the step counter from
 device memory -- no upload, no host read, capturable in a hipGraph.  Image decoding and resizing stay the caller's (once per scene).
+A bank may also hold the split's sensor depth frames (`FrameBank(depth=...)`): the batch then carries `gt_depth` per ray, written by a fourth
+launch of the same kind (csrc/depth_sup.hip), for train.train_step(gt_depth=, w_depth=).
 
 The nearest-view tables are per-frame constants and are computed on the host: `nearest_by_id` (ScanNet), `nearest_by_pose` (synthetic scenes).
 tests/frames_ref.py restates the sampler's arithmetic in NumPy; the GPU results equal it bit for bit.
@@ -87,9 +89,16 @@ class FrameBank:
     """All frames of one split on the device: images [F,H,W,3] uint8 (stored as they are) or float32, c2w [F,4,4], w2c = torch.inverse(c2w) (computed
     once, on the device), intrinsic [3,3] shared or [F,3,3], weight[f] = float32(weights[f] ** weight_exp) (float64 arithmetic, as
     scannet_ft_dataset.py:758; ones without weights) and angle[f] = float32(ids[f] / total_num_image * 2 pi) (:830).  `ids`: the frames' vids
-    (default 0..F-1); total_num_image defaults to max(ids) + 1."""
+    (default 0..F-1); total_num_image defaults to max(ids) + 1.
 
-    def __init__(self, images, c2w, intrinsic, device, ids=None, weights=None, weight_exp=1.0, total_num_image=None):
+    depth (optional): the split's sensor depth frames [F,Hd,Wd], stored as given -- raw uint16 (a NumPy uint16 array, or torch.int16 carrying the
+    uint16 bit pattern, cloud_init.DepthFusion's convention: a negative value v means 65536 + v) divided by `depth_div` when read, or float32 metres.
+    A value outside [depth_min, depth_max] reads as 0 = no measurement.  depth_intrinsic [3,3]: the depth camera's intrinsic when the depth frames
+    have another size or calibration than the colour frames; without it (Hd,Wd) must equal (H,W) and a ray reads the texel gt_image reads.  With
+    depth the samplers of this bank emit `gt_depth` [R] (hnr_frame_depth_rays; the definitions are in include/hnr.h and tests/depth_sup_ref.py)."""
+
+    def __init__(self, images, c2w, intrinsic, device, ids=None, weights=None, weight_exp=1.0, total_num_image=None, depth=None, depth_div=1000.,
+                 depth_min=0.3, depth_max=8.0, depth_intrinsic=None):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise HnrError("FrameBank: device must be a GPU (the HIP path has no CPU fallback)")
@@ -100,6 +109,7 @@ class FrameBank:
         if F < 1 or H < 1 or W < 1 or H * W > (1 << 26):
             raise HnrError("FrameBank: F, H, W >= 1 and H * W <= 2^26")
         self.F, self.H, self.W = F, H, W
+        depth, Kd = self._check_depth(depth, depth_div, depth_min, depth_max, depth_intrinsic)     # (before anything is uploaded)
         self.images = images.to(self.device).contiguous()
         c2w = torch.as_tensor(np.asarray(c2w.detach().cpu() if isinstance(c2w, torch.Tensor) else c2w, dtype=np.float32))
         if tuple(c2w.shape) != (F, 4, 4):
@@ -127,6 +137,44 @@ class FrameBank:
         self.nearest, self.reference, self.V = None, self, 0
         self._c = _lib.FrameBankC(_lib.ptr(self.images), _lib.ptr(self.c2w), _lib.ptr(self.w2c), _lib.ptr(self.intrinsic), _lib.ptr(self.weight),
                                   _lib.ptr(self.angle), 1 if self.images.dtype == torch.float32 else 0, F, H, W, 1 if K.dim() == 3 else 0)
+        self.depth = self.depth_intrinsic = self._dc = None
+        if depth is not None:
+            self.depth = depth.to(self.device).contiguous()
+            self.depth_intrinsic = None if Kd is None else Kd.to(self.device).contiguous()
+            self.depth_div, self.depth_min, self.depth_max = float(depth_div), float(depth_min), float(depth_max)
+            self._dc = _lib.DepthBankC(_lib.ptr(self.depth), _lib.ptr(self.depth_intrinsic), 1 if self.depth.dtype == torch.float32 else 0, F,
+                                       int(self.depth.shape[1]), int(self.depth.shape[2]), self.depth_div, self.depth_min, self.depth_max)
+
+    def _check_depth(self, depth, depth_div, depth_min, depth_max, depth_intrinsic):
+        """The depth arguments, validated before any upload -> (depth tensor as given or None, depth intrinsic [3,3] CPU tensor or None)."""
+        if depth is None:
+            if depth_intrinsic is not None:
+                raise HnrError("FrameBank: depth_intrinsic without depth")
+            return None, None
+        if isinstance(depth, np.ndarray):
+            if depth.dtype == np.uint16:                   # torch has no uint16 arithmetic: the bytes travel as int16, the kernel reads uint16
+                depth = np.ascontiguousarray(depth).view(np.int16)
+            if depth.dtype not in (np.int16, np.float32):
+                raise HnrError("FrameBank: depth must be uint16 (raw) or float32 (metres), got %s" % depth.dtype)
+            depth = torch.from_numpy(np.ascontiguousarray(depth))
+        if not isinstance(depth, torch.Tensor) or depth.dtype not in (torch.int16, torch.float32):
+            raise HnrError("FrameBank: depth must be uint16 (raw; torch.int16 with the uint16 bit pattern) or float32 (metres), got %s"
+                           % getattr(depth, "dtype", type(depth)))
+        if depth.dim() != 3 or int(depth.shape[0]) != self.F or int(depth.shape[1]) < 1 or int(depth.shape[2]) < 1 or \
+                int(depth.shape[1]) * int(depth.shape[2]) > (1 << 26):
+            raise HnrError("FrameBank: depth must be [%d,Hd,Wd] (one frame per image, Hd * Wd <= 2^26), got %s" % (self.F, tuple(depth.shape)))
+        if depth.is_cuda and depth.device != self.device:
+            raise HnrError("FrameBank: depth is on %s, the bank on %s" % (depth.device, self.device))
+        if not (float(depth_div) > 0 and float(depth_min) <= float(depth_max)):
+            raise HnrError("FrameBank: depth_div > 0 and depth_min <= depth_max")
+        Kd = None
+        if depth_intrinsic is not None:
+            Kd = torch.as_tensor(np.asarray(depth_intrinsic.detach().cpu() if isinstance(depth_intrinsic, torch.Tensor) else depth_intrinsic, dtype=np.float32))
+            if tuple(Kd.shape) != (3, 3):
+                raise HnrError("FrameBank: depth_intrinsic must be [3,3], got %s" % (tuple(Kd.shape),))
+        elif (int(depth.shape[1]), int(depth.shape[2])) != (self.H, self.W):
+            raise HnrError("FrameBank: depth frames of %dx%d for colour frames of %dx%d need depth_intrinsic" % (int(depth.shape[1]), int(depth.shape[2]), self.H, self.W))
+        return depth, Kd
 
     def set_nearest(self, table, reference=None):
         """table [F,V] int32: the rows of every frame's nearest reference frames in `reference` (default: this bank; a test-set bank names its
@@ -157,7 +205,9 @@ class BatchSampler:
     The dict has the dataset item's keys: raydir [R,3], pixel_idx [R,2] float32 (x, y), gt_image [R,3]; campos [3], camrotc2w = camrot [3,3], c2w [4,4],
     intrinsic [3,3]; c2w_nearest, w2c_nearest [V,4,4], campos_nearest [V,3], intrinsic_nearest [3,3], images_nearest [V,H,W,3] float32,
     frame_weight_nearest [V], vid_angle_nearest [V]; frame_weight [1] (device), bg_color [3], near, far, h, w; frame_row [1] int32 and, for
-    patch / dilated, patch_table [pn^2,3] int32 (d, x0, y0)."""
+    patch / dilated, patch_table [pn^2,3] int32 (d, x0, y0).  A bank with depth frames adds gt_depth [R] float32 (metres, 0 = no measurement): one
+    more launch behind the three, hnr_frame_depth_rays, which reads the frame row and the pixels the batch kernels just wrote -- still capturable;
+    `next(out=...)` writes it when `out` holds that key."""
 
     def __init__(self, bank, mode, size=None, dilation_setup=None, margin=0, seed=0, dir_norm=0, bg_color=(1, 1, 1), near=None, far=None,
                  downweight_blurry_feats=0):
@@ -209,7 +259,7 @@ class BatchSampler:
         self._item_scratch = torch.zeros((16,), dtype=torch.uint8, device=dev)
         self.step = torch.zeros((1,), dtype=torch.int64, device=dev)          # the step counter (read and advanced by the header kernel)
         self.schedule, self._n_schedule = None, 0
-        self._static, self._bound = None, {}
+        self._static, self._bound, self._own = None, {}, {}
 
     # ------------------------------------------------------------------------------------------------ plumbing
     def _shapes(self, R):
@@ -218,6 +268,8 @@ class BatchSampler:
         f, i = torch.float32, torch.int32
         sh = dict(raydir=((R, 3), f), pixel_idx=((R, 2), f), gt_image=((R, 3), f), campos=((3,), f), camrot=((3, 3), f), c2w=((4, 4), f), intrinsic=((3, 3), f),
                   frame_weight=((1,), f), bg_color=((3,), f), frame_row=((1,), i))
+        if b._dc is not None:
+            sh["gt_depth"] = ((R,), f)
         if V > 0:
             sh.update(c2w_nearest=((V, 4, 4), f), w2c_nearest=((V, 4, 4), f), campos_nearest=((V, 3), f), intrinsic_nearest=((3, 3), f),
                       images_nearest=((V, H, W, 3), f), frame_weight_nearest=((V,), f), vid_angle_nearest=((V,), f))
@@ -237,9 +289,19 @@ class BatchSampler:
         return d
 
     def _bind(self, tensors, R, what):
-        """name -> tensor  =>  hnr_frame_batch_out; every tensor checked against the expected element count and dtype"""
+        """name -> tensor  =>  (hnr_frame_batch_out, the depth launch's tensors or None); every tensor checked against the expected element count
+        and dtype.  gt_depth among the tensors: the lookup reads the item's frame_row, pixel_idx (and intrinsic, with a depth intrinsic) from the
+        device, so outputs of those names that the caller did not give are bound to tensors of the sampler's own (allocated here, once per R)."""
         sh = self._shapes(R)
         o = _lib.FrameBatchOut()
+        if "gt_depth" in sh and "gt_depth" in tensors:
+            tensors = dict(tensors)
+            for k in ("frame_row", "pixel_idx") + (("intrinsic",) if self.bank.depth_intrinsic is not None else ()):
+                if k not in tensors:
+                    if (k, R) not in self._own:
+                        self._own[(k, R)] = torch.empty(sh[k][0], dtype=sh[k][1], device=self.bank.device)
+                    tensors[k] = self._own[(k, R)]
+        dep = None
         for k, t in tensors.items():
             if k not in sh:
                 continue
@@ -250,8 +312,18 @@ class BatchSampler:
                     what, k, dt, "x".join(str(s) for s in shape), self.bank.device, getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
             if k == "images_nearest" and t.data_ptr() % 16:
                 raise HnrError("%s: images_nearest must be 16-byte aligned" % what)
-            setattr(o, "d_" + k, t.data_ptr())
-        return o
+            if k != "gt_depth":
+                setattr(o, "d_" + k, t.data_ptr())
+        if "gt_depth" in sh and "gt_depth" in tensors:
+            dep = (tensors["frame_row"], tensors["pixel_idx"], tensors.get("intrinsic"), tensors["gt_depth"])
+        return o, dep
+
+    def _depth_rays(self, dep, R):
+        """gt_depth of the item just written: one launch behind the batch's, reading its frame_row / pixel_idx on the device"""
+        row, pix, K, gt = dep
+        _lib.check(self.L.hnr_frame_depth_rays(ctypes.byref(self.bank._dc), _lib.ptr(row), _lib.ptr(pix),
+                                               _lib.ptr(K) if self.bank.depth_intrinsic is not None else None, R, _lib.ptr(gt), _lib.stream()),
+                   "hnr_frame_depth_rays")
 
     def _views(self):
         b = self.bank
@@ -283,10 +355,10 @@ class BatchSampler:
             if self._static is None:
                 t = self._alloc(self.R, True)
                 self._static = (self._finish(t), self._bind(t, self.R, "BatchSampler.next"))
-            res, o = self._static
+            res, (o, dep) = self._static
         else:
             key = tuple((k, v.data_ptr(), v.numel(), v.dtype) for k, v in out.items() if isinstance(v, torch.Tensor))
-            o = self._bound.get(key)
+            o, dep = self._bound.get(key, (None, None))
             if o is None:                                     # shapes and dtypes are checked once per set of tensors
                 t = {k: v for k, v in out.items() if isinstance(v, torch.Tensor)}
                 if "camrotc2w" in t:
@@ -295,13 +367,15 @@ class BatchSampler:
                     t["camrot"] = t.pop("camrotc2w")
                 if len(self._bound) > 16:
                     self._bound.clear()
-                o = self._bound[key] = self._bind(t, self.R, "BatchSampler.next")
+                o, dep = self._bound[key] = self._bind(t, self.R, "BatchSampler.next")
             res = out
         ref, nearest, V = self._views()
         with torch.cuda.device(self.bank.device):
             _lib.check(self.L.hnr_frame_batch(ctypes.byref(self.bank._c), ref, nearest, V, ctypes.byref(self.prm), _lib.ptr(self.schedule), self._n_schedule,
                                               _lib.ptr(self.step), ctypes.byref(o), _lib.ptr(self._scratch), int(self._scratch.numel()), _lib.stream()),
                        "hnr_frame_batch")
+            if dep is not None:
+                self._depth_rays(dep, self.R)
         return res
 
     def item(self, row, pixels=None):
@@ -319,10 +393,12 @@ class BatchSampler:
         else:
             R = (self.bank.W - 2 * self.margin) * (self.bank.H - 2 * self.margin)
         t = self._alloc(R, False)
-        o = self._bind(t, R, "BatchSampler.item")
+        o, dep = self._bind(t, R, "BatchSampler.item")
         ref, nearest, V = self._views()
         with torch.cuda.device(dev):
             _lib.check(self.L.hnr_frame_item(ctypes.byref(self.bank._c), ref, nearest, V, row, _lib.ptr(pixels), R, self.margin, self.dir_norm,
                                              (ctypes.c_float * 3)(*self.bg), self.downweight, ctypes.byref(o), _lib.ptr(self._item_scratch), 16, _lib.stream()),
                        "hnr_frame_item")
+            if dep is not None:
+                self._depth_rays(dep, R)                      # (the row travels through the item's own frame_row word on the device)
         return self._finish(t)

@@ -96,3 +96,64 @@ def shipped_loss_grads(coarse_raycolor, conf_coefficient, gt_image, ray_mask, ze
     device_frame_weight: a one-float device tensor holding the item's scalar (a captured step; the kernel reads it)."""
     fw = device_frame_weight if device_frame_weight is not None else _fw(frame_weight)
     return _loss_call(coarse_raycolor, conf_coefficient, gt_image, ray_mask, zero_epsilon, w_color, w_zero_one, fw, bool(conf_rows))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The depth term (hnr_depth_loss, csrc/depth_sup.hip): masked mean of (D - d)^2 over the rays with a hit and a measurement.  The reference's
+# depth_loss_items branch (models/base_rendering_model.py:1209-1215) has no dataset that feeds it; include/hnr.h defines the term.
+# ----------------------------------------------------------------------------------------------------------------------
+def _depth_args(coarse_depth, gt_depth, ray_mask, w_depth):
+    D = _lib.require_gpu(coarse_depth.detach(), "coarse_depth", torch.float32).reshape(-1)
+    d = _lib.require_gpu(gt_depth, "gt_depth", torch.float32).reshape(-1)
+    m = _lib.require_gpu(ray_mask, "ray_mask").reshape(-1)
+    if m.dtype != torch.int8:
+        m = m.to(torch.int8)
+    R = int(D.shape[0])
+    if R < 1 or d.shape[0] != R or m.shape[0] != R:
+        raise HnrError("depth_loss: coarse_depth, gt_depth and ray_mask must hold one value per ray (%d, %d, %d)" % (R, d.shape[0], m.shape[0]))
+    if d.device != D.device or m.device != D.device:
+        raise HnrError("depth_loss: coarse_depth, gt_depth and ray_mask must be on one device")
+    w = float(w_depth)
+    if not (w >= 0.0 and w < float("inf")):
+        raise HnrError("depth_loss: w_depth must be finite and >= 0, got %r" % (w_depth,))
+    return D, d, m, R, w
+
+
+def depth_loss_grads(coarse_depth, gt_depth, ray_mask, w_depth, total=None, want_grad=True):
+    """The depth term without an autograd graph, one launch: (out3 = {L, n, w_depth L} on the device, d (w_depth L) / d coarse_depth [R]).
+    L = mean over the rays with ray_mask > 0 and gt_depth > 0 of (coarse_depth - gt_depth)^2 (0 when there is none).  total: the `parts`
+    tensor of shipped_loss_grads (or any float32 device tensor); w_depth L is added to its first element on the device, after the frame-weight
+    scaling the shipped kernels applied, as the reference orders it (:1204-1215)."""
+    L = _lib.lib()
+    D, d, m, R, w = _depth_args(coarse_depth, gt_depth, ray_mask, w_depth)
+    if total is not None:
+        total = _lib.require_gpu(total, "total", torch.float32)
+        if total.numel() < 1 or not total.is_contiguous() or total.device != D.device:
+            raise HnrError("depth_loss: total must be a contiguous float32 tensor on the depth's device")
+    out3 = torch.empty((3,), dtype=torch.float32, device=D.device)
+    g = torch.empty_like(D) if want_grad else None
+    p = _lib.ptr
+    with torch.cuda.device(D.device):
+        _lib.check(L.hnr_depth_loss(p(D), p(d), p(m), R, w, p(total), p(out3), p(g), None, _lib.stream()), "hnr_depth_loss")
+    return out3, g
+
+
+class _DepthLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, coarse_depth, gt_depth, ray_mask, w_depth):
+        out3, g = depth_loss_grads(coarse_depth, gt_depth, ray_mask, w_depth)
+        ctx.save_for_backward(g)
+        ctx.shape = coarse_depth.shape
+        ctx.mark_non_differentiable(out3)
+        return out3[2].clone(), out3
+
+    @staticmethod
+    def backward(ctx, g_term, _g_out):
+        (g,) = ctx.saved_tensors
+        return (g * g_term).reshape(ctx.shape), None, None, None
+
+
+def depth_loss(coarse_depth, gt_depth, ray_mask, w_depth=1.0):
+    """(w_depth * L, out3 = {L, n, w_depth L}) over the same kernel; the first is differentiable w.r.t. coarse_depth (what
+    render_train(want_depth=True) returns): `loss = shipped_loss(...)[0] + depth_loss(out["coarse_depth"], gt_depth, out["ray_mask"], w)[0]`."""
+    return _DepthLoss.apply(coarse_depth, gt_depth, ray_mask, w_depth)

@@ -104,6 +104,51 @@ def derive(rows):
     return res
 
 
+# the row hnr_depth_metrics writes (include/hnr.h: HNR_DM_*)
+DM = dict(N=0, ABS=1, SQ=2, ABSREL=3, D1=4)
+DM_NCOLS = 5
+
+
+def depth_frame_metrics(render_out, frame, out=None, row=0):
+    """One frame's row of depth errors, on the device, without a host synchronisation (hnr_depth_metrics, one launch): over the rays with a hit
+    (ray_mask > 0) and a measurement (gt_depth > 0), {n, sum |e|, sum e^2, sum |e| / d, #(max(D / d, d / D) < 1.25)} with e = D - d in fp64.
+    render_out: driver.render_image(depth=True)'s result (coarse_depth [R], ray_mask [R]); frame: the item with gt_depth [R] (metres, 0 = no
+    measurement; frames.BatchSampler.item of a bank with depth frames).  out / row: a [capacity, DM_NCOLS] float64 device table."""
+    L = _lib.lib()
+    if "coarse_depth" not in render_out:
+        raise HnrError("depth_frame_metrics: the render has no coarse_depth (driver.render_image(..., depth=True))")
+    if "gt_depth" not in frame:
+        raise HnrError("depth_frame_metrics: the frame has no gt_depth (a FrameBank with depth frames emits it)")
+    D = _lib.require_gpu(render_out["coarse_depth"], "coarse_depth", torch.float32).reshape(-1)
+    d = _lib.require_gpu(frame["gt_depth"], "gt_depth", torch.float32).reshape(-1)
+    mask = _lib.require_gpu(render_out["ray_mask"], "ray_mask").reshape(-1)
+    if mask.dtype != torch.int8:
+        mask = mask.to(torch.int8)
+    R = int(D.shape[0])
+    if R < 1 or d.shape[0] != R or mask.shape[0] != R or d.device != D.device:
+        raise HnrError("depth_frame_metrics: coarse_depth, gt_depth and ray_mask must hold one value per ray on one device")
+    if out is None:
+        out = torch.zeros((1, DM_NCOLS), dtype=torch.float64, device=D.device)
+    if not (out.is_cuda and out.dtype == torch.float64 and out.dim() == 2 and out.shape[1] == DM_NCOLS and out.is_contiguous()):
+        raise HnrError("depth_frame_metrics: out must be a contiguous [capacity, %d] float64 table on the GPU" % DM_NCOLS)
+    if not 0 <= row < out.shape[0]:
+        raise HnrError("depth_frame_metrics: row %d outside the table (%d rows)" % (row, out.shape[0]))
+    p = _lib.ptr
+    with torch.cuda.device(D.device):
+        _lib.check(L.hnr_depth_metrics(p(D), p(d), p(mask), R, p(out[row]), _lib.stream()), "hnr_depth_metrics")
+    return out
+
+
+def derive_depth(rows):
+    """Host side: [n, DM_NCOLS] float64 rows -> per-frame depth_abs (mean |e|, metres), depth_rmse, depth_absrel (mean |e| / d), depth_d1 (the
+    fraction of rays with max(D / d, d / D) < 1.25) and depth_n; NaN for a frame without a ray that has both a hit and a measurement."""
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, DM_NCOLS)
+    n = rows[:, DM["N"]]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return dict(depth_abs=rows[:, DM["ABS"]] / n, depth_rmse=np.sqrt(rows[:, DM["SQ"]] / n), depth_absrel=rows[:, DM["ABSREL"]] / n,
+                    depth_d1=rows[:, DM["D1"]] / n, depth_n=n.copy())
+
+
 class TestSetEvaluator:
     """A [capacity, NCOLS] device table of per-frame rows: add() per frame (no host synchronisation), summary() = the one host read.
 
@@ -116,9 +161,13 @@ class TestSetEvaluator:
 
     ORDER = ("psnr", "ssim", "lpips", "vgglpips", "rmse")          # report_metrics' order; other lpips keys follow "vgglpips"
 
-    def __init__(self, capacity, win=11, data_range=2.0, device="cuda:0", save_images=False, lpips=None):
+    def __init__(self, capacity, win=11, data_range=2.0, device="cuda:0", save_images=False, lpips=None, depth=False):
         if capacity <= 0:
             raise HnrError("TestSetEvaluator: capacity must be positive")
+        # depth: add() also fills row n of a [capacity, DM_NCOLS] table of its own (depth_frame_metrics: the render needs coarse_depth, the frame
+        # gt_depth) and summary() gains depth_abs / depth_rmse / depth_absrel / depth_d1 / depth_n; the other table does not change
+        self.depth_table = torch.zeros((int(capacity), DM_NCOLS), dtype=torch.float64, device=device) if depth else None
+        self._depth_host = None
         self.capacity, self.win, self.data_range, self.save_images = int(capacity), int(win), float(data_range), bool(save_images)
         self.table = torch.zeros((self.capacity, NCOLS), dtype=torch.float64, device=device)
         self.n = 0
@@ -175,8 +224,10 @@ class TestSetEvaluator:
             if model is None:
                 raise HnrError("TestSetEvaluator: %s has rows but no model (from_rows): add() is not available" % key)
             model.pair8(pair[0], pair[1], out=self.lpips_tables[key], row=self.n)
+        if self.depth_table is not None:
+            depth_frame_metrics(render_out, frame, out=self.depth_table, row=self.n)
         self.n += 1
-        self._host = self._lpips_host = None
+        self._host = self._lpips_host = self._depth_host = None
         return self.n - 1
 
     def summary(self):
@@ -190,6 +241,10 @@ class TestSetEvaluator:
             for k, rows in self._lpips_host.items():
                 res[k] = rows[:, 0].copy()
                 res[k + "_layers"] = rows[:, 1:].copy()
+        if self.depth_table is not None:
+            if self._depth_host is None:
+                self._depth_host = self.depth_table[:self.n].cpu().numpy()
+            res.update(derive_depth(self._depth_host))
         with np.errstate(invalid="ignore"):
             res["mean"] = {k: (float(np.mean(v)) if len(v) else float("nan")) for k, v in res.items() if not k.endswith("_layers")}
         return res

@@ -404,14 +404,16 @@ def render_train(path, aggregator, xyz, emb, conf, pdir, color, raydir, campos, 
 
 def _queue_step(path, cloud, raydir, campos, camrot, bg_color, near, far, c2w_nearest, campos_nearest, intrinsic_nearest, images_nearest, gt_image,
                 zero_epsilon, w_color, w_zero_one, frame_weight, tmid, ray_drop, frame_weight_nearest, blur, w2c_nearest, device_frame_weight=None,
-                learnable_blur=None):
-    """The launches of one step, queued back to back on the current stream: forward -> [blur module] -> loss kernels -> [blur module backward] ->
-    backward.  Nothing is read back; shared by train_step (eager) and CapturedTrainStep (inside a hipGraph capture).  learnable_blur
-    (blur.LearnableBlur): the learnable-kernel form of the blur module in the same two places; its eight gradients join `ag`."""
-    from .losses import shipped_loss_grads
+                learnable_blur=None, gt_depth=None, w_depth=0.0):
+    """The launches of one step, queued back to back on the current stream: forward -> [blur module] -> loss kernels -> [depth term] ->
+    [blur module backward] -> backward.  Nothing is read back; shared by train_step (eager) and CapturedTrainStep (inside a hipGraph capture).
+    learnable_blur (blur.LearnableBlur): the learnable-kernel form of the blur module in the same two places; its eight gradients join `ag`.
+    gt_depth [R] (checked by _depth_arg): the forward also forms coarse_depth, hnr_depth_loss adds w_depth * L to the total and its gradient goes
+    into the backward (hnr_render_train_backward_depth); None: none of that."""
+    from .losses import shipped_loss_grads, depth_loss_grads
     from .blur import blur_select, blur_select_bwd
     out, S = path.forward(cloud, raydir, campos, camrot, bg_color, near, far, c2w_nearest, campos_nearest, intrinsic_nearest, images_nearest,
-                          frame_weight=frame_weight_nearest, tmid=tmid, ray_drop=ray_drop, w2c_nearest=w2c_nearest)
+                          frame_weight=frame_weight_nearest, tmid=tmid, ray_drop=ray_drop, w2c_nearest=w2c_nearest, want_depth=gt_depth is not None)
     col = out["coarse_raycolor"]
     sel = None
     if blur is not None:
@@ -424,13 +426,19 @@ def _queue_step(path, cloud, raydir, campos, camrot, bg_color, near, far, c2w_ne
         col = learnable_blur.forward(col, gt_image)
     parts, g_col, g_cc = shipped_loss_grads(col, out["conf_coefficient"], gt_image, out["ray_mask"], zero_epsilon, w_color, w_zero_one, frame_weight,
                                             conf_rows=True, device_frame_weight=device_frame_weight)
+    g_depth = loss_depth = None
+    if gt_depth is not None:
+        # the depth of the UNBLURRED render (the blur module models the camera's colour response, not its geometry); parts[0] += w_depth * L
+        loss_depth, g_depth = depth_loss_grads(out["coarse_depth"], gt_depth, out["ray_mask"], w_depth, total=parts)
     if blur is not None:
         g_col = blur_select_bwd(g_col, kk, sel, pn, ps)
     elif learnable_blur is not None:
         g_col, g_blur = learnable_blur.backward(g_col)        # two launches: per patch, then the weight / bias gradients
-    pg, ag = path.backward(S, g_col, g_cc)
+    pg, ag = path.backward(S, g_col, g_cc, g_depth)
     out = dict(out)
     out["loss"] = parts
+    if loss_depth is not None:
+        out["loss_depth"] = loss_depth
     if blur is not None:
         out["blurred_raycolor"], out["blur_select"] = col, sel
     elif learnable_blur is not None:
@@ -450,6 +458,27 @@ def _learnable_arg(who, blur_kernels, learnable_blur):
     if not isinstance(learnable_blur, LearnableBlur):
         raise HnrError("%s: learnable_blur must be a blur.LearnableBlur" % who)
     return learnable_blur
+
+
+def _depth_arg(who, gt_depth, w_depth, raydir, patch_layout="grid"):
+    """gt_depth [R] on the rays' device and w_depth >= 0, checked before anything is queued -> (gt_depth flat or None, float w_depth)."""
+    w = float(w_depth)
+    if gt_depth is None:
+        if w != 0.0:
+            raise HnrError("%s: w_depth=%g without gt_depth (frames.BatchSampler emits it for a FrameBank with depth frames)" % (who, w))
+        return None, 0.0
+    if not (w >= 0.0 and w < float("inf")):
+        raise HnrError("%s: w_depth must be finite and >= 0, got %r" % (who, w_depth))
+    if not isinstance(gt_depth, torch.Tensor) or not gt_depth.is_cuda or gt_depth.dtype != torch.float32:
+        raise HnrError("%s: gt_depth must be a float32 tensor on the GPU (0 = no measurement)" % who)
+    R = int(raydir.reshape(-1, 3).shape[0])
+    if gt_depth.numel() != R or gt_depth.device != raydir.device:
+        raise HnrError("%s: gt_depth must hold one depth per ray (%d) on %s, got %d on %s" % (who, R, raydir.device, gt_depth.numel(), gt_depth.device))
+    if patch_layout == "patch_major":
+        # whole-patch packing is a rank's share of a sharded batch (parallel.shard_patches): the masked mean's n would be the rank's own
+        raise HnrError("%s: gt_depth is not supported for a rank's share of a sharded batch (patch_layout='patch_major'): the depth term's ray "
+                       "count is local to the call" % who)
+    return gt_depth.contiguous().reshape(-1), w
 
 
 def _blur_arg(blur_kernels, patch_num, patch_size, patch_layout):
@@ -486,7 +515,8 @@ def _assign_grads(aggregator, emb, conf, pdir, color, pg, ag, accumulate=True, c
 def train_step(path, aggregator, xyz, emb, conf, pdir, color, raydir, campos, camrot, bg_color, near, far, c2w_nearest, campos_nearest,
                intrinsic_nearest, images_nearest, gt_image, zero_epsilon=1e-3, w_color=1.0, w_zero_one=1e-4, frame_weight=None, tmid=None,
                ray_drop=None, assign_grads=True, frame_weight_nearest=None, blur_kernels=None, patch_num=None, patch_size=None, patch_layout="grid",
-               w2c_nearest=None, accumulate_grads=True, device_frame_weight=None, optimizer=None, learnable_blur=None, Rw2c=None):
+               w2c_nearest=None, accumulate_grads=True, device_frame_weight=None, optimizer=None, learnable_blur=None, Rw2c=None, gt_depth=None,
+               w_depth=0.0):
     """forward -> [blur module] -> shipped loss terms -> backward of one ray batch as groups of library launches queued back to back: no autograd
     graph, no masked copies, nothing read back to the host -- the body of the reference's optimize_parameters before its optimizer steps
     (models/neural_points_volumetric_model.py:202-214: self.forward(); loss_total.backward(), with compute_losses of
@@ -521,15 +551,28 @@ def train_step(path, aggregator, xyz, emb, conf, pdir, color, raydir, campos, ca
     backward on the same stream -- two more launches that read `pg` / `ag` in place -- and .grad is NOT assigned (the reference's
     optimizer.step() + neural_point_optimizer.step() + scheduler.step(), models/mvs_points_volumetric_model.py:111-131, models/base_model.py:148-150).
     The parameters' `_version` is bumped, so the renderer's caches follow the new weights.  With TrainPath.reuse_outputs the gradient buffers keep
-    their addresses and the optimiser's descriptor table is uploaded once; without it, once per step.  Returns (outputs dict with `loss` = {total, colour MSE, zero-one mean, valid rays} on the device and `_saved` = the step's
+    their addresses and the optimiser's descriptor table is uploaded once; without it, once per step.
+
+    gt_depth [R] float32 on the device (metres, 0 = no measurement; frames.BatchSampler's `gt_depth` for a FrameBank with depth frames) with
+    w_depth >= 0: depth supervision.  The forward also forms coarse_depth (want_depth), hnr_depth_loss -- one launch behind the shipped-loss
+    kernels -- computes L = mean over the rays with a hit and a measurement of (coarse_depth - gt_depth)^2, adds w_depth * L to `loss`[0] (NOT
+    scaled by the frame weight: the reference scales before it adds its depth items, models/base_rendering_model.py:1204-1215) and hands its gradient
+    to the backward (hnr_render_train_backward_depth).  Depth supervises the UNBLURRED render: with a blur module the colour losses see the blurred
+    colours, the depth term the depth as rendered.  The outputs gain `coarse_depth` and `loss_depth` = {L, rays counted, w_depth L}.  Same
+    arithmetic as render_train(want_depth=True) + losses.depth_loss + backward().  None: exactly the launches above.  Not covered: a rank's share
+    of a sharded batch (the ray count n is local; patch_layout="patch_major" raises, and a caller that shards by hand would have to all-reduce n),
+    Rw2c clouds (raise), the TORCH_LIBRARY ops.
+
+    Returns (outputs dict with `loss` = {total, colour MSE, zero-one mean, valid rays} on the device and `_saved` = the step's
     state for TrainPath.touched_points / the flat weight-gradient buffer, point grads dict, aggregator grads dict keyed by parameter name)."""
     _no_rotation("train_step", Rw2c, xyz)           # (Rw2c: only so that a non-identity one raises; see _no_rotation)
     learnable_blur = _learnable_arg("train_step", blur_kernels, learnable_blur)
+    gt_depth, w_depth = _depth_arg("train_step", gt_depth, w_depth, raydir, patch_layout)
     cloud = PointCloud(xyz, emb.detach(), conf.detach(), pdir.detach(), color.detach())
     out, S, pg, ag = _queue_step(path, cloud, raydir, campos, camrot, bg_color, near, far, c2w_nearest, campos_nearest, intrinsic_nearest, images_nearest,
                                  gt_image, zero_epsilon, w_color, w_zero_one, frame_weight, tmid, ray_drop, frame_weight_nearest,
                                  _blur_arg(blur_kernels, patch_num, patch_size, patch_layout), w2c_nearest, device_frame_weight=device_frame_weight,
-                                 learnable_blur=learnable_blur)
+                                 learnable_blur=learnable_blur, gt_depth=gt_depth, w_depth=w_depth)
     if learnable_blur is not None and not path.reuse_outputs:
         # LearnableBlur writes into its own static buffers; without reuse_outputs a step hands out gradient tensors of its own (240 KB)
         ag.update({n: ag[n].clone() for n in learnable_blur.names})
@@ -564,9 +607,11 @@ class CapturedTrainStep:
     addresses then: TrainPath.reuse_outputs is switched on for the path.  `step()` bumps the parameters' `_version` after the replay."""
 
     def __init__(self, path, aggregator, xyz, emb, conf, pdir, color, sample, near, far, zero_epsilon=1e-3, w_color=1.0, w_zero_one=1e-4,
-                 patch_num=None, patch_size=None, patch_layout="grid", warmup=2, optimizer=None, learnable_blur=None, Rw2c=None):
+                 patch_num=None, patch_size=None, patch_layout="grid", warmup=2, optimizer=None, learnable_blur=None, Rw2c=None, w_depth=0.0):
         """sample: dict of example input tensors (see the class docstring) that fixes shapes and optional inputs.  learnable_blur: as for
-        train_step (not together with a `blur_kernels` sample input); its buffers are static, so `blur_kernels_pred` follows every replay."""
+        train_step (not together with a `blur_kernels` sample input); its buffers are static, so `blur_kernels_pred` follows every replay.
+        A `gt_depth` [R] tensor in the sample captures the depth-supervised form of the step with the weight w_depth (train_step(gt_depth=,
+        w_depth=)); it is an input like the others: `step(gt_depth=...)` copies it, `sampler.next(out=cap.inputs)` writes it in place."""
         _no_rotation("CapturedTrainStep", Rw2c, xyz)
         learnable_blur = _learnable_arg("CapturedTrainStep", sample.get("blur_kernels"), learnable_blur)
         self.path, self.agg = path, aggregator
@@ -579,6 +624,7 @@ class CapturedTrainStep:
         for k in req:
             if k not in sample:
                 raise HnrError("CapturedTrainStep: sample input %r is missing" % k)
+        _depth_arg("CapturedTrainStep", sample.get("gt_depth"), w_depth, sample["raydir"], patch_layout)
         st = {k: _lib.require_gpu(v, k).clone() for k, v in sample.items() if isinstance(v, torch.Tensor) and k != "frame_weight"}
         if "w2c_nearest" not in st:
             st["w2c_nearest"] = torch.inverse(st["c2w_nearest"].reshape(-1, 4, 4)).contiguous()
@@ -593,7 +639,7 @@ class CapturedTrainStep:
             return _queue_step(path, cloud, st["raydir"], st["campos"], st["camrot"], st["bg_color"], near, far, st["c2w_nearest"], st["campos_nearest"],
                                st["intrinsic_nearest"], st["images_nearest"], st["gt_image"], zero_epsilon, w_color, w_zero_one, None, st.get("tmid"),
                                st.get("ray_drop"), st.get("frame_weight_nearest"), blur, st["w2c_nearest"], device_frame_weight=st["frame_weight"],
-                               learnable_blur=learnable_blur)
+                               learnable_blur=learnable_blur, gt_depth=st.get("gt_depth"), w_depth=float(w_depth))
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):

@@ -27,7 +27,7 @@
  *              hnr_featnet_*, hnr_point_embed*, hnr_geo_consistency, hnr_geo_filter_select*, hnr_mvsnet_*,
  *              hnr_alpha_pack, hnr_visual_hull_select*, hnr_point_occlusion*, hnr_point_view_attrs_vis,
  *              hnr_frame_batch*, hnr_frame_item, hnr_ray_miss_rank, hnr_raft_flow*, hnr_blur_score_pair* (hnr_blur_edges and the other hnr_raft_*
- *              entries are STAGE), hnr_adam_plan, hnr_adam_step.
+ *              entries are STAGE), hnr_adam_plan, hnr_adam_step, hnr_frame_depth_rays, hnr_depth_loss, hnr_depth_metrics (and the HNR_DM_* row layout).
  *   STAGE   -- everything else (hnr_chain_*, hnr_mlp3_*, hnr_merge*, hnr_mixup_stage, hnr_proj_*, hnr_h2*, hnr_linear_*, hnr_gather_*, hnr_ksum*,
  *              hnr_segment_*, hnr_absmax, hnr_div_probe, hnr_image_features_bwd_bbox, the glue kernels of the training backward -- hnr_final_color_bwd*,
  *              hnr_ksum_bwd_rows8, hnr_extras_dgrad, hnr_point_small_grads, hnr_point_rows_bwd, hnr_dleaky_add, hnr_sum_views, hnr_unique_points*,
@@ -1110,6 +1110,67 @@ int hnr_frame_batch(const hnr_frame_bank *target, const hnr_frame_bank *referenc
 int hnr_frame_item(const hnr_frame_bank *target, const hnr_frame_bank *reference, const int32_t *d_nearest, int V, int row, const float *d_pixels,
                    int64_t n_rays, int margin, int dir_norm, const float *bg_color, int downweight_blurry_feats, const hnr_frame_batch_out *out,
                    void *d_scratch, int64_t scratch_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Depth supervision from resident sensor depth (csrc/depth_sup.hip): the per-ray ground-truth depth of a batch, the depth term of the training loss
+ * with its gradient, and the depth error of a rendered test frame.  The reference has a `depth_loss_items` branch
+ * (models/base_rendering_model.py:1209-1215) but neither of its datasets emits gt_depth or gt_mask, so the behaviour is DEFINED here and restated
+ * in tests/depth_sup_ref.py.  All three: one launch, stream-ordered, no allocation, no host read, no atomics, sums in a fixed order (two runs give
+ * the same bits), capturable on one stream.  gt_depth = 0 means "no measurement" everywhere.
+ *
+ * hnr_depth_bank -- the depth frames of a split, beside its hnr_frame_bank (same F, same rows):
+ *   d_depth [F,Hd,Wd] uint16 raw sensor values, or float32 metres with depth_f32 = 1; stored as given;
+ *   d_depth_intrinsic [3,3] on the device, or NULL: then (Hd, Wd) is the colour frame's (H, W) and a ray reads the texel gt_image reads;
+ *   depth_div (raw units per metre, 1000 for ScanNet), depth_min, depth_max: the valid range in metres. */
+typedef struct {
+    const void *d_depth;
+    const float *d_depth_intrinsic;
+    int depth_f32, F, Hd, Wd;
+    float depth_div, depth_min, depth_max;
+} hnr_depth_bank;
+
+/* hnr_frame_depth_rays -- d_gt_depth [R] float32 for the rays of an item, one lane per ray.
+ *   frame        row = d_frame_row[0], READ ON THE DEVICE: the word hnr_frame_batch / hnr_frame_item wrote (their d_frame_row output), so the call
+ *                follows the batch inside a captured graph.  There is no host-row variant: an explicit item passes its row through that same
+ *                device int.  A row outside the bank reads row 0, like the other frame kernels.
+ *   value        d = (float) raw / depth_div, a correctly rounded division (read_depth of the reference's dataset); float banks are copied;
+ *                d = 0 unless depth_min <= d <= depth_max (so d > depth_max, d < depth_min and a NaN all read 0).
+ *   pixel        (px, py) = d_pixel_idx[r] (x, y), the item's pixel_idx.
+ *     no depth intrinsic:  (u, v) = ((int) px, (int) py), the texel gt_image reads.
+ *     depth intrinsic Kd:  the ray's plane coordinates as the batch kernel forms them, x = ((px + 0.5f) - K02) / K00, y = ((py + 0.5f) - K12) / K11 with
+ *                K = d_intrinsic [3,3], the item's colour intrinsic; u = (int) floorf((x * Kd00 + Kd02) + 0.5f), v = (int) floorf((y * Kd11 + Kd12) + 0.5f):
+ *                integer pixel = centre, the convention load_init_depth_points unprojects with (scannet_ft_dataset.py:617-633), so supervision and
+ *                the initial cloud agree.  Each fp32 operation is rounded on its own in the order written.
+ *     (u, v) outside the depth frame: 0.
+ *   d_intrinsic may be NULL without a depth intrinsic.  1 <= R <= 2^26. */
+int hnr_frame_depth_rays(const hnr_depth_bank *bank, const int32_t *d_frame_row, const float *d_pixel_idx, const float *d_intrinsic, int R,
+                         float *d_gt_depth, void *stream);
+
+/* hnr_depth_loss -- the depth term of the training loss, value and gradient, ONE workgroup (batches are a few thousand rays; any 1 <= R <= 2^26 is
+ * correct, the 1024 lanes stride over the rays).
+ *   m_r = d_ray_mask[r] > 0 && d_gt_depth[r] > 0,  n = sum m_r
+ *   L = sum m_r (D_r - d_r)^2 / n, 0 when n = 0: a masked mean like the colour item (the reference's unmasked mean would make the weight depend on
+ *       the hit fraction).  Each (D_r - d_r)^2 is formed in fp32 (difference, then square) and the SUM RUNS IN fp64 in a fixed order -- per lane
+ *       over r = lane, lane + 1024, ...; an xor butterfly (32, 16, .. 1) over each wave; the sixteen waves in order -- then L = (float)(sum / n).
+ *   d_out3 = {L, n, w_depth * L};  d_total[0] += w_depth * L, one fp32 add (skipped when n = 0: the bits of d_total stay) -- d_total is d_out4 of
+ *       the hnr_shipped_loss* kernels, queued before this call; NULL: value only.  The term is NOT multiplied by the frame weight: the reference
+ *       scales by frame_weight before it adds its depth items (:1204-1215).
+ *   d_g_depth[r] = m_r * (D_r - d_r) * ((2 w_depth) / (float) n) -- the scale once in fp32, a correctly rounded division -- and exactly 0 where
+ *       m_r = 0 or n = 0; NULL: no gradient.  It is the d_g_depth of hnr_render_train_backward_depth.
+ *   w_depth >= 0 and finite.  d_scratch is not used (the reduction stays in LDS) and may be NULL. */
+int hnr_depth_loss(const float *d_depth, const float *d_gt_depth, const int8_t *d_ray_mask, int R, float w_depth, float *d_total, float *d_out3,
+                   float *d_g_depth, void *d_scratch, void *stream);
+
+/* hnr_depth_metrics -- the depth error of a rendered frame over the rays with a hit and a measurement (m_r as above), ONE workgroup:
+ *   d_row [5] fp64 = {n, sum |e|, sum e^2, sum |e| / d, #(max(D / d, d / D) < 1.25)}, e = D - d in fp64 from the fp32 inputs, sums in the fixed
+ *   order of hnr_depth_loss.  The threshold is evaluated as D > 0 && D < 1.25 d && d < 1.25 D (exact in fp64). */
+#define HNR_DM_N       0
+#define HNR_DM_ABS     1
+#define HNR_DM_SQ      2
+#define HNR_DM_ABSREL  3
+#define HNR_DM_D1      4
+#define HNR_DM_NCOLS   5
+int hnr_depth_metrics(const float *d_depth, const float *d_gt_depth, const int8_t *d_ray_mask, int R, double *d_row, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Growth schedule, the per-step part: the step's ray-miss loss and the table of the worst frames (prob_mode 0), ONE launch of one workgroup.
