@@ -286,6 +286,9 @@ SIGNATURES = {
     "hnr_frame_depth_rays": (_I, [ctypes.POINTER(DepthBankC), _P, _P, _P, _I, _P, _P]),
     "hnr_depth_loss": (_I, [_P, _P, _P, _I, _F, _P, _P, _P, _P, _P]),
     "hnr_depth_metrics": (_I, [_P, _P, _P, _I, _P, _P]),
+    # patch SSIM term of the training loss, value + gradient (csrc/ssim_loss.hip)
+    "hnr_ssim_loss_scratch_bytes": (ctypes.c_int64, [_I]),
+    "hnr_ssim_loss": (_I, [_P, _P, _P, _I, _I, _I, ctypes.POINTER(_F), _F, _F, _P, _P, _P, _P, _I, _P, _P]),
     # growth schedule: ray-miss loss + the table of the worst frames, one launch per step (csrc/rank.hip)
     "hnr_ray_miss_rank": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _P, _P]),
     # the optimiser step: Adam for all parameter groups in one launch + the schedule tick (csrc/adam.hip)

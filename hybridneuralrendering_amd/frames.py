@@ -207,7 +207,11 @@ class BatchSampler:
     frame_weight_nearest [V], vid_angle_nearest [V]; frame_weight [1] (device), bg_color [3], near, far, h, w; frame_row [1] int32 and, for
     patch / dilated, patch_table [pn^2,3] int32 (d, x0, y0).  A bank with depth frames adds gt_depth [R] float32 (metres, 0 = no measurement): one
     more launch behind the three, hnr_frame_depth_rays, which reads the frame row and the pixels the batch kernels just wrote -- still capturable;
-    `next(out=...)` writes it when `out` holds that key."""
+    `next(out=...)` writes it when `out` holds that key.
+
+    Both patch modes feed the patch SSIM term of train.train_step(w_ssim=) / losses.ssim_patch_loss: "dilated" with patch_num = pn, patch_size = ps
+    (7 <= ps <= 64), "patch" as ONE size x size patch (patch_num = 1, patch_size = size <= 64) -- the sampler's `pn`, `ps` attributes, layout "grid".
+    A "random" batch has no patches and the term raises for it."""
 
     def __init__(self, bank, mode, size=None, dilation_setup=None, margin=0, seed=0, dir_norm=0, bg_color=(1, 1, 1), near=None, far=None,
                  downweight_blurry_feats=0):

@@ -105,7 +105,12 @@ def shard_patches(patch_num, patch_size, world_size, rank):
     """Whole dilated patches per rank (49 patches on 8 ranks -> 7,6,6,6,6,6,6,6), so the per-patch blur / argmin of the shell needs
     no halo.  The batch is a (patch_num*patch_size)^2 grid of rays in row-major order (data/scannet_ft_dataset.py:899-949), so a
     patch is NOT a contiguous ray range.  Returns (patch ids [n_local], ray indices [n_local * patch_size^2]) with the rays
-    packed patch-major (patch, y, x) -- the layout blur.blur_update_output(..., layout="patch_major") expects."""
+    packed patch-major (patch, y, x) -- the layout blur.blur_update_output(..., layout="patch_major") expects.
+
+    The patch SSIM term (train.train_step(w_ssim=, patch_layout="patch_major"), losses.ssim_patch_loss(layout="patch_major")) takes the same packing;
+    a rank passes ssim_norm_patches (norm_patches) = patch_num * patch_num, the batch-wide count, so that its term and its colour gradient are its
+    share of the whole batch's: the terms all-reduce by sum like the rest of `loss`, and the gradients need nothing beyond the collectives that
+    exist (tests/test_ssim_loss.py, tests/test_ssim_loss_gpu.py: two halves add up to the whole batch)."""
     lo, hi = shard_bounds(patch_num * patch_num, world_size, rank)
     ids = torch.arange(lo, hi)
     S = patch_num * patch_size

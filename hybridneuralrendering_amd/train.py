@@ -404,13 +404,15 @@ def render_train(path, aggregator, xyz, emb, conf, pdir, color, raydir, campos, 
 
 def _queue_step(path, cloud, raydir, campos, camrot, bg_color, near, far, c2w_nearest, campos_nearest, intrinsic_nearest, images_nearest, gt_image,
                 zero_epsilon, w_color, w_zero_one, frame_weight, tmid, ray_drop, frame_weight_nearest, blur, w2c_nearest, device_frame_weight=None,
-                learnable_blur=None, gt_depth=None, w_depth=0.0):
-    """The launches of one step, queued back to back on the current stream: forward -> [blur module] -> loss kernels -> [depth term] ->
+                learnable_blur=None, gt_depth=None, w_depth=0.0, ssim=None):
+    """The launches of one step, queued back to back on the current stream: forward -> [blur module] -> loss kernels -> [SSIM term] -> [depth term] ->
     [blur module backward] -> backward.  Nothing is read back; shared by train_step (eager) and CapturedTrainStep (inside a hipGraph capture).
     learnable_blur (blur.LearnableBlur): the learnable-kernel form of the blur module in the same two places; its eight gradients join `ag`.
     gt_depth [R] (checked by _depth_arg): the forward also forms coarse_depth, hnr_depth_loss adds w_depth * L to the total and its gradient goes
-    into the backward (hnr_render_train_backward_depth); None: none of that."""
-    from .losses import shipped_loss_grads, depth_loss_grads
+    into the backward (hnr_render_train_backward_depth); None: none of that.  ssim (from _ssim_arg): hnr_ssim_loss on the colours the colour losses
+    see, its term added to the total and its gradient added in place to the colour gradient, so it travels back through the blur module; None: none
+    of that."""
+    from .losses import shipped_loss_grads, depth_loss_grads, ssim_patch_loss_grads
     from .blur import blur_select, blur_select_bwd
     out, S = path.forward(cloud, raydir, campos, camrot, bg_color, near, far, c2w_nearest, campos_nearest, intrinsic_nearest, images_nearest,
                           frame_weight=frame_weight_nearest, tmid=tmid, ray_drop=ray_drop, w2c_nearest=w2c_nearest, want_depth=gt_depth is not None)
@@ -426,6 +428,12 @@ def _queue_step(path, cloud, raydir, campos, camrot, bg_color, near, far, c2w_ne
         col = learnable_blur.forward(col, gt_image)
     parts, g_col, g_cc = shipped_loss_grads(col, out["conf_coefficient"], gt_image, out["ray_mask"], zero_epsilon, w_color, w_zero_one, frame_weight,
                                             conf_rows=True, device_frame_weight=device_frame_weight)
+    loss_ssim = None
+    if ssim is not None:
+        # models/base_rendering_model.py:1120-1143: 1 - SSIM on the patches of `col`; parts[0] += fw w_ssim L, g_col += its gradient (two launches)
+        s_pn, s_ps, s_layout, s_w, s_norm = ssim
+        loss_ssim, g_col = ssim_patch_loss_grads(col, gt_image, out["ray_mask"], s_pn, s_ps, s_w, layout=s_layout, norm_patches=s_norm,
+                                                 frame_weight=frame_weight, device_frame_weight=device_frame_weight, total=parts, g_color=g_col)
     g_depth = loss_depth = None
     if gt_depth is not None:
         # the depth of the UNBLURRED render (the blur module models the camera's colour response, not its geometry); parts[0] += w_depth * L
@@ -439,6 +447,8 @@ def _queue_step(path, cloud, raydir, campos, camrot, bg_color, near, far, c2w_ne
     out["loss"] = parts
     if loss_depth is not None:
         out["loss_depth"] = loss_depth
+    if loss_ssim is not None:
+        out["loss_ssim"] = loss_ssim
     if blur is not None:
         out["blurred_raycolor"], out["blur_select"] = col, sel
     elif learnable_blur is not None:
@@ -481,6 +491,22 @@ def _depth_arg(who, gt_depth, w_depth, raydir, patch_layout="grid"):
     return gt_depth.contiguous().reshape(-1), w
 
 
+def _ssim_arg(who, w_ssim, patch_num, patch_size, patch_layout, raydir, norm_patches=None):
+    """The SSIM term's arguments, checked before anything is queued -> None (w_ssim == 0: today's launches) or (patch_num, patch_size, layout,
+    w_ssim, norm_patches) for losses.ssim_patch_loss_grads."""
+    from .losses import _ssim_check
+    w = float(w_ssim)
+    if w == 0.0:
+        if norm_patches is not None:
+            raise HnrError("%s: ssim_norm_patches without w_ssim" % who)
+        return None
+    if not patch_num or not patch_size:
+        raise HnrError("%s: w_ssim=%g needs a patch-sampled batch (patch_num, patch_size, patch_layout 'grid' | 'patch_major'; frames.BatchSampler's "
+                       "'dilated' and 'patch' modes): a 'random' batch has no patches" % (who, w))
+    _ssim_check(who, int(raydir.reshape(-1, 3).shape[0]), patch_num, patch_size, patch_layout, w, norm_patches)
+    return (int(patch_num), int(patch_size), patch_layout, w, None if norm_patches is None else int(norm_patches))
+
+
 def _blur_arg(blur_kernels, patch_num, patch_size, patch_layout):
     if blur_kernels is None:
         return None
@@ -516,7 +542,7 @@ def train_step(path, aggregator, xyz, emb, conf, pdir, color, raydir, campos, ca
                intrinsic_nearest, images_nearest, gt_image, zero_epsilon=1e-3, w_color=1.0, w_zero_one=1e-4, frame_weight=None, tmid=None,
                ray_drop=None, assign_grads=True, frame_weight_nearest=None, blur_kernels=None, patch_num=None, patch_size=None, patch_layout="grid",
                w2c_nearest=None, accumulate_grads=True, device_frame_weight=None, optimizer=None, learnable_blur=None, Rw2c=None, gt_depth=None,
-               w_depth=0.0):
+               w_depth=0.0, w_ssim=0.0, ssim_norm_patches=None):
     """forward -> [blur module] -> shipped loss terms -> backward of one ray batch as groups of library launches queued back to back: no autograd
     graph, no masked copies, nothing read back to the host -- the body of the reference's optimize_parameters before its optimizer steps
     (models/neural_points_volumetric_model.py:202-214: self.forward(); loss_total.backward(), with compute_losses of
@@ -563,16 +589,28 @@ def train_step(path, aggregator, xyz, emb, conf, pdir, color, raydir, campos, ca
     of a sharded batch (the ray count n is local; patch_layout="patch_major" raises, and a caller that shards by hand would have to all-reduce n),
     Rw2c clouds (raise), the TORCH_LIBRARY ops.
 
+    w_ssim > 0 with patch_num / patch_size / patch_layout (a patch-sampled batch: frames.BatchSampler's "dilated" or "patch" mode; a "random" batch
+    raises): the patch SSIM term of models/base_rendering_model.py:1120-1143 as include/hnr.h defines it.  hnr_ssim_loss -- two launches directly
+    behind the shipped-loss kernels, on the same colours (the blurred ones when a blur module is on) -- adds frame_weight * w_ssim * (1 - SSIM) to
+    `loss`[0] and ADDS its gradient in place to the colour gradient, before the depth term and before the blur module's backward, so it travels back
+    through whichever blur module is on.  w_ssim is an absolute weight (the reference's branch takes color_loss_weights[i]).  The outputs gain
+    `loss_ssim` = {L, SSIM, frame_weight w_ssim L, hit rays}.  ssim_norm_patches: with a rank's share of a patch-sharded batch
+    (patch_layout="patch_major", parallel.shard_patches) the batch-wide patch count; the ranks' terms and gradients then add up to the whole
+    batch's, so the term all-reduces by sum like the rest.  Same arithmetic as render_train + [blur module] + losses.shipped_loss +
+    losses.ssim_patch_loss + backward().  w_ssim = 0: exactly the launches above.  Not covered: MS-SSIM, other windows / sigmas / data_range, patch
+    sizes outside 7..64 (raise), the TORCH_LIBRARY ops.
+
     Returns (outputs dict with `loss` = {total, colour MSE, zero-one mean, valid rays} on the device and `_saved` = the step's
     state for TrainPath.touched_points / the flat weight-gradient buffer, point grads dict, aggregator grads dict keyed by parameter name)."""
     _no_rotation("train_step", Rw2c, xyz)           # (Rw2c: only so that a non-identity one raises; see _no_rotation)
     learnable_blur = _learnable_arg("train_step", blur_kernels, learnable_blur)
     gt_depth, w_depth = _depth_arg("train_step", gt_depth, w_depth, raydir, patch_layout)
+    ssim = _ssim_arg("train_step", w_ssim, patch_num, patch_size, patch_layout, raydir, ssim_norm_patches)
     cloud = PointCloud(xyz, emb.detach(), conf.detach(), pdir.detach(), color.detach())
     out, S, pg, ag = _queue_step(path, cloud, raydir, campos, camrot, bg_color, near, far, c2w_nearest, campos_nearest, intrinsic_nearest, images_nearest,
                                  gt_image, zero_epsilon, w_color, w_zero_one, frame_weight, tmid, ray_drop, frame_weight_nearest,
                                  _blur_arg(blur_kernels, patch_num, patch_size, patch_layout), w2c_nearest, device_frame_weight=device_frame_weight,
-                                 learnable_blur=learnable_blur, gt_depth=gt_depth, w_depth=w_depth)
+                                 learnable_blur=learnable_blur, gt_depth=gt_depth, w_depth=w_depth, ssim=ssim)
     if learnable_blur is not None and not path.reuse_outputs:
         # LearnableBlur writes into its own static buffers; without reuse_outputs a step hands out gradient tensors of its own (240 KB)
         ag.update({n: ag[n].clone() for n in learnable_blur.names})
@@ -607,11 +645,14 @@ class CapturedTrainStep:
     addresses then: TrainPath.reuse_outputs is switched on for the path.  `step()` bumps the parameters' `_version` after the replay."""
 
     def __init__(self, path, aggregator, xyz, emb, conf, pdir, color, sample, near, far, zero_epsilon=1e-3, w_color=1.0, w_zero_one=1e-4,
-                 patch_num=None, patch_size=None, patch_layout="grid", warmup=2, optimizer=None, learnable_blur=None, Rw2c=None, w_depth=0.0):
+                 patch_num=None, patch_size=None, patch_layout="grid", warmup=2, optimizer=None, learnable_blur=None, Rw2c=None, w_depth=0.0, w_ssim=0.0,
+                 ssim_norm_patches=None):
         """sample: dict of example input tensors (see the class docstring) that fixes shapes and optional inputs.  learnable_blur: as for
         train_step (not together with a `blur_kernels` sample input); its buffers are static, so `blur_kernels_pred` follows every replay.
         A `gt_depth` [R] tensor in the sample captures the depth-supervised form of the step with the weight w_depth (train_step(gt_depth=,
-        w_depth=)); it is an input like the others: `step(gt_depth=...)` copies it, `sampler.next(out=cap.inputs)` writes it in place."""
+        w_depth=)); it is an input like the others: `step(gt_depth=...)` copies it, `sampler.next(out=cap.inputs)` writes it in place.
+        w_ssim > 0 (with patch_num / patch_size; ssim_norm_patches as for train_step): the patch SSIM term is captured with the step; it reads the
+        item's frame weight from the `frame_weight` input like the shipped-loss kernels, and `out["loss_ssim"]` follows every replay."""
         _no_rotation("CapturedTrainStep", Rw2c, xyz)
         learnable_blur = _learnable_arg("CapturedTrainStep", sample.get("blur_kernels"), learnable_blur)
         self.path, self.agg = path, aggregator
@@ -625,6 +666,7 @@ class CapturedTrainStep:
             if k not in sample:
                 raise HnrError("CapturedTrainStep: sample input %r is missing" % k)
         _depth_arg("CapturedTrainStep", sample.get("gt_depth"), w_depth, sample["raydir"], patch_layout)
+        ssim = _ssim_arg("CapturedTrainStep", w_ssim, patch_num, patch_size, patch_layout, sample["raydir"], ssim_norm_patches)
         st = {k: _lib.require_gpu(v, k).clone() for k, v in sample.items() if isinstance(v, torch.Tensor) and k != "frame_weight"}
         if "w2c_nearest" not in st:
             st["w2c_nearest"] = torch.inverse(st["c2w_nearest"].reshape(-1, 4, 4)).contiguous()
@@ -639,7 +681,7 @@ class CapturedTrainStep:
             return _queue_step(path, cloud, st["raydir"], st["campos"], st["camrot"], st["bg_color"], near, far, st["c2w_nearest"], st["campos_nearest"],
                                st["intrinsic_nearest"], st["images_nearest"], st["gt_image"], zero_epsilon, w_color, w_zero_one, None, st.get("tmid"),
                                st.get("ray_drop"), st.get("frame_weight_nearest"), blur, st["w2c_nearest"], device_frame_weight=st["frame_weight"],
-                               learnable_blur=learnable_blur, gt_depth=st.get("gt_depth"), w_depth=float(w_depth))
+                               learnable_blur=learnable_blur, gt_depth=st.get("gt_depth"), w_depth=float(w_depth), ssim=ssim)
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):

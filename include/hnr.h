@@ -27,7 +27,8 @@
  *              hnr_featnet_*, hnr_point_embed*, hnr_geo_consistency, hnr_geo_filter_select*, hnr_mvsnet_*,
  *              hnr_alpha_pack, hnr_visual_hull_select*, hnr_point_occlusion*, hnr_point_view_attrs_vis,
  *              hnr_frame_batch*, hnr_frame_item, hnr_ray_miss_rank, hnr_raft_flow*, hnr_blur_score_pair* (hnr_blur_edges and the other hnr_raft_*
- *              entries are STAGE), hnr_adam_plan, hnr_adam_step, hnr_frame_depth_rays, hnr_depth_loss, hnr_depth_metrics (and the HNR_DM_* row layout).
+ *              entries are STAGE), hnr_adam_plan, hnr_adam_step, hnr_frame_depth_rays, hnr_depth_loss, hnr_depth_metrics (and the HNR_DM_* row layout),
+ *              hnr_ssim_loss, hnr_ssim_loss_scratch_bytes.
  *   STAGE   -- everything else (hnr_chain_*, hnr_mlp3_*, hnr_merge*, hnr_mixup_stage, hnr_proj_*, hnr_h2*, hnr_linear_*, hnr_gather_*, hnr_ksum*,
  *              hnr_segment_*, hnr_absmax, hnr_div_probe, hnr_image_features_bwd_bbox, the glue kernels of the training backward -- hnr_final_color_bwd*,
  *              hnr_ksum_bwd_rows8, hnr_extras_dgrad, hnr_point_small_grads, hnr_point_rows_bwd, hnr_dleaky_add, hnr_sum_views, hnr_unique_points*,
@@ -1171,6 +1172,49 @@ int hnr_depth_loss(const float *d_depth, const float *d_gt_depth, const int8_t *
 #define HNR_DM_D1      4
 #define HNR_DM_NCOLS   5
 int hnr_depth_metrics(const float *d_depth, const float *d_gt_depth, const int8_t *d_ray_mask, int R, double *d_row, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Patch SSIM term of the training loss (csrc/ssim_loss.hip): L = 1 - SSIM over the ps x ps patches of a patch-sampled batch, value and gradient.
+ * The reference carries the term in models/base_rendering_model.py:1120-1143 -- pytorch_msssim's SSIM(win_size=7, win_sigma=1.5, data_range=1,
+ * channel=3) (:27) on the dilated patches, `loss = loss + (1 - ssim_module(patch_output_all, patch_gt_all))` -- but parks it behind a
+ * pdb.set_trace(), and that package is not part of this project.  The formulas below follow its `_ssim` as far as known; THE DEFINITION HERE IS
+ * THE CONTRACT, restated in tests/ssim_loss_ref.py.  Two launches, stream-ordered, no allocation, no host read, no atomics, sums in a fixed
+ * order (two runs give the same bits), capturable on one stream.
+ *
+ *   patches     patch_num > 0 ("grid"): n = patch_num^2 patches tiled over an S x S batch, S = patch_num * patch_size; ray row * S + col is pixel
+ *               (row % ps, col % ps) of patch (row / ps) * patch_num + col / ps.  patch_num < 0 ("patch_major", the sign convention of
+ *               hnr_blur_select): n = -patch_num whole patches packed (patch, y, x).  7 <= ps = patch_size <= 64, W = ps - 6, n ps^2 <= 2^26.
+ *   masking     m = d_ray_mask > 0;  X = m ? d_color : 0,  Y = m ? d_gt : 0  per ray and channel (:1124-1128).
+ *   window      g = win[0..6], host memory, read during the call: losses.ssim_window() -- exp(-(i - 3)^2 / (2 * 1.5^2)) normalised to sum 1,
+ *               formed in fp32 with the torch ops of the package's _fspecial_gauss_1d.  Each value must lie in [0, 1].
+ *   filtering   "valid", separable, per patch and channel, every fp32 operation rounded on its own (no FMA), taps added in ascending i
+ *               starting from 0.f:   T_q(y, x) = sum_{i=0..6} g[i] * q(y, x + i)  for q = X, Y, X*X, Y*Y, X*Y (products first),  x < W;
+ *               then                 M_q(y, x) = sum_{i=0..6} g[i] * T_q(y + i, x),  y < W.
+ *   window      mx = M_X, my = M_Y, exx = M_XX, eyy = M_YY, exy = M_XY;  mxx = mx*mx, myy = my*my, mxy = mx*my;
+ *               sx = exx - mxx, sy = eyy - myy, sxy = exy - mxy;  C1 = 1e-4f, C2 = 9e-4f;
+ *               A1 = 2*mxy + C1, B1 = (mxx + myy) + C1, A2 = 2*sxy + C2, B2 = (sx + sy) + C2;  l = A1 / B1, cs = A2 / B2,  s = l * cs
+ *               (divisions correctly rounded).  No clamping, no nonnegative_ssim.
+ *   gradient    a = ds/dmx = ((2*(my - l*mx)) / B1) * cs + l * ((2*(mx*cs - my)) / B2),  b = ds/dexx = -(s / B2),  c = ds/dexy = (2*l) / B2,
+ *               each 0 outside the W x W windows;  U_k(y, x) = sum_{i=0..min(6,y)} g[i] * k(y - i, x),  G_k(y, x) = sum_{i=0..min(6,x)} g[i] *
+ *               U_k(y, x - i)  for k = a, b, c;  d(sum s)/dX(y, x) = (G_a + (2*X) * G_b) + Y * G_c.
+ *   value       N = norm_patches, or n when norm_patches = 0.  sum s runs in fp64 over the fp32 s: per lane over its windows (channel, y, x
+ *               ascending), xor butterfly (32 .. 1) over each wave, waves in order, then patches (lane-strided over 64 lanes, butterfly).
+ *               SSIM = (float)(sum s / (N 3 W^2)),  L = (float)((n 3 W^2 - sum s) / (N 3 W^2)): 1 - SSIM for N = n, and with N the batch-wide
+ *               count the L of the ranks of a patch-sharded batch add up to the whole batch's.  hits = rays with m.  hits = 0: L = 0.
+ *   outputs     d_out4 = {L, SSIM, (fw * w_ssim) * L, hits};  d_total[0] += (fw * w_ssim) * L, one fp32 add, skipped (bits untouched) when
+ *               hits = 0 (:1117,1144-1145); d_total is d_out4 of the hnr_shipped_loss* kernels queued before, or NULL.  fw = d_frame_weight[0]
+ *               (device, one float) when given, else frame_weight: the reference adds the term inside the colour item, before the frame-weight
+ *               scaling (:1143,1198,1205).  w_ssim is an absolute weight.
+ *               d_g_color [n ps^2, 3]:  v = m ? -((fw * w_ssim) / (float)(N 3 W^2)) * d(sum s)/dX : 0  -- written when accumulate = 0, ADDED in
+ *               place (g = g + v, every ray, plain stores: each ray belongs to one patch) when accumulate = 1, e.g. onto d_g_color of
+ *               hnr_shipped_loss_rows*; NULL (accumulate = 0): value only.
+ *   errors      HNR_ERR_BADARG before anything is queued: patch_size outside 7..64, patch_num = 0, norm_patches < 0 or 0 < norm_patches < n,
+ *               w_ssim or frame_weight negative or not finite, a window value outside [0, 1], NULL pointers.
+ *   d_scratch   hnr_ssim_loss_scratch_bytes(n) bytes (n = patches of the call), 8-byte aligned. */
+int64_t hnr_ssim_loss_scratch_bytes(int n_patches);
+int hnr_ssim_loss(const float *d_color, const float *d_gt, const int8_t *d_ray_mask, int patch_num, int patch_size, int norm_patches,
+                  const float *win, float w_ssim, float frame_weight, const float *d_frame_weight, float *d_total, float *d_out4,
+                  float *d_g_color, int accumulate, void *d_scratch, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Growth schedule, the per-step part: the step's ray-miss loss and the table of the worst frames (prob_mode 0), ONE launch of one workgroup.
