@@ -319,6 +319,7 @@ SIGNATURES = {
     "hnr_segment_sum_rows_csr": (_I, [_P, _I, _P, _P, _P, _I, _I, _P, ctypes.c_int64, _P, _I, _I, _P, ctypes.c_int64, _P, _P]),
     # the glue kernels of the training backward, each alone (tests/test_backward_glue_gpu.py)
     "hnr_final_color_bwd_max": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P]),
+    "hnr_merge_bwd_max": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _F, _P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _P, _P]),   # (tests/test_ray_bwd_gpu.py)
     "hnr_ksum_bwd_rows8": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _F, _I, _P, _P, _P, _P, _P, _P]),
     "hnr_extras_dgrad": (_I, [_P, _P, _P, ctypes.c_int64, _P, _P]),
     "hnr_point_small_grads": (_I, [_P, _P, _I, _P, _P, _P, _P, _P]),

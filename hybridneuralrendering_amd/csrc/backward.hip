@@ -84,8 +84,7 @@ __global__ __launch_bounds__(256) void composite_bwd_serial_kernel(CompositeBwdA
         }
         if (dist < 1e-8f || (a.unit_mode && dist > 2.f * a.vsize_z)) dist = a.vsize_z;
         const bool valid = s < ns && a.pidx[((size_t)r * a.SR + s) * a.K] >= 0;
-        const float4 d = reinterpret_cast<const float4 *>(a.decoded)[(size_t)r * a.SR + s];
-        const float sigma = valid ? d.x : 0.f;
+        const float sigma = valid ? a.decoded[((size_t)r * a.SR + s) * 4] : 0.f;
         const float rd = valid ? dist : 0.f;
         const float o = 1.f - expf(-sigma * rd);
         float zs = 0.f;
@@ -110,7 +109,8 @@ __global__ __launch_bounds__(256) void composite_bwd_serial_kernel(CompositeBwdA
     for (int s = a.SR - 1; s >= 0; --s) {
         const float4 t = dd[s];
         const float o = t.x, rd = t.y, Ts = t.z;
-        const float4 d = reinterpret_cast<const float4 *>(a.decoded)[(size_t)r * a.SR + s];
+        // slots past nsamp are not read (composite_kernel's rule): they count as zeros, which is what the padded query leaves there
+        const float4 d = s < ns ? reinterpret_cast<const float4 *>(a.decoded)[(size_t)r * a.SR + s] : make_float4(0.f, 0.f, 0.f, 0.f);
         float gs = d.y * g0 + d.z * g1 + d.w * g2;
         if (DEPTH) gs += kD * (t.w - D);
         const float q = 1.f - o + 1e-10f;
@@ -126,7 +126,9 @@ __global__ __launch_bounds__(256) void composite_bwd_serial_kernel(CompositeBwdA
 // One WAVE per ray, lane = shading sample (SR <= 64): every lane loads its own sample's operands up front, the two serial recurrences (front
 // to back: running depth maximum and transmittance; back to front: the suffix sum S) then run over wave-uniform values fetched with
 // v_readlane, each lane keeping the step that is its own.  The same operations in the same order as one thread per ray -- which took 56 us
-// for 3 136 rays: 2 x 24 dependent steps, each waiting for its own loads (thirteen workgroups on the whole chip).
+// for 3 136 rays: 2 x 24 dependent steps, each waiting for its own loads (thirteen workgroups on the whole chip).  tests/test_ray_bwd_gpu.py
+// holds both claims bit for bit: the same rays through this form (SR = 24) and the serial one (SR = 65), and d rgb under g = (1, 0, 0)
+// against composite_kernel's blend weight.
 template <bool DEPTH>
 __global__ __launch_bounds__(256) void composite_bwd_kernel(CompositeBwdArgs a)
 {
@@ -150,7 +152,7 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(CompositeBwdArgs a)
         const float s0 = __fsub_rn(q0, a.campos[0]), s1 = __fsub_rn(q1, a.campos[1]), s2 = __fsub_rn(q2, a.campos[2]);
         z_l = __fadd_rn(__fadd_rn(__fmul_rn(a.camrot[2], s0), __fmul_rn(a.camrot[5], s1)), __fmul_rn(a.camrot[8], s2));
         valid_l = lane < ns && a.pidx[((size_t)r * a.SR + lane) * a.K] >= 0;
-        d_l = reinterpret_cast<const float4 *>(a.decoded)[(size_t)r * a.SR + lane];
+        if (lane < ns) d_l = reinterpret_cast<const float4 *>(a.decoded)[(size_t)r * a.SR + lane];      // not past nsamp (composite_kernel's rule): zeros there
     }
     const float sig_l = valid_l ? d_l.x : 0.f;
     auto bc = [&](float v, int s) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), s)); };
@@ -1246,6 +1248,17 @@ extern "C" int hnr_final_color_bwd_max(const float *d_Y, int ldy, const float *d
     if (!d_gY_max || cap_samples < 0 || mis16(d_g_decoded)) { set_error("hnr_final_color_bwd_max: bad argument (NULL d_gY_max: hnr_final_color_bwd is the form without it)"); return HNR_ERR_BADARG; }
     return hnr::final_color_bwd_max(d_Y, ldy, d_CF, ldcf, d_w_fin, d_b_fin, d_vs_item, d_counts, cap_samples, d_g_decoded, d_gY, ldgy, d_gCF, ldgcf, d_g_sigma, d_g_w_fin,
                                     d_g_b_fin, d_gY_max, stream);
+}
+
+extern "C" int hnr_merge_bwd_max(const float *d_X6, int ld6, const float *d_Hm, int ldh, const float *d_w_last, const float *d_b_last,
+                                 const float *d_vmask, const float *d_frame_w, const int64_t *d_counts, int V, int cap_samples, float slope,
+                                 const uint8_t *d_ray_drop, const int32_t *d_vs_item, int SR, const float *d_gX7, int ldg7,
+                                 float *d_gF, int ldgf, float *d_gZ3, int ldgz, float *d_gCF, int ldgcf, float *d_g_w_last, float *d_g_b_last,
+                                 uint32_t *d_gZ3_max, void *stream)
+{
+    if (!d_gZ3_max || cap_samples < 0) { set_error("hnr_merge_bwd_max: bad argument (NULL d_gZ3_max: hnr_merge_bwd is the form without it)"); return HNR_ERR_BADARG; }
+    return hnr::merge_bwd_max(d_X6, ld6, d_Hm, ldh, d_w_last, d_b_last, d_vmask, d_frame_w, d_counts, V, cap_samples, slope, d_ray_drop, d_vs_item, SR, d_gX7, ldg7, d_gF, ldgf,
+                              d_gZ3, ldgz, d_gCF, ldgcf, d_g_w_last, d_g_b_last, d_gZ3_max, stream);
 }
 
 extern "C" int hnr_point_small_grads(const float *d_P8, const int32_t *d_ulist, int U_cap, const int64_t *d_u, float *d_g_conf, float *d_g_dir, float *d_g_color,

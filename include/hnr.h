@@ -496,7 +496,10 @@ int hnr_ray_march(const float *d_ray_dist, const uint8_t *d_ray_valid, const flo
  */
 
 /* ray_march + alpha blend (models/rendering/diff_ray_marching.py:508-557) and fill_invalid (:87-126):
- * d_g_raycolor [R,3] -> d_g_decoded [R,SR,4] = (d sigma, d rgb), zeros for invalid samples / rays. */
+ * d_g_raycolor [R,3] -> d_g_decoded [R,SR,4] = (d sigma, d rgb), zeros for invalid samples / rays.
+ * With d_ray_nsamp given, the slots s >= nsamp[r] of d_decoded, d_sample_loc_w and d_sample_pidx are not read (hnr_composite's rule): they count as
+ * decoded = 0, position 0, no neighbour, and the result is that of the padded call, bit for bit.  Holes inside nsamp (pidx < 0) ARE read:
+ * their d_decoded must be finite, as the forward leaves it. */
 int hnr_composite_bwd(const float *d_decoded, const float *d_sample_loc_w, const int32_t *d_sample_pidx, const int8_t *d_ray_mask,
                       const int32_t *d_ray_nsamp, const float *d_campos, const float *d_camrot, const float *d_bg_color,
                       int R, int SR, int K, float vsize_z, int raydist_mode_unit, const float *d_g_raycolor,
@@ -592,6 +595,13 @@ int hnr_final_color_bwd_max(const float *d_Y, int ldy, const float *d_CF, int ld
                             const int32_t *d_vs_item, const int64_t *d_counts, int cap_samples, const float *d_g_decoded,
                             float *d_gY, int ldgy, float *d_gCF, int ldgcf, float *d_g_sigma, float *d_g_w_fin, float *d_g_b_fin,
                             uint32_t *d_gY_max, void *stream);
+/* hnr_merge_bwd, and *d_gZ3_max = max(*d_gZ3_max, max |d_gZ3[v * cap + s, 0:64]|, s < n_valid) as a bit pattern (exponent-exact, as above): the scale of
+ * the fp16 GEMM that follows in the training step.  The other outputs are the bits of hnr_merge_bwd. */
+int hnr_merge_bwd_max(const float *d_X6, int ld6, const float *d_Hm, int ldh, const float *d_w_last, const float *d_b_last,
+                      const float *d_vmask, const float *d_frame_w, const int64_t *d_counts, int V, int cap_samples, float slope,
+                      const uint8_t *d_ray_drop, const int32_t *d_vs_item, int SR, const float *d_gX7, int ldg7,
+                      float *d_gF, int ldgf, float *d_gZ3, int ldgz, float *d_gCF, int ldgcf, float *d_g_w_last, float *d_g_b_last,
+                      uint32_t *d_gZ3_max, void *stream);
 /* Alpha branch + K-weighted sums transposed, 8 row slots per sample (row = 8 s + k, s < d_counts[HNR_CNT_SAMPLES_VALID] <= cap_samples).  d_aux: per 32-row group
  * 1280 bytes {int32 pid[32]; float w[32]; 1024 bytes unused here}.  Slot with pid >= 0, h = d_H4[row, 0:256]:  y = h . alpha_w + alpha_b - 1;
  * da = w g_sigma[s] sigmoid(y);  d_gZ4[row] = (w gX5[s] + da alpha_w) * (h > 0 ? 1 : slope);  d_g_wagg[row] = softplus(y) g_sigma[s] + h . gX5[s];

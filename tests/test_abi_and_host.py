@@ -398,6 +398,11 @@ def test_c_abi_rejects_bad_arguments_without_touching_the_gpu():
     refused("hnr_final_color_bwd", L.hnr_final_color_bwd_max(*(fc[:1] + [44] + fc[2:] + [one, null])))    # ldy < 45
     refused("hnr_final_color_bwd", L.hnr_final_color_bwd_max(*(fc[:9] + [odd] + fc[10:] + [one, null])))  # float4 reads of g_decoded
     assert L.hnr_final_color_bwd_max(*(fc[:8] + [0] + fc[9:] + [one, null])) == 0
+    mb = [one, 48, one, 64, one, one, one, null, one, 4, 10, sl, null, one, 24, one, 92, one, 48, one, 64, one, 128, one, one]
+    refused("hnr_merge_bwd_max", L.hnr_merge_bwd_max(*(mb + [null, null])))                               # the word is what this entry is for
+    refused("hnr_merge_bwd", L.hnr_merge_bwd_max(*(mb[:9] + [9] + mb[10:] + [one, null])))                # V > 8
+    refused("hnr_merge_bwd", L.hnr_merge_bwd_max(*(mb[:16] + [89] + mb[17:] + [one, null])))              # ldg7 < 90
+    assert L.hnr_merge_bwd_max(*(mb[:10] + [0] + mb[11:] + [one, null])) == 0
     ks = [one16, one, one16, one, one, one16, 256, one, sl, 10, one16, one, one, one, one, null]
     refused("hnr_ksum_bwd_rows8", L.hnr_ksum_bwd_rows8(*(ks[:1] + [null] + ks[2:])))                      # no aux
     refused("hnr_ksum_bwd_rows8", L.hnr_ksum_bwd_rows8(*(ks[:6] + [255] + ks[7:])))                       # ldg5
