@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("HNR_LIB_PATH") or os.path.join(_HERE, "libhnr_hip.so"
 NCOUNTS = 9
 FEATNET_PACKED_ELEMS = 41368           # HNR_FEATNET_PACKED_ELEMS
 PREMLP_PACKED_ELEMS = 3104             # HNR_PREMLP_PACKED_ELEMS
+PATH_SCRATCH_BYTES = 512               # HNR_PATH_SCRATCH_BYTES
 MVSNET_FEATURE_PACKED_ELEMS = 40248    # HNR_MVSNET_FEATURE_PACKED_ELEMS
 MVSNET_REG_PACKED_ELEMS = 298297       # HNR_MVSNET_REG_PACKED_ELEMS
 CNT = dict(RAYS_HIT=0, SAMPLES=1, RAYS_VALID=2, NEIGHBOURS=3, CELLS_VISITED=4, CANDIDATES=5, SAMPLES_VALID=6, SAMPLES_SMALL=7, SAMPLES_TINY=8)
@@ -282,6 +283,11 @@ SIGNATURES = {
                              ctypes.POINTER(FrameBatchOut), _P, ctypes.c_int64, _P]),
     "hnr_frame_item": (_I, [ctypes.POINTER(FrameBankC), ctypes.POINTER(FrameBankC), _P, _I, _I, _P, ctypes.c_int64, _I, _I, ctypes.POINTER(_F), _I,
                             ctypes.POINTER(FrameBatchOut), _P, ctypes.c_int64, _P]),
+    # camera paths: reference views of free poses, the item of a path frame, the store into a clip (csrc/path.hip)
+    "hnr_pose_views": (_I, [ctypes.POINTER(FrameBankC), _P, _I, _P, _I, _P, _I, _I, _P, _P]),
+    "hnr_path_item": (_I, [ctypes.POINTER(FrameBankC), _P, _I, _P, _I, _I, _I, _P, _I, _I, _I, ctypes.POINTER(_F), _I, ctypes.POINTER(FrameBatchOut), _P,
+                           ctypes.c_int64, _P]),
+    "hnr_frame_store": (_I, [_P, _P, _P, ctypes.c_int64, _I, _I, _P, _P, _P, _P]),
     # depth supervision from resident depth frames: per-ray gt_depth, the loss term, the depth metrics row (csrc/depth_sup.hip)
     "hnr_frame_depth_rays": (_I, [ctypes.POINTER(DepthBankC), _P, _P, _P, _I, _P, _P]),
     "hnr_depth_loss": (_I, [_P, _P, _P, _I, _F, _P, _P, _P, _P, _P]),

@@ -9,20 +9,19 @@ and reassembled on rank 0 with one gather (parallel.render_sharded).  Chunking i
 the same pixels at jitter 0 (tests/test_render_gpu.py::test_whole_frame_equals_the_reference_chunk_loop, against a frame the imported
 reference rendered chunk by chunk).
 """
+import os
+
 import torch
 import torch.distributed as dist
 
+from . import _lib
 from ._lib import HnrError
 from . import parallel
 
 
-def render_image(renderer, cloud, frame, chunk_rays=0, sharded=None, group=None, depth=False):
-    """frame: dict with the dataset item of the reference (data/scannet_ft_dataset.py:855-976), batch dim optional:
-    raydir [R,3], pixel_idx [R,2] (x, y), campos [3], camrotc2w [3,3], bg_color [3], near, far, h, w, c2w_nearest [V,4,4],
-    campos_nearest [V,3], intrinsic_nearest [3,3], images_nearest [V,H,W,3] (+ optional frame_weight_nearest [V]).
-    Returns dict(image [h,w,3] (zero where no ray was cast: run/test_ft.py:191 scatters into np.zeros), ray_mask [R] i8, coarse_raycolor [R,3]) --
-    on rank 0 when sharded, None on the other ranks.  depth=True adds depth [h,w] (zero where no ray was cast) and coarse_depth [R], the expected
-    camera-space depth of every ray (render_rays(want_depth=True); 0 where ray_mask = 0); sharded, it travels as a fifth row column."""
+def _frame_rows(renderer, cloud, frame, chunk_rays, sharded, group, depth):
+    """The ray path of render_image: the frame's rays through render_rays (whole, chunked or sharded), the status words checked once per frame ->
+    (rows [R, 4 or 5] = colour, mask, depth; None on the ranks that do not assemble), pixel_idx [R,2], h, w."""
     sq = lambda t, nd: t.reshape(t.shape[-nd:]) if isinstance(t, torch.Tensor) else t
     raydir = sq(frame["raydir"], 2)
     pix = sq(frame["pixel_idx"], 2)
@@ -66,6 +65,17 @@ def render_image(renderer, cloud, frame, chunk_rays=0, sharded=None, group=None,
     # the device status words of this rank's launches, read once per frame (after everything is queued): an overflow of a workspace capacity
     # must not pass silently
     renderer.check_status([dict(status=o.get("status")) for o in statuses])
+    return rows, pix, h, w
+
+
+def render_image(renderer, cloud, frame, chunk_rays=0, sharded=None, group=None, depth=False):
+    """frame: dict with the dataset item of the reference (data/scannet_ft_dataset.py:855-976), batch dim optional:
+    raydir [R,3], pixel_idx [R,2] (x, y), campos [3], camrotc2w [3,3], bg_color [3], near, far, h, w, c2w_nearest [V,4,4],
+    campos_nearest [V,3], intrinsic_nearest [3,3], images_nearest [V,H,W,3] (+ optional frame_weight_nearest [V]).
+    Returns dict(image [h,w,3] (zero where no ray was cast: run/test_ft.py:191 scatters into np.zeros), ray_mask [R] i8, coarse_raycolor [R,3]) --
+    on rank 0 when sharded, None on the other ranks.  depth=True adds depth [h,w] (zero where no ray was cast) and coarse_depth [R], the expected
+    camera-space depth of every ray (render_rays(want_depth=True); 0 where ray_mask = 0); sharded, it travels as a fifth row column."""
+    rows, pix, h, w = _frame_rows(renderer, cloud, frame, chunk_rays, sharded, group, depth)
     if rows is None:
         return None
     col, mask = rows[:, :3].contiguous(), rows[:, 3].to(torch.int8)
@@ -107,3 +117,75 @@ def evaluate_frames(renderer, cloud, frames, evaluator=None, win=11, data_range=
                                          depth=bool(depth))
         evaluator.add(out, frame)
     return evaluator
+
+
+class Clip:
+    """The frames of a rendered camera path, on the device: frames [P,h,w,3] uint8 (quantised as hnr_frame_metrics quantises: trunc(clip(x, 0, 1) *
+    255)), ray_hits [P] int64 (rays of every frame that hit the cloud), and, when asked for, depth [P,h,w] float32 and images [P,h,w,3] float32."""
+
+    def __init__(self, frames, ray_hits, depth=None, images=None):
+        self.frames, self.ray_hits, self.depth, self.images = frames, ray_hits, depth, images
+
+    def __len__(self):
+        return int(self.frames.shape[0])
+
+    def to_numpy(self):
+        """The one host read: dict(frames, ray_hits[, depth][, images]) of NumPy arrays."""
+        out = dict(frames=self.frames.cpu().numpy(), ray_hits=self.ray_hits.cpu().numpy())
+        if self.depth is not None:
+            out["depth"] = self.depth.cpu().numpy()
+        if self.images is not None:
+            out["images"] = self.images.cpu().numpy()
+        return out
+
+    def write(self, out_dir, name="coarse_raycolor", gif=False, fps=10):
+        """step-%04d-<name>.png per frame (the file names of the reference's visualizer), and with gif=True <name>.gif of all frames; returns the
+        list of files written."""
+        from PIL import Image
+        os.makedirs(out_dir, exist_ok=True)
+        frames = self.frames.cpu().numpy()
+        files = []
+        for i, f in enumerate(frames):
+            files.append(os.path.join(out_dir, "step-%04d-%s.png" % (i, name)))
+            Image.fromarray(f).save(files[-1])
+        if gif:
+            files.append(os.path.join(out_dir, "%s.gif" % name))
+            ims = [Image.fromarray(f) for f in frames]
+            ims[0].save(files[-1], save_all=True, append_images=ims[1:], duration=max(int(round(1000.0 / fps)), 1), loop=0)
+        return files
+
+
+def render_path(renderer, cloud, sampler, frames=None, depth=False, chunk_rays=0, keep_float=False):
+    """run/render_vid.py's loop, on the device: every frame of a camera path (frames.PathSampler) rendered through render_image's ray path and stored
+    into a clip by hnr_frame_store -- one launch behind the composite instead of torch.zeros + index-put + a quantisation per frame, no host
+    read besides the status words render_image also reads.  frames=None: the whole path, P frames in order from the sampler's device counter
+    (`sampler.next()`); frames = a list of frame numbers: those (`sampler.item(i)`).  depth=True adds the expected-depth maps, keep_float=True the
+    float32 frames.  Returns a Clip.  A cloud with per-part rotations (edit.compose: Rw2c) goes through as it does in render_image.
+    Not covered: sharded rendering (world size > 1)."""
+    from .frames import PathSampler
+    if not isinstance(sampler, PathSampler):
+        raise HnrError("render_path: sampler must be a frames.PathSampler")
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        raise HnrError("render_path: sharded rendering (world size > 1) is not covered; render the path on one rank")
+    if frames is not None:
+        frames = [int(i) for i in frames]
+        if not frames or min(frames) < 0 or max(frames) >= sampler.P:
+            raise HnrError("render_path: frames must be a non-empty list of frame numbers 0 .. %d" % (sampler.P - 1))
+    n = sampler.P if frames is None else len(frames)
+    dev, h, w = sampler.bank.device, sampler.bank.H, sampler.bank.W
+    L = _lib.lib()
+    clip8 = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+    clipd = torch.empty((n, h, w), dtype=torch.float32, device=dev) if depth else None
+    clipf = torch.empty((n, h, w, 3), dtype=torch.float32, device=dev) if keep_float else None
+    hits = torch.zeros((n,), dtype=torch.int64, device=dev)
+    for k in range(n):
+        item = sampler.next() if frames is None else sampler.item(frames[k])
+        rows, pix, _h, _w = _frame_rows(renderer, cloud, item, chunk_rays, False, None, bool(depth))
+        col = rows[:, :3].contiguous()
+        d = rows[:, 4].contiguous() if depth else None
+        hits[k] = rows[:, 3].sum().to(torch.int64)
+        with torch.cuda.device(dev):
+            _lib.check(L.hnr_frame_store(_lib.ptr(col), _lib.ptr(pix.contiguous()), _lib.ptr(d), int(col.shape[0]), h, w, _lib.ptr(clip8[k]),
+                                         _lib.ptr(clipf[k]) if keep_float else None, _lib.ptr(clipd[k]) if depth else None, _lib.stream()),
+                       "hnr_frame_store")
+    return Clip(clip8, hits, depth=clipd, images=clipf)

@@ -406,3 +406,195 @@ class BatchSampler:
             if dep is not None:
                 self._depth_rays(dep, R)                      # (the row travels through the item's own frame_row word on the device)
         return self._finish(t)
+
+
+class PathSampler:
+    """The dataset item of a camera that is no row of a bank: frame i of a pose table, with the reference views chosen on the device (csrc/path.hip;
+    the definitions are in include/hnr.h and tests/path_ref.py).
+
+    poses [P,4,4] c2w (paths.spherical_path / paths.keyframe_path, or any array; a torch tensor must already be on the bank's device) and
+    intrinsic [3,3] or [P,3,3] live on the device and are READ THERE by every item: `set_poses(t)` copies new poses in place, a viewer or a
+    device-side path generator may write `self.poses` directly, and the next item follows.  reference_bank: the FrameBank the V reference views come
+    from (H, W are its frame size); they are picked per item by get_nearest_cam_id's rule -- of the n1 = min(num_times V, T // 10) train cameras
+    looking most nearly the same way, the V closest -- with ties decided (hnr_pose_views).  margin, dir_norm, bg_color (a triple), near, far and
+    downweight_blurry_feats as BatchSampler.
+
+    `next(out=None)` writes the item of frame step % P and advances the device counter `step`: the same static tensors on every call, no
+    allocation after the first, no host read, at most three launches, capturable on one stream; `out` as BatchSampler.next.  (Its tensors' `_version`
+    is bumped per call, so the renderer's feature-map cache follows the new reference views; after a graph REPLAY the caller bumps them.)  `item(i)` is the explicit
+    form (fresh tensors).  `views(poses=None)` is the [Q,V] table alone.  The dict has the keys driver.render_image reads -- raydir, pixel_idx,
+    campos, camrotc2w = camrot, c2w, intrinsic, bg_color, near, far, h, w, c2w_nearest, w2c_nearest, campos_nearest, intrinsic_nearest,
+    images_nearest, frame_weight_nearest, vid_angle_nearest -- and frame_row [1] = i.  A path frame has no gt_image, frame_weight or patch_table."""
+
+    OUTPUTS = ("raydir", "pixel_idx", "campos", "camrot", "c2w", "intrinsic", "bg_color", "frame_row", "c2w_nearest", "w2c_nearest", "campos_nearest",
+               "intrinsic_nearest", "images_nearest", "frame_weight_nearest", "vid_angle_nearest")
+
+    def __init__(self, poses, intrinsic, reference_bank, V, margin=0, dir_norm=0, bg_color=(1, 1, 1), near=None, far=None, num_times=3,
+                 downweight_blurry_feats=False):
+        bank = reference_bank
+        if not isinstance(bank, FrameBank):
+            raise HnrError("PathSampler: reference_bank must be a FrameBank")
+        if near is None or far is None:
+            raise HnrError("PathSampler: near and far (the item's depth range) are required")
+        self.bank, self.V, self.margin = bank, int(V), int(margin)
+        self.near, self.far = float(near), float(far)
+        if self.V < 1 or self.V > 64:
+            raise HnrError("PathSampler: 1 <= V <= 64, got %d" % self.V)
+        if bank.F > 8192:
+            raise HnrError("PathSampler: at most 8192 reference cameras, the bank has %d" % bank.F)
+        self.n1 = min(int(num_times) * self.V, bank.F // 10)
+        if self.n1 < self.V:
+            raise HnrError("PathSampler: n1 = min(num_times V, T // 10) = %d candidates of %d cameras cannot give %d views" % (self.n1, bank.F, self.V))
+        if isinstance(bg_color, str):
+            raise HnrError("PathSampler: bg_color must be a triple (%r is not supported for path frames)" % (bg_color,))
+        self.bg = tuple(float(c) for c in bg_color)
+        if len(self.bg) != 3:
+            raise HnrError("PathSampler: bg_color must have three components")
+        H, W, m = bank.H, bank.W, self.margin
+        if m < 0 or W - 2 * m <= 0 or H - 2 * m <= 0:
+            raise HnrError("PathSampler: margin %d leaves no pixel of a %dx%d frame (an empty range)" % (m, H, W))
+        self.R = (W - 2 * m) * (H - 2 * m)
+        self.dir_norm, self.downweight = int(bool(dir_norm)), int(bool(downweight_blurry_feats))
+        poses = self._poses(poses, None, "PathSampler")
+        self.P = int(poses.shape[0])
+        if isinstance(intrinsic, torch.Tensor):
+            if not intrinsic.is_cuda or intrinsic.device != bank.device:
+                raise HnrError("PathSampler: an intrinsic tensor must be on the bank's device %s, got %s" % (bank.device, intrinsic.device))
+            K = intrinsic.to(torch.float32)
+        else:
+            K = torch.from_numpy(np.ascontiguousarray(intrinsic, dtype=np.float32))
+        if tuple(K.shape) not in ((3, 3), (self.P, 3, 3)):
+            raise HnrError("PathSampler: intrinsic must be [3,3] or [%d,3,3], got %s" % (self.P, tuple(K.shape)))
+        self.L = _lib.lib()
+        dev = bank.device
+        self.poses, self.intrinsic = poses.to(dev).contiguous().clone(), K.to(dev).contiguous().clone()      # the sampler's own tables
+        self._K_per_pose = 1 if K.dim() == 3 else 0
+        self._scratch = torch.zeros((_lib.PATH_SCRATCH_BYTES,), dtype=torch.uint8, device=dev)
+        self.step = torch.zeros((1,), dtype=torch.int64, device=dev)          # the frame counter (read and advanced on the device)
+        self._static, self._bound = None, {}
+
+    # ------------------------------------------------------------------------------------------------ plumbing
+    def _poses(self, poses, P, what):
+        """[P,4,4] float32: an array is validated (finite) here, on the host; a tensor must be on the device already and is taken as it is"""
+        if isinstance(poses, torch.Tensor):
+            if not poses.is_cuda or poses.device != self.bank.device:
+                raise HnrError("%s: a pose tensor must be on the bank's device %s, got %s" % (what, self.bank.device, poses.device))
+            t = poses.to(torch.float32)
+        else:
+            a = np.ascontiguousarray(poses, dtype=np.float32)
+            if a.ndim == 3 and not np.isfinite(a).all():
+                raise HnrError("%s: a pose is not finite" % what)
+            t = torch.from_numpy(a)
+        if t.dim() != 3 or tuple(t.shape[1:]) != (4, 4) or t.shape[0] < 1 or (P is not None and t.shape[0] != P):
+            raise HnrError("%s: poses must be [%s,4,4], got %s" % (what, "P" if P is None else P, tuple(t.shape)))
+        return t
+
+    def _shapes(self):
+        b, V, R = self.bank, self.V, self.R
+        f, i = torch.float32, torch.int32
+        return dict(raydir=((R, 3), f), pixel_idx=((R, 2), f), campos=((3,), f), camrot=((3, 3), f), c2w=((4, 4), f), intrinsic=((3, 3), f), bg_color=((3,), f),
+                    frame_row=((1,), i), c2w_nearest=((V, 4, 4), f), w2c_nearest=((V, 4, 4), f), campos_nearest=((V, 3), f), intrinsic_nearest=((3, 3), f),
+                    images_nearest=((V, b.H, b.W, 3), f), frame_weight_nearest=((V,), f), vid_angle_nearest=((V,), f))
+
+    def _alloc(self):
+        return {k: torch.empty(s, dtype=d, device=self.bank.device) for k, (s, d) in self._shapes().items()}
+
+    def _finish(self, t):
+        d = dict(t)
+        d["camrotc2w"] = d["camrot"]
+        d.update(near=self.near, far=self.far, h=self.bank.H, w=self.bank.W)
+        return d
+
+    def _bind(self, tensors, what):
+        sh = self._shapes()
+        o = _lib.FrameBatchOut()
+        for k, t in tensors.items():
+            if k in ("gt_image", "frame_weight", "patch_table", "gt_depth"):
+                raise HnrError("%s: a path frame has no %s (there is no ground truth for a free camera)" % (what, k))
+            if k not in sh:
+                continue
+            shape, dt = sh[k]
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != self.bank.device or t.dtype != dt or not t.is_contiguous() or \
+                    t.numel() != int(np.prod(shape)):
+                raise HnrError("%s: output %r must be a contiguous %s tensor of %s on %s, got %s %s" % (
+                    what, k, dt, "x".join(str(s) for s in shape), self.bank.device, getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
+            if k == "images_nearest" and t.data_ptr() % 16:
+                raise HnrError("%s: images_nearest must be 16-byte aligned" % what)
+            setattr(o, "d_" + k, t.data_ptr())
+        return o
+
+    def _launch(self, o, step, i, written):
+        """... and the `_version` rule (optim.py): the kernels write `written` behind torch's back -- the static tensors of next() keep their
+        addresses from frame to frame -- and the renderer caches the reference views' feature map per (address, _version)."""
+        for t in written:
+            torch.autograd.graph.increment_version(t)
+        with torch.cuda.device(self.bank.device):
+            _lib.check(self.L.hnr_path_item(ctypes.byref(self.bank._c), _lib.ptr(self.poses), self.P, _lib.ptr(self.intrinsic), self._K_per_pose, self.V, self.n1,
+                                            step, i, self.margin, self.dir_norm, (ctypes.c_float * 3)(*self.bg), self.downweight, ctypes.byref(o),
+                                            _lib.ptr(self._scratch), int(self._scratch.numel()), _lib.stream()), "hnr_path_item")
+
+    # ------------------------------------------------------------------------------------------------ the interface
+    def set_poses(self, poses):
+        """New poses [P,4,4] (the same P) copied into the device table in place: captured graphs and later items read them."""
+        self.poses.copy_(self._poses(poses, self.P, "PathSampler.set_poses"))
+        return self
+
+    def set_step(self, step):
+        self.step.fill_(int(step))
+        return self
+
+    def views(self, poses=None, exclude_rows=None):
+        """hnr_pose_views: the [Q,V] int32 rows of the reference bank for `poses` [Q,4,4] (default: the sampler's own table, with its intrinsic;
+        other poses use the shared intrinsic, so the sampler's must be [3,3] or Q must be P).  exclude_rows [Q] int32 (-1 = none): the `is_train`
+        rule -- a query that IS that train row does not pick itself; it needs one more candidate, n1 >= V + 1.  Stays on the device."""
+        dev = self.bank.device
+        p = self.poses if poses is None else self._poses(poses, None, "PathSampler.views").to(dev).contiguous()
+        Q = int(p.shape[0])
+        if self._K_per_pose and Q != self.P:
+            raise HnrError("PathSampler.views: %d poses for per-pose intrinsics of %d" % (Q, self.P))
+        ex = None
+        if exclude_rows is not None:
+            if self.n1 < self.V + 1:
+                raise HnrError("PathSampler.views: n1 = %d candidates cannot give %d views plus an excluded row" % (self.n1, self.V))
+            ex = torch.as_tensor(np.asarray(exclude_rows.detach().cpu() if isinstance(exclude_rows, torch.Tensor) else exclude_rows, dtype=np.int32))
+            if tuple(ex.shape) != (Q,):
+                raise HnrError("PathSampler.views: exclude_rows must be [%d], got %s" % (Q, tuple(ex.shape)))
+            ex = ex.to(dev).contiguous()
+        out = torch.empty((Q, self.V), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(self.L.hnr_pose_views(ctypes.byref(self.bank._c), _lib.ptr(p), Q, _lib.ptr(self.intrinsic), self._K_per_pose, _lib.ptr(ex), self.V, self.n1,
+                                             _lib.ptr(out), _lib.stream()), "hnr_pose_views")
+        return out
+
+    def next(self, out=None):
+        """The item of frame step % P; step += 1 on the device.  out=None: the sampler's own static tensors; out = a dict: the outputs whose keys
+        are present in it ("camrot" or "camrotc2w" for the rotation) are written into those tensors and no others are touched."""
+        if out is None:
+            if self._static is None:
+                t = self._alloc()
+                self._static = (self._finish(t), self._bind(t, "PathSampler.next"))
+            res, o = self._static
+        else:
+            key = tuple((k, v.data_ptr(), v.numel(), v.dtype) for k, v in out.items() if isinstance(v, torch.Tensor))
+            o = self._bound.get(key)
+            if o is None:
+                t = {k: v for k, v in out.items() if isinstance(v, torch.Tensor)}
+                if "camrotc2w" in t:
+                    if "camrot" in t and t["camrot"].data_ptr() != t["camrotc2w"].data_ptr():
+                        raise HnrError("PathSampler.next: out has both camrot and camrotc2w, and they are different tensors")
+                    t["camrot"] = t.pop("camrotc2w")
+                if len(self._bound) > 16:
+                    self._bound.clear()
+                o = self._bound[key] = self._bind(t, "PathSampler.next")
+            res = out
+        self._launch(o, _lib.ptr(self.step), 0, [v for k, v in res.items() if isinstance(v, torch.Tensor) and k != "camrotc2w"])
+        return res
+
+    def item(self, i):
+        """The item of frame i of the table as it stands on the device, no counter; fresh tensors."""
+        i = int(i)
+        if i < 0 or i >= self.P:
+            raise HnrError("PathSampler.item: frame %d is outside the path (0 .. %d)" % (i, self.P - 1))
+        t = self._alloc()
+        self._launch(self._bind(t, "PathSampler.item"), None, i, ())
+        return self._finish(t)

@@ -28,7 +28,7 @@
  *              hnr_alpha_pack, hnr_visual_hull_select*, hnr_point_occlusion*, hnr_point_view_attrs_vis,
  *              hnr_frame_batch*, hnr_frame_item, hnr_ray_miss_rank, hnr_raft_flow*, hnr_blur_score_pair* (hnr_blur_edges and the other hnr_raft_*
  *              entries are STAGE), hnr_adam_plan, hnr_adam_step, hnr_frame_depth_rays, hnr_depth_loss, hnr_depth_metrics (and the HNR_DM_* row layout),
- *              hnr_ssim_loss, hnr_ssim_loss_scratch_bytes.
+ *              hnr_ssim_loss, hnr_ssim_loss_scratch_bytes, hnr_pose_views, hnr_path_item, hnr_frame_store.
  *   STAGE   -- everything else (hnr_chain_*, hnr_mlp3_*, hnr_merge*, hnr_mixup_stage, hnr_proj_*, hnr_h2*, hnr_linear_*, hnr_gather_*, hnr_ksum*,
  *              hnr_segment_*, hnr_absmax, hnr_div_probe, hnr_image_features_bwd_bbox, the glue kernels of the training backward -- hnr_final_color_bwd*,
  *              hnr_ksum_bwd_rows8, hnr_extras_dgrad, hnr_point_small_grads, hnr_point_rows_bwd, hnr_dleaky_add, hnr_sum_views, hnr_unique_points*,
@@ -1121,6 +1121,55 @@ int hnr_frame_batch(const hnr_frame_bank *target, const hnr_frame_bank *referenc
 int hnr_frame_item(const hnr_frame_bank *target, const hnr_frame_bank *reference, const int32_t *d_nearest, int V, int row, const float *d_pixels,
                    int64_t n_rays, int margin, int dir_norm, const float *bg_color, int downweight_blurry_feats, const hnr_frame_batch_out *out,
                    void *d_scratch, int64_t scratch_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Camera paths (csrc/path.hip): the dataset item of a camera that is NOT a row of a frame bank -- a fly-through, an orbit, a viewer's pose -- and
+ * the store of a rendered frame into a clip.  The reference's run/render_vid.py is no usable definition (get_dummyrot_item carries no reference
+ * views, its rays come from the Blender ray builder applied to an OpenCV pose, the ScanNet dataset has no render_poses), so the behaviour is DEFINED
+ * here and restated in tests/path_ref.py.  All three entries: stream-ordered, nothing allocated, nothing read back, no atomics, deterministic,
+ * capturable on one stream; every fp32 operation rounded on its own in the order written; HNR_ERR_BADARG before any launch.
+ *
+ * hnr_pose_views -- the V reference views of Q free cameras among the T = reference->F cameras of a bank: get_nearest_cam_id
+ * (data/nerf_synth360_ft_dataset.py:49-74; frames.nearest_by_pose on the host) with every tie decided.  Only d_c2w, d_intrinsic
+ * (intrinsic_per_frame), F, H, W of the bank are read.
+ *   d_poses [Q,4,4] c2w, d_intrinsic [3,3] or, with intrinsic_per_pose = 1, [Q,3,3]: device memory, read when the kernel runs.
+ *   direction   of a camera (c2w, K): the normalised ray of pixel (W / 2, H / 2) (integer halves), the arithmetic of the batch's rays:
+ *               x = ((px + 0.5f) - K02) / K00, y = ((py + 0.5f) - K12) / K11, dir[c] = (x R[c][0] + y R[c][1]) + R[c][2],
+ *               d = dir / (sqrt((dx^2 + dy^2) + dz^2) + 1e-5f); a train camera's direction is this expression of its own c2w and K.
+ *   step 1      score s_t = (tx dx + ty dy) + tz dz; the n1 rows with the largest s, equal scores (-0 = +0) the lower row first (a stable
+ *               argsort(-s)).  n1 is the caller's: min(num_times V, floor(T / 10)) in the reference.
+ *   step 2      those n1 rows by e_t = sqrt((ax^2 + ay^2) + az^2), a = c2w_t[:3,3] - c2w_q[:3,3], ascending, equal distances in step-1 order.
+ *   exclude     d_exclude_row [Q] int32 or NULL: when the FIRST row of step 2 equals d_exclude_row[q] (>= 0) it is skipped (the `is_train` rule).
+ *   result      the first V rows that remain -> d_nearest [Q,V] int32.  A NaN score or distance orders last.
+ *   limits      1 <= V <= 64, 1 <= T <= 8192, 1 <= Q <= 2^24, V + (d_exclude_row ? 1 : 0) <= n1 <= T.
+ * One launch, one workgroup per query; the orders come from a bitonic sort of 64-bit keys (float bits, index) in LDS. */
+int hnr_pose_views(const hnr_frame_bank *reference, const float *d_poses, int Q, const float *d_intrinsic, int intrinsic_per_pose,
+                   const int32_t *d_exclude_row, int V, int n1, int32_t *d_nearest, void *stream);
+
+/* hnr_path_item -- the dataset item of frame i of a pose table d_poses [P,4,4] (d_intrinsic [3,3], or [P,3,3] with intrinsic_per_pose = 1), into the
+ * struct hnr_frame_batch / hnr_frame_item fill; NULL outputs are skipped.  i = d_step[0] % P read on the device, d_step[0] (uint64) advancing by
+ * exactly one; with d_step = NULL, i is the explicit host int.  Pose and intrinsic are read from device memory when the kernels run: rewriting the
+ * table in place (a viewer, a path generator on the device) changes the next item, the host knows nothing about them.
+ *   written     d_campos, d_camrot, d_c2w, d_intrinsic (of pose i); the V views hnr_pose_views picks for it (no exclusion) as d_c2w_nearest,
+ *               d_w2c_nearest, d_campos_nearest, d_intrinsic_nearest, d_frame_weight_nearest (the bank's weights with downweight_blurry_feats,
+ *               ones otherwise), d_vid_angle_nearest, d_images_nearest float32 (16-byte aligned for a uint8 bank); d_bg_color = bg_color (3 host
+ *               floats), d_frame_row = i; d_raydir / d_pixel_idx for every pixel minus `margin` in scan-line order, (W - 2 margin)(H - 2 margin) rays,
+ *               H and W the reference bank's.  The arithmetic is hnr_frame_item's: for a pose equal to a bank row's camera the bits are equal.
+ *   not written d_gt_image, d_frame_weight, d_patch_table: non-NULL is HNR_ERR_BADARG.
+ *   d_scratch   HNR_PATH_SCRATCH_BYTES bytes, private to the call sequence of one sampler.
+ * At most three launches. */
+#define HNR_PATH_SCRATCH_BYTES 512
+int hnr_path_item(const hnr_frame_bank *reference, const float *d_poses, int P, const float *d_intrinsic, int intrinsic_per_pose, int V, int n1,
+                  uint64_t *d_step, int i, int margin, int dir_norm, const float *bg_color, int downweight_blurry_feats, const hnr_frame_batch_out *out,
+                  void *d_scratch, int64_t scratch_bytes, void *stream);
+
+/* hnr_frame_store -- rendered rays into one frame of a clip: d_color [R,3], d_pixel_idx [R,2] float32 (x, y; truncated), optional d_depth [R] ->
+ * any non-NULL combination of d_img8 [h,w,3] uint8 = q(colour), q(x) = (uint8) trunc(min(max(x, 0), 1) * 255.0f) as hnr_frame_metrics quantises
+ * (one fp32 product; NaN -> 0), d_image [h,w,3] float32, d_depth_image [h,w] float32 (needs d_depth).  The frame is cleared first, in stream order:
+ * pixels no ray reached read 0.  A pixel index outside the frame (or NaN) is dropped; the indices of one call must be distinct pixels.
+ * R = 0 only clears.  Replaces torch.zeros + index-put + a separate quantisation per frame. */
+int hnr_frame_store(const float *d_color, const float *d_pixel_idx, const float *d_depth, int64_t R, int h, int w, uint8_t *d_img8, float *d_image,
+                    float *d_depth_image, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Depth supervision from resident sensor depth (csrc/depth_sup.hip): the per-ray ground-truth depth of a batch, the depth term of the training loss
