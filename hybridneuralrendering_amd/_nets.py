@@ -4,6 +4,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._cache import Derived as Packed          # a module's packed weights on the device: one cache entry (flow, perceptual, mvs_init, mvs_depth import it from here)
 from ._lib import HnrError
 
 
@@ -57,24 +58,6 @@ def load_checked(module, sd, who, strict=True, hint="", **kw):
     return res
 
 
-class Packed:
-    """A packed copy of a module's weights on the device, rebuilt when a parameter or buffer changes or moves.  A change is seen through the tensors'
-    addresses and in-place version counters: `load_state_dict`, optimiser steps, `.to()` and any other in-place update are covered.  A tensor swapped in
-    through `p.data = other` can, in principle, land on a recycled address with the same counter: call `invalidate()` after such an assignment."""
-
-    def __init__(self):
-        self.key, self.value = None, None
-
-    def invalidate(self):
-        self.key, self.value = None, None
-
-    def get(self, tensors, build):
-        key = tuple((t.data_ptr(), t._version, str(t.device)) for t in tensors)
-        if key != self.key:
-            self.value, self.key = build(), key
-        return self.value
-
-
 class PackedWeights:
     """Mixin of an nn.Module that has `pack_host()` (a CPU tensor or a tuple of them) and a `Packed` in `self._packed`."""
 
@@ -92,5 +75,5 @@ class PackedWeights:
         return self._packed.get(list(self.parameters()) + list(self.buffers()), build)
 
     def invalidate_packed(self):
-        """Needed only after replacing a parameter's storage with `p.data = ...` (see Packed)."""
+        """Needed only after replacing a parameter's storage with `p.data = ...` (_cache.py, rule 2)."""
         self._packed.invalidate()

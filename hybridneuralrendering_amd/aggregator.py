@@ -16,6 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._cache import Derived
 from ._lib import HnrError
 from .linear import PackedLinear, FusedMlp3
 
@@ -123,8 +124,7 @@ class PointAggregator(nn.Module):
                   self.aux_merge_weight_block, self.aux_block_s1, self.aux_block_s2, self.aux_block_s3,
                   self.color_mixup_block, self.color_final_block):
             _init_seq(m)
-        self._packed = None
-        self._packed_key = None
+        self._packed, self._packed_chain, self._packed_mlp3 = Derived(), Derived(), Derived()      # the latter two follow packed()'s key
 
     def blur_predictor(self):
         """What viewmlp returns next to the decoded features (:1339-1344): None, the MLP, or [conv block, MLP]."""
@@ -137,15 +137,15 @@ class PointAggregator(nn.Module):
     # ------------------------------------------------------------------------------------------
     def packed(self):
         """Weights in the kernels' layouts, re-packed only when a parameter changed."""
-        key = tuple((p.data_ptr(), p._version) for p in self.parameters())
-        if self._packed is not None and key == self._packed_key:
-            return self._packed
+        return self._packed.get(self.parameters(), self._pack)
+
+    def _pack(self):
         dev = next(self.parameters()).device
         if dev.type != "cuda":
             raise HnrError("PointAggregator weights must be on the GPU (there is no CPU path)")
         lin = lambda seq, i: PackedLinear(seq[i].weight, seq[i].bias)
         f32 = lambda t: t.detach().to(torch.float32).contiguous()
-        pk = dict(
+        return dict(
             b1=[lin(self.block1, 0), lin(self.block1, 2)], b3=[lin(self.block3, 0), lin(self.block3, 2)],
             # block1.0 split by input columns: [emb32 | PE(emb) 192] depend on the point only, [PE(dists) 60] on the pair
             b1_point=PackedLinear(self.block1[0].weight[:, :224].contiguous(), None),
@@ -165,16 +165,13 @@ class PointAggregator(nn.Module):
             conv_b=[f32(m[i].bias) for m in (self.aux_block_s1, self.aux_block_s2, self.aux_block_s3) for i in (0, 2)],
             slope=float(self.block1[1].negative_slope),
         )
-        self._packed, self._packed_key = pk, key
-        self._packed_chain = None
-        self._packed_mlp3 = None
-        return pk
 
     def packed_chain(self):
         """block1 / block3 / alpha_branch in the image of the fused per-neighbour chain (hnr_chain_pack; csrc/chain.hip), packed
         with the fp32 images and re-packed when a parameter changes."""
         self.packed()
-        if getattr(self, "_packed_chain", None) is None:
+
+        def build():
             L = _lib.lib()
             dev = next(self.parameters()).device
             buf = torch.empty((int(L.hnr_chain_packed_bytes()),), dtype=torch.uint8, device=dev)
@@ -185,23 +182,24 @@ class PointAggregator(nn.Module):
                     f32(self.alpha_branch[0].weight).reshape(256), f32(self.alpha_branch[0].bias).reshape(1)]
             with torch.cuda.device(dev):
                 _lib.check(L.hnr_chain_pack(_lib.ptr(w0), 60, *[_lib.ptr(t) for t in args], _lib.ptr(buf), _lib.stream()), "hnr_chain_pack")
-            self._packed_chain = buf
-        return self._packed_chain
+            return buf
+        return self._packed_chain.get((), build, extra=self._packed.key)
 
     def packed_mlp3(self):
         """The per-sample MLPs as fused three-layer launches (hnr_mlp3_forward; csrc/mlp.hip): colour feature, merge weights
         (first layer split: the image-feature / view-direction columns here, the colour-feature columns per sample in `mw0_cf`), mix-up."""
         self.packed()
-        if getattr(self, "_packed_mlp3", None) is None:
+
+        def build():
             cf, mw, mx = self.color_feature_branch, self.aux_merge_weight_block, self.color_mixup_block
             w_fd = torch.cat([mw[0].weight[:, :45], mw[0].weight[:, 173:176]], dim=1).contiguous()
-            self._packed_mlp3 = dict(
+            return dict(
                 # colour feature + on its tail the colour-feature columns of aux_merge_weight_block.0 (with that layer's bias), once per sample
                 cf=FusedMlp3([cf[0].weight, cf[2].weight, cf[4].weight, mw[0].weight[:, 45:173].contiguous()],
                              [cf[0].bias, cf[2].bias, cf[4].bias, mw[0].bias], [1, 1, 1, 0]),
                 mw=FusedMlp3([w_fd, mw[2].weight, mw[4].weight], [None, mw[2].bias, mw[4].bias], [1, 1, 1]),
                 mx=FusedMlp3([mx[0].weight, mx[2].weight, mx[4].weight], [mx[0].bias, mx[2].bias, mx[4].bias], [1, 1, 0]))
-        return self._packed_mlp3
+        return self._packed_mlp3.get((), build, extra=self._packed.key)
 
     def point_table(self, emb, ids=None, n_ids=None, want_rows=False, out=None):
         """[N,256] = [emb | PE3(emb)] @ block1.0.weight[:, :224]^T -- the point-only part of block1's first layer

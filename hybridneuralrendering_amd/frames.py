@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._cache import mark_written
 from ._lib import HnrError
 
 MODES = {"random": 0, "patch": 1, "dilated": 2}
@@ -192,7 +193,75 @@ class FrameBank:
         return self
 
 
-class BatchSampler:
+class _Sampler:
+    """What BatchSampler and PathSampler share: the checks of the margin, the background colour and the output tensors, the item's host-side keys,
+    and where next() writes.  A subclass has `bank`, `margin`, `near`, `far`, `_static = None`, `_bound = {}`, `_shapes()` (name -> (shape, dtype)
+    of next()'s outputs), `_alloc()` (those tensors) and `_bind(tensors, what)`."""
+
+    def _check_margin(self):
+        H, W, m = self.bank.H, self.bank.W, self.margin
+        if m < 0 or W - 2 * m <= 0 or H - 2 * m <= 0:
+            raise HnrError("%s: margin %d leaves no pixel of a %dx%d frame (an empty range)" % (type(self).__name__, m, H, W))
+
+    def _triple(self, bg_color):
+        bg = tuple(float(c) for c in bg_color)
+        if len(bg) != 3:
+            raise HnrError("%s: bg_color must have three components" % type(self).__name__)
+        return bg
+
+    def _finish(self, t):
+        d = dict(t)
+        d["camrotc2w"] = d["camrot"]
+        d.update(near=self.near, far=self.far, h=self.bank.H, w=self.bank.W)
+        return d
+
+    def _bind_outputs(self, tensors, sh, what):
+        """name -> tensor  =>  hnr_frame_batch_out; every tensor that is an output (a name of `sh`) checked against the expected element count and
+        dtype.  (gt_depth is no field of the struct: BatchSampler hands it to the depth launch.)"""
+        o = _lib.FrameBatchOut()
+        for k, t in tensors.items():
+            if k not in sh:
+                continue
+            shape, dt = sh[k]
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != self.bank.device or t.dtype != dt or not t.is_contiguous() or \
+                    t.numel() != int(np.prod(shape)):
+                raise HnrError("%s: output %r must be a contiguous %s tensor of %s on %s, got %s %s" % (
+                    what, k, dt, "x".join(str(s) for s in shape), self.bank.device, getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
+            if k == "images_nearest" and t.data_ptr() % 16:
+                raise HnrError("%s: images_nearest must be 16-byte aligned" % what)
+            if k != "gt_depth":
+                setattr(o, "d_" + k, t.data_ptr())
+        return o
+
+    def _next_outputs(self, out):
+        """Where next(out) writes: (the dict it returns, what _bind made of its tensors).  out=None: the sampler's own static tensors, allocated and
+        bound on the first call.  out = a dict: bound once per set of tensors (the bound image holds addresses, so address, size and dtype are its
+        whole key).  The launches that follow write these tensors behind torch's back, at the same addresses call after call: rule 3 of _cache.py."""
+        what = type(self).__name__ + ".next"
+        if out is None:
+            if self._static is None:
+                t = self._alloc()
+                self._static = (self._finish(t), self._bind(t, what))
+            res, bound = self._static
+        else:
+            key = tuple((k, v.data_ptr(), v.numel(), v.dtype) for k, v in out.items() if isinstance(v, torch.Tensor))
+            bound = self._bound.get(key)
+            if bound is None:                                 # shapes and dtypes are checked once per set of tensors
+                t = {k: v for k, v in out.items() if isinstance(v, torch.Tensor)}
+                if "camrotc2w" in t:
+                    if "camrot" in t and t["camrot"].data_ptr() != t["camrotc2w"].data_ptr():
+                        raise HnrError("%s: out has both camrot and camrotc2w, and they are different tensors" % what)
+                    t["camrot"] = t.pop("camrotc2w")
+                if len(self._bound) > 16:
+                    self._bound.clear()
+                bound = self._bound[key] = self._bind(t, what)
+            res = out
+        sh = self._shapes()
+        mark_written(v for k, v in res.items() if (k in sh or k == "camrotc2w") and isinstance(v, torch.Tensor))
+        return res, bound
+
+
+class BatchSampler(_Sampler):
     """The dataset item of every step, written on the device.
 
     mode "random" | "patch" (size x size rays) | "dilated" (dilation_setup "pn_ps_dlo_dhi": (pn ps)^2 rays in the layout of scenes.dilated_patch_batch and
@@ -225,8 +294,7 @@ class BatchSampler:
         self.bank, self.mode, self.margin = bank, mode, int(margin)
         self.near, self.far = float(near), float(far)
         H, W, m = bank.H, bank.W, self.margin
-        if m < 0 or W - 2 * m <= 0 or H - 2 * m <= 0:
-            raise HnrError("BatchSampler: margin %d leaves no pixel of a %dx%d frame (an empty range)" % (m, H, W))
+        self._check_margin()
         pn = ps = dlo = dhi = 0
         if mode == "dilated":
             try:
@@ -248,9 +316,7 @@ class BatchSampler:
         bg_random = isinstance(bg_color, str)
         if bg_random and bg_color != "random":
             raise HnrError("BatchSampler: bg_color must be a triple or 'random'")
-        self.bg = (1.0, 1.0, 1.0) if bg_random else tuple(float(c) for c in bg_color)
-        if len(self.bg) != 3:
-            raise HnrError("BatchSampler: bg_color must have three components")
+        self.bg = (1.0, 1.0, 1.0) if bg_random else self._triple(bg_color)
         self.dir_norm, self.downweight = int(bool(dir_norm)), int(bool(downweight_blurry_feats))
         seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.seed = seed
@@ -266,8 +332,9 @@ class BatchSampler:
         self._static, self._bound, self._own = None, {}, {}
 
     # ------------------------------------------------------------------------------------------------ plumbing
-    def _shapes(self, R):
-        b = self.bank
+    def _shapes(self, R=None):
+        """R: the item's ray count (default: next()'s)"""
+        b, R = self.bank, self.R if R is None else R
         V, H, W = b.V, b.H, b.W
         f, i = torch.float32, torch.int32
         sh = dict(raydir=((R, 3), f), pixel_idx=((R, 2), f), gt_image=((R, 3), f), campos=((3,), f), camrot=((3, 3), f), c2w=((4, 4), f), intrinsic=((3, 3), f),
@@ -281,23 +348,17 @@ class BatchSampler:
             sh["patch_table"] = ((self.pn * self.pn, 3), i)
         return sh
 
-    def _alloc(self, R, with_table):
-        dev = self.bank.device
-        t = {k: torch.empty(s, dtype=d, device=dev) for k, (s, d) in self._shapes(R).items() if with_table or k != "patch_table"}
-        return t
+    def _alloc(self, R=None):
+        """next()'s tensors, or, R given, those of an item of R rays (no patch_table)"""
+        return {k: torch.empty(s, dtype=d, device=self.bank.device) for k, (s, d) in self._shapes(R).items() if R is None or k != "patch_table"}
 
-    def _finish(self, t):
-        d = dict(t)
-        d["camrotc2w"] = d["camrot"]
-        d.update(near=self.near, far=self.far, h=self.bank.H, w=self.bank.W)
-        return d
-
-    def _bind(self, tensors, R, what):
+    def _bind(self, tensors, what, R=None):
         """name -> tensor  =>  (hnr_frame_batch_out, the depth launch's tensors or None); every tensor checked against the expected element count
         and dtype.  gt_depth among the tensors: the lookup reads the item's frame_row, pixel_idx (and intrinsic, with a depth intrinsic) from the
         device, so outputs of those names that the caller did not give are bound to tensors of the sampler's own (allocated here, once per R)."""
+        R = self.R if R is None else R
         sh = self._shapes(R)
-        o = _lib.FrameBatchOut()
+        dep = None
         if "gt_depth" in sh and "gt_depth" in tensors:
             tensors = dict(tensors)
             for k in ("frame_row", "pixel_idx") + (("intrinsic",) if self.bank.depth_intrinsic is not None else ()):
@@ -305,22 +366,8 @@ class BatchSampler:
                     if (k, R) not in self._own:
                         self._own[(k, R)] = torch.empty(sh[k][0], dtype=sh[k][1], device=self.bank.device)
                     tensors[k] = self._own[(k, R)]
-        dep = None
-        for k, t in tensors.items():
-            if k not in sh:
-                continue
-            shape, dt = sh[k]
-            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != self.bank.device or t.dtype != dt or not t.is_contiguous() or \
-                    t.numel() != int(np.prod(shape)):
-                raise HnrError("%s: output %r must be a contiguous %s tensor of %s on %s, got %s %s" % (
-                    what, k, dt, "x".join(str(s) for s in shape), self.bank.device, getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
-            if k == "images_nearest" and t.data_ptr() % 16:
-                raise HnrError("%s: images_nearest must be 16-byte aligned" % what)
-            if k != "gt_depth":
-                setattr(o, "d_" + k, t.data_ptr())
-        if "gt_depth" in sh and "gt_depth" in tensors:
             dep = (tensors["frame_row"], tensors["pixel_idx"], tensors.get("intrinsic"), tensors["gt_depth"])
-        return o, dep
+        return self._bind_outputs(tensors, sh, what), dep
 
     def _depth_rays(self, dep, R):
         """gt_depth of the item just written: one launch behind the batch's, reading its frame_row / pixel_idx on the device"""
@@ -355,24 +402,7 @@ class BatchSampler:
         -- `sampler.next(out=cap.inputs); cap.step()` is a training step with no copy and no host read.  Returns the dict written to."""
         if self.schedule is None:
             raise HnrError("BatchSampler.next: no schedule (set_schedule(rows) first)")
-        if out is None:
-            if self._static is None:
-                t = self._alloc(self.R, True)
-                self._static = (self._finish(t), self._bind(t, self.R, "BatchSampler.next"))
-            res, (o, dep) = self._static
-        else:
-            key = tuple((k, v.data_ptr(), v.numel(), v.dtype) for k, v in out.items() if isinstance(v, torch.Tensor))
-            o, dep = self._bound.get(key, (None, None))
-            if o is None:                                     # shapes and dtypes are checked once per set of tensors
-                t = {k: v for k, v in out.items() if isinstance(v, torch.Tensor)}
-                if "camrotc2w" in t:
-                    if "camrot" in t and t["camrot"].data_ptr() != t["camrotc2w"].data_ptr():
-                        raise HnrError("BatchSampler.next: out has both camrot and camrotc2w, and they are different tensors")
-                    t["camrot"] = t.pop("camrotc2w")
-                if len(self._bound) > 16:
-                    self._bound.clear()
-                o, dep = self._bound[key] = self._bind(t, self.R, "BatchSampler.next")
-            res = out
+        res, (o, dep) = self._next_outputs(out)
         ref, nearest, V = self._views()
         with torch.cuda.device(self.bank.device):
             _lib.check(self.L.hnr_frame_batch(ctypes.byref(self.bank._c), ref, nearest, V, ctypes.byref(self.prm), _lib.ptr(self.schedule), self._n_schedule,
@@ -396,8 +426,8 @@ class BatchSampler:
                 raise HnrError("BatchSampler.item: pixels must be [R,2], R >= 1")
         else:
             R = (self.bank.W - 2 * self.margin) * (self.bank.H - 2 * self.margin)
-        t = self._alloc(R, False)
-        o, dep = self._bind(t, R, "BatchSampler.item")
+        t = self._alloc(R)
+        o, dep = self._bind(t, "BatchSampler.item", R)
         ref, nearest, V = self._views()
         with torch.cuda.device(dev):
             _lib.check(self.L.hnr_frame_item(ctypes.byref(self.bank._c), ref, nearest, V, row, _lib.ptr(pixels), R, self.margin, self.dir_norm,
@@ -408,7 +438,7 @@ class BatchSampler:
         return self._finish(t)
 
 
-class PathSampler:
+class PathSampler(_Sampler):
     """The dataset item of a camera that is no row of a bank: frame i of a pose table, with the reference views chosen on the device (csrc/path.hip;
     the definitions are in include/hnr.h and tests/path_ref.py).
 
@@ -420,8 +450,7 @@ class PathSampler:
     downweight_blurry_feats as BatchSampler.
 
     `next(out=None)` writes the item of frame step % P and advances the device counter `step`: the same static tensors on every call, no
-    allocation after the first, no host read, at most three launches, capturable on one stream; `out` as BatchSampler.next.  (Its tensors' `_version`
-    is bumped per call, so the renderer's feature-map cache follows the new reference views; after a graph REPLAY the caller bumps them.)  `item(i)` is the explicit
+    allocation after the first, no host read, at most three launches, capturable on one stream; `out` as BatchSampler.next.  `item(i)` is the explicit
     form (fresh tensors).  `views(poses=None)` is the [Q,V] table alone.  The dict has the keys driver.render_image reads -- raydir, pixel_idx,
     campos, camrotc2w = camrot, c2w, intrinsic, bg_color, near, far, h, w, c2w_nearest, w2c_nearest, campos_nearest, intrinsic_nearest,
     images_nearest, frame_weight_nearest, vid_angle_nearest -- and frame_row [1] = i.  A path frame has no gt_image, frame_weight or patch_table."""
@@ -447,12 +476,9 @@ class PathSampler:
             raise HnrError("PathSampler: n1 = min(num_times V, T // 10) = %d candidates of %d cameras cannot give %d views" % (self.n1, bank.F, self.V))
         if isinstance(bg_color, str):
             raise HnrError("PathSampler: bg_color must be a triple (%r is not supported for path frames)" % (bg_color,))
-        self.bg = tuple(float(c) for c in bg_color)
-        if len(self.bg) != 3:
-            raise HnrError("PathSampler: bg_color must have three components")
+        self.bg = self._triple(bg_color)
+        self._check_margin()
         H, W, m = bank.H, bank.W, self.margin
-        if m < 0 or W - 2 * m <= 0 or H - 2 * m <= 0:
-            raise HnrError("PathSampler: margin %d leaves no pixel of a %dx%d frame (an empty range)" % (m, H, W))
         self.R = (W - 2 * m) * (H - 2 * m)
         self.dir_norm, self.downweight = int(bool(dir_norm)), int(bool(downweight_blurry_feats))
         poses = self._poses(poses, None, "PathSampler")
@@ -499,35 +525,13 @@ class PathSampler:
     def _alloc(self):
         return {k: torch.empty(s, dtype=d, device=self.bank.device) for k, (s, d) in self._shapes().items()}
 
-    def _finish(self, t):
-        d = dict(t)
-        d["camrotc2w"] = d["camrot"]
-        d.update(near=self.near, far=self.far, h=self.bank.H, w=self.bank.W)
-        return d
-
     def _bind(self, tensors, what):
-        sh = self._shapes()
-        o = _lib.FrameBatchOut()
-        for k, t in tensors.items():
+        for k in tensors:
             if k in ("gt_image", "frame_weight", "patch_table", "gt_depth"):
                 raise HnrError("%s: a path frame has no %s (there is no ground truth for a free camera)" % (what, k))
-            if k not in sh:
-                continue
-            shape, dt = sh[k]
-            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != self.bank.device or t.dtype != dt or not t.is_contiguous() or \
-                    t.numel() != int(np.prod(shape)):
-                raise HnrError("%s: output %r must be a contiguous %s tensor of %s on %s, got %s %s" % (
-                    what, k, dt, "x".join(str(s) for s in shape), self.bank.device, getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
-            if k == "images_nearest" and t.data_ptr() % 16:
-                raise HnrError("%s: images_nearest must be 16-byte aligned" % what)
-            setattr(o, "d_" + k, t.data_ptr())
-        return o
+        return self._bind_outputs(tensors, self._shapes(), what)
 
-    def _launch(self, o, step, i, written):
-        """... and the `_version` rule (optim.py): the kernels write `written` behind torch's back -- the static tensors of next() keep their
-        addresses from frame to frame -- and the renderer caches the reference views' feature map per (address, _version)."""
-        for t in written:
-            torch.autograd.graph.increment_version(t)
+    def _launch(self, o, step, i):
         with torch.cuda.device(self.bank.device):
             _lib.check(self.L.hnr_path_item(ctypes.byref(self.bank._c), _lib.ptr(self.poses), self.P, _lib.ptr(self.intrinsic), self._K_per_pose, self.V, self.n1,
                                             step, i, self.margin, self.dir_norm, (ctypes.c_float * 3)(*self.bg), self.downweight, ctypes.byref(o),
@@ -569,25 +573,8 @@ class PathSampler:
     def next(self, out=None):
         """The item of frame step % P; step += 1 on the device.  out=None: the sampler's own static tensors; out = a dict: the outputs whose keys
         are present in it ("camrot" or "camrotc2w" for the rotation) are written into those tensors and no others are touched."""
-        if out is None:
-            if self._static is None:
-                t = self._alloc()
-                self._static = (self._finish(t), self._bind(t, "PathSampler.next"))
-            res, o = self._static
-        else:
-            key = tuple((k, v.data_ptr(), v.numel(), v.dtype) for k, v in out.items() if isinstance(v, torch.Tensor))
-            o = self._bound.get(key)
-            if o is None:
-                t = {k: v for k, v in out.items() if isinstance(v, torch.Tensor)}
-                if "camrotc2w" in t:
-                    if "camrot" in t and t["camrot"].data_ptr() != t["camrotc2w"].data_ptr():
-                        raise HnrError("PathSampler.next: out has both camrot and camrotc2w, and they are different tensors")
-                    t["camrot"] = t.pop("camrotc2w")
-                if len(self._bound) > 16:
-                    self._bound.clear()
-                o = self._bound[key] = self._bind(t, "PathSampler.next")
-            res = out
-        self._launch(o, _lib.ptr(self.step), 0, [v for k, v in res.items() if isinstance(v, torch.Tensor) and k != "camrotc2w"])
+        res, o = self._next_outputs(out)
+        self._launch(o, _lib.ptr(self.step), 0)
         return res
 
     def item(self, i):
@@ -596,5 +583,5 @@ class PathSampler:
         if i < 0 or i >= self.P:
             raise HnrError("PathSampler.item: frame %d is outside the path (0 .. %d)" % (i, self.P - 1))
         t = self._alloc()
-        self._launch(self._bind(t, "PathSampler.item"), None, i, ())
+        self._launch(self._bind(t, "PathSampler.item"), None, i)
         return self._finish(t)

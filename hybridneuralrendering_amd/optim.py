@@ -12,10 +12,8 @@ m' = m + w1 (g - m);  v' = v b2 + (w2 g) g;  den = sqrt(v') / bs + e;  p' = p - 
 row the tick kernel wrote (lr_t / bc1, sqrt(bc2), ...).  No weight decay, no amsgrad, no maximize: the reference uses none, and a group that asks
 for one is refused.
 
-The `_version` rule.  A kernel that writes parameter memory behind torch's back leaves `tensor._version` where it was, and the packed weights
-(aggregator.py), the feature map / per-point table / record cache (render.py) and the voxel grid (querier.py) are cached per `_version`: without a
-bump the next evaluation would silently render with the old weights.  `step()` therefore calls torch.autograd.graph.increment_version on every
-parameter it wrote; after a graph replay that contains the step, `mark_updated()` does (CapturedTrainStep.step calls it).
+The step writes parameter memory behind torch's back, and the renderer caches values derived from the parameters: `step()` marks every parameter
+it wrote (_cache.py, rule 3); after a graph replay that contains the step, `mark_updated()` does (CapturedTrainStep.step calls it).
 
 One step counter per optimiser (`adam_step`), not one per parameter: a parameter that never receives a gradient is skipped, like in torch; one that
 receives its FIRST gradient at a later step would get that step's bias correction where torch starts its own count at 1 -- no shipped configuration
@@ -28,6 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._cache import mark_written
 from ._lib import HnrError
 
 _DEFAULTS = dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8, lr_decay_exp=1.0, lr_decay_iters=1)
@@ -202,9 +201,8 @@ class DeviceAdam:
         self.mark_updated()
 
     def mark_updated(self):
-        """The `_version` rule (module docstring): every parameter the last prepared step writes counts as modified in place."""
-        for p in self._written:
-            torch.autograd.graph.increment_version(p)
+        """Every parameter the last prepared step writes counts as modified in place (_cache.py, rule 3)."""
+        mark_written(self._written)
 
     def zero_grad(self, set_to_none=True):
         for g in self.param_groups:

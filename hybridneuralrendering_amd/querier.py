@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._cache import Derived
 from ._lib import HnrError, GridParams, GridStats, QueryParams, CNT, NCOUNTS
 
 
@@ -237,10 +238,7 @@ class lighting_fast_querier:
             raise HnrError("opt.inverse > 0 (disparity-linear marching) is not used by any shipped config and is unsupported")
         self.inverse = getattr(opt, "inverse", 0)
         self.count = 0
-        self._grid = None
-        self._grid_key = None
-        self._grid_src = None
-        self._hp = None
+        self._grid_cache = Derived()          # value: (VoxelGrid, hyper-parameters, (min, max) of the cloud the grid describes)
         self._tmid = {}
         self.last_counts = None
         self.last_grid_stats = None
@@ -249,7 +247,21 @@ class lighting_fast_querier:
     def clean_up(self):
         if self._grid is not None:
             self._grid.free()
-        self._grid, self._grid_key, self._hp, self._grid_src, self._grid_bounds = None, None, None, None, None
+        self._grid_cache.invalidate()
+
+    @property
+    def _grid(self):
+        return None if self._grid_cache.value is None else self._grid_cache.value[0]
+
+    @property
+    def _grid_key(self):
+        """The entry's key in the flat form this attribute has always had: (address, shape, version of xyz) + the option tuple, None when empty."""
+        key = self._grid_cache.key
+        return None if key is None else key[0][0][:3] + key[1]
+
+    @property
+    def _hp(self):
+        return None if self._grid_cache.value is None else self._grid_cache.value[1]
 
     # -- hyper-parameters (:46-77) -------------------------------------------------------------
     def get_hyperparameters(self, vsize_np, point_xyz_w_tensor, ranges=None, bounds=None):
@@ -266,52 +278,47 @@ class lighting_fast_querier:
                 to_dev(ranges_np), to_dev(scaled_vsize_np), to_dev(scaled_vdim_np), to_dev(vscale_np),
                 to_dev(np.asarray(self.opt.kernel_size, dtype=np.int32)), to_dev(np.asarray(self.opt.query_size, dtype=np.int32)))
 
+    def _options(self):
+        return (tuple(self.opt.vsize), tuple(self.opt.vscale), tuple(self.opt.kernel_size), tuple(self.opt.query_size),
+                tuple(self.opt.ranges) if self.opt.ranges is not None else None, int(self.opt.P), int(self.opt.max_o), float(self.opt.radius_limit_scale))
+
     def _grid_for(self, point_xyz_w_tensor):
         xyz = point_xyz_w_tensor.detach()
-        key = self._key_of(xyz)
-        if self._grid is not None and key == self._grid_key:
-            return self._grid, self._hp
-        self.clean_up()
-        hp = self.get_hyperparameters(self.opt.vsize, point_xyz_w_tensor, ranges=self.opt.ranges)
-        self._grid_bounds = self._last_bounds
-        radius_limit_np, _, ranges_np, _, _, scaled_vsize_np, scaled_vdim_np = hp[:7]
-        self._grid = VoxelGrid(xyz.reshape(-1, 3), ranges_np[:3], scaled_vsize_np, scaled_vdim_np, self.opt.query_size,
-                               self.opt.P, self.opt.max_o)
-        self._grid_key, self._hp = key, hp
-        self._grid_src = xyz                                     # keeps the keyed buffer alive (its address must not be recycled)
-        self.last_grid_stats = self._grid.stats
-        return self._grid, hp
 
-    def _key_of(self, xyz):
-        return (xyz.data_ptr(), tuple(xyz.shape), xyz._version, tuple(self.opt.vsize), tuple(self.opt.vscale),
-                tuple(self.opt.kernel_size), tuple(self.opt.query_size), tuple(self.opt.ranges) if self.opt.ranges is not None else None,
-                int(self.opt.P), int(self.opt.max_o), float(self.opt.radius_limit_scale))
+        def build():
+            self.clean_up()
+            hp = self.get_hyperparameters(self.opt.vsize, point_xyz_w_tensor, ranges=self.opt.ranges)
+            _, _, ranges_np, _, _, scaled_vsize_np, scaled_vdim_np = hp[:7]
+            grid = VoxelGrid(xyz.reshape(-1, 3), ranges_np[:3], scaled_vsize_np, scaled_vdim_np, self.opt.query_size, self.opt.P, self.opt.max_o)
+            self.last_grid_stats = grid.stats
+            return grid, hp, self._last_bounds
+        return self._grid_cache.get((xyz,), build, self._options())[:2]
 
     def grow(self, point_xyz_w_tensor, n_old):
         """After NeuralPoints.grow_points (neural_points.py:376-402): `point_xyz_w_tensor` [1,N,3] / [N,3] is the grown cloud whose first n_old rows
         are the cloud the cached grid was built from.  When the grown cloud gives the SAME grid geometry (get_hyperparameters: its bounding box
         decides origin and dims) the tables are extended in place (hnr_grid_grow: 0.85 - 0.9 ms for 1 % new points at 2 M against a 4.7 ms rebuild) and
-        True is returned; otherwise the cache is dropped and the next query rebuilds.  Logically identical to a rebuild either way."""
+        True is returned; otherwise the cache is dropped and the next query rebuilds.  Logically identical to a rebuild either way.
+        The caller's contract: rows [:n_old] hold the positions of the cloud this querier built its grid from (grow_points appends).  They are not
+        compared on the device -- that would be a host read on this path; what is checked is that the tensor the grid was built from has not been
+        written, moved or reshaped since (an in-place change of the old positions: rebuild)."""
         xyz = point_xyz_w_tensor.detach()
-        if self._grid is None or self._hp is None or self._grid.n_points != int(n_old):
-            self.clean_up()
-            return False
-        # the grown cloud's bounds = the old cloud's combined with the NEW points' (min / max are exact: the same values as a pass over all N points)
-        old_b = getattr(self, "_grid_bounds", None)                    # bounds of the cloud the cached grid describes (_grid_for / grow)
         flat = xyz.reshape(-1, 3)
-        if old_b is None or flat.shape[0] <= int(n_old):
+        if not self._grid_cache.sources_unchanged() or self._grid.n_points != int(n_old) or flat.shape[0] <= int(n_old):
             self.clean_up()
             return False
+        grid, hp_old, old_b = self._grid_cache.value
+        # the grown cloud's bounds = the old cloud's combined with the NEW points' (min / max are exact: the same values as a pass over all N points)
         mn2, mx2 = points_bounds(flat[int(n_old):])
         hp = self.get_hyperparameters(self.opt.vsize, xyz if xyz.dim() == 3 else xyz[None], ranges=self.opt.ranges,
                                       bounds=(np.minimum(old_b[0], mn2), np.maximum(old_b[1], mx2)))
-        same = all(np.array_equal(np.asarray(hp[i]), np.asarray(self._hp[i])) for i in (0, 2, 5, 6))
-        if not same or not self._grid.grow(xyz.reshape(-1, 3)):
+        same = all(np.array_equal(np.asarray(hp[i]), np.asarray(hp_old[i])) for i in (0, 2, 5, 6))
+        if not same or not grid.grow(flat):
             self.clean_up()
             return False
-        self._grid_key, self._hp, self._grid_src = self._key_of(xyz if xyz.dim() == 3 else xyz[None]), hp, xyz
-        self._grid_bounds = self._last_bounds
-        self.last_grid_stats = self._grid.stats
+        # the entry now describes the grown cloud (a new key: the "build" hands the extended grid over)
+        self._grid_cache.get((xyz if xyz.dim() == 3 else xyz[None],), lambda: (grid, hp, self._last_bounds), self._options())
+        self.last_grid_stats = grid.stats
         return True
 
     def _tmid_for(self, near, far, D, R, device):

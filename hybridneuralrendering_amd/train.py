@@ -576,7 +576,7 @@ def train_step(path, aggregator, xyz, emb, conf, pdir, color, raydir, campos, ca
     optimizer (optim.DeviceAdam / optim.ShellOptimizers; None: exactly the path above): the optimiser step and the schedule tick are queued behind the
     backward on the same stream -- two more launches that read `pg` / `ag` in place -- and .grad is NOT assigned (the reference's
     optimizer.step() + neural_point_optimizer.step() + scheduler.step(), models/mvs_points_volumetric_model.py:111-131, models/base_model.py:148-150).
-    The parameters' `_version` is bumped, so the renderer's caches follow the new weights.  With TrainPath.reuse_outputs the gradient buffers keep
+    The parameters are marked as written (_cache.py), so the renderer's caches follow the new weights.  With TrainPath.reuse_outputs the gradient buffers keep
     their addresses and the optimiser's descriptor table is uploaded once; without it, once per step.
 
     gt_depth [R] float32 on the device (metres, 0 = no measurement; frames.BatchSampler's `gt_depth` for a FrameBank with depth frames) with
@@ -642,7 +642,7 @@ class CapturedTrainStep:
     optimizer (optim.DeviceAdam / optim.ShellOptimizers; None: the graph ends with the backward, as before): the optimiser step and the schedule tick
     are captured behind the backward -- one replay = one whole iteration -- and .grad is never assigned.  The warm-up steps run WITHOUT the
     optimiser (they must not move the parameters); its descriptor table is uploaded before the capture, which needs the gradient buffers'
-    addresses then: TrainPath.reuse_outputs is switched on for the path.  `step()` bumps the parameters' `_version` after the replay."""
+    addresses then: TrainPath.reuse_outputs is switched on for the path.  `step()` marks the parameters as written after the replay."""
 
     def __init__(self, path, aggregator, xyz, emb, conf, pdir, color, sample, near, far, zero_epsilon=1e-3, w_color=1.0, w_zero_one=1e-4,
                  patch_num=None, patch_size=None, patch_layout="grid", warmup=2, optimizer=None, learnable_blur=None, Rw2c=None, w_depth=0.0, w_ssim=0.0,
@@ -713,7 +713,7 @@ class CapturedTrainStep:
             self.inputs["frame_weight"].fill_(float(frame_weight))
         self.graph.replay()
         if self.optimizer is not None:
-            self.optimizer.mark_updated()              # the replay wrote the parameters behind torch's back: the caches keyed on _version must see it
+            self.optimizer.mark_updated()              # the replay wrote the parameters behind torch's back: the caches must see it (_cache.py, rule 3)
         elif assign_grads:
             emb, conf, pdir, color = self.leaves
             _assign_grads(self.agg, emb, conf, pdir, color, self.pg, self.ag, accumulate=False)

@@ -188,6 +188,33 @@ def test_the_seed_decides_the_sequence():
     assert torch.equal(mk(5).set_step(2).next()["pixel_idx"], pa)               # resuming at a step gives that step's batch
 
 
+@pytest.mark.parametrize("form", ["static", "out"])
+def test_next_marks_what_it_wrote_and_the_feature_map_follows(form):
+    """next() writes the same tensors on every call, from kernels torch knows nothing of: it marks them as written (_cache.py, rule 3), so a
+    renderer that cached the feature map of the first frame's reference views builds the second frame's."""
+    from hybridneuralrendering_amd import scenes
+    from hybridneuralrendering_amd.aggregator import PointAggregator
+    from hybridneuralrendering_amd.frames import BatchSampler
+    from hybridneuralrendering_amd.render import HybridRenderer
+    tr = _banks()[0]
+    opt = scenes.default_opt()
+    torch.manual_seed(0)
+    agg = PointAggregator(opt).to(DEV)
+    rnd = HybridRenderer(opt, agg, torch.device(DEV))
+    s = BatchSampler(tr, "random", size=8, margin=MARGIN, near=0.1, far=8.0).set_schedule([7, 0])
+    out = None if form == "static" else dict(images_nearest=torch.empty((4, 48, 64, 3), device=DEV), raydir=torch.empty((64, 3), device=DEV))
+    a = s.next(out=out)
+    img = a["images_nearest"]
+    v0, first = img._version, img.clone()
+    fm0 = rnd.feature_map(img).clone()
+    assert torch.equal(fm0, agg.image_features(img))
+    b = s.next(out=out)
+    assert b["images_nearest"] is img and img._version > v0 and b["raydir"]._version > 0
+    assert not torch.equal(img, first)                                          # (another frame, other reference views)
+    fm1 = rnd.feature_map(img)
+    assert torch.equal(fm1, agg.image_features(img)) and not torch.equal(fm1, fm0)
+
+
 def test_next_is_capturable_and_replays_the_following_steps():
     """next() captured in a torch.cuda.graph on one side stream after a warm-up call and replayed three times gives the batches of steps 1..3 that a
     second sampler with the same seed gives eagerly; the counter ends at 4; the three-row schedule wraps."""
