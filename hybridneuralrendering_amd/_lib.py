@@ -15,6 +15,9 @@ NCOUNTS = 9
 FEATNET_PACKED_ELEMS = 41368           # HNR_FEATNET_PACKED_ELEMS
 PREMLP_PACKED_ELEMS = 3104             # HNR_PREMLP_PACKED_ELEMS
 PATH_SCRATCH_BYTES = 512               # HNR_PATH_SCRATCH_BYTES
+RESIZE_TILE_W, RESIZE_TILE_H, RESIZE_LDS_BUDGET = 64, 16, 65536       # HNR_RESIZE_TILE_W, HNR_RESIZE_TILE_H, HNR_RESIZE_LDS_BUDGET
+RESIZE_FILTERS = dict(box=0, bilinear=1, hamming=2, bicubic=3, lanczos=4)         # HNR_RESIZE_BOX .. HNR_RESIZE_LANCZOS
+RESIZE_FORMS = dict(auto=0, fused=1, two_pass=2)                                  # HNR_RESIZE_AUTO .. HNR_RESIZE_TWO_PASS
 MVSNET_FEATURE_PACKED_ELEMS = 40248    # HNR_MVSNET_FEATURE_PACKED_ELEMS
 MVSNET_REG_PACKED_ELEMS = 298297       # HNR_MVSNET_REG_PACKED_ELEMS
 CNT = dict(RAYS_HIT=0, SAMPLES=1, RAYS_VALID=2, NEIGHBOURS=3, CELLS_VISITED=4, CANDIDATES=5, SAMPLES_VALID=6, SAMPLES_SMALL=7, SAMPLES_TINY=8)
@@ -288,6 +291,14 @@ SIGNATURES = {
     "hnr_path_item": (_I, [ctypes.POINTER(FrameBankC), _P, _I, _P, _I, _I, _I, _P, _I, _I, _I, ctypes.POINTER(_F), _I, ctypes.POINTER(FrameBatchOut), _P,
                            ctypes.c_int64, _P]),
     "hnr_frame_store": (_I, [_P, _P, _P, ctypes.c_int64, _I, _I, _P, _P, _P, _P]),
+    # raw frames to the bank's size: Pillow's resize, RGBA mode, compose (csrc/resize.hip)
+    "hnr_resize_coeffs": (_I, [_I, _I, _I, _P, _P, ctypes.c_int64]),
+    "hnr_resize_u8_scratch_bytes": (ctypes.c_int64, [_I, _I, _I, _I, _I, _I]),
+    "hnr_resize_u8_form": (_I, [_I, _I, _I, _I, _I, _I, _I]),
+    "hnr_resize_u8": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _P, _I, _P, _P, _I, _I, _P, ctypes.c_int64, _P]),
+    "hnr_rgba_premultiply": (_I, [_P, _P, ctypes.c_int64, _P]),
+    "hnr_rgba_unpremultiply": (_I, [_P, _P, ctypes.c_int64, _P]),
+    "hnr_rgba_compose": (_I, [_P, ctypes.c_int64, _P, _P, _P, _P, _P]),
     # depth supervision from resident depth frames: per-ray gt_depth, the loss term, the depth metrics row (csrc/depth_sup.hip)
     "hnr_frame_depth_rays": (_I, [ctypes.POINTER(DepthBankC), _P, _P, _P, _I, _P, _P]),
     "hnr_depth_loss": (_I, [_P, _P, _P, _I, _F, _P, _P, _P, _P, _P]),

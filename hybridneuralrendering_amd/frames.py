@@ -4,7 +4,8 @@ The reference builds a batch on the host, per step: data/scannet_ft_dataset.py:7
 and its nearest frames, draws pixel coordinates with numpy, builds `raydir` with get_dtu_raydir, gathers `gt_image` and uploads ~15 MB of float
 reference images.  A train split is 200 - 1000 frames of 480 x 640 x 3 bytes: it fits on the device as it is.  `FrameBank` holds it there,
 `BatchSampler.next()` writes the dataset item of the next step with at most three launches that read the frame number and the step counter from
-device memory -- no upload, no host read, capturable in a hipGraph.  Image decoding and resizing stay the caller's (once per scene).
+device memory -- no upload, no host read, capturable in a hipGraph.  Image decoding stays the caller's (once per scene); the resize to the bank's
+size -- Pillow's LANCZOS, the same bytes -- runs on the device: `FrameBank.from_raw`, `FrameBank.ingest`, `resize_frames` (csrc/resize.hip).
 A bank may also hold the split's sensor depth frames (`FrameBank(depth=...)`): the batch then carries `gt_depth` per ray, written by a fourth
 launch of the same kind (csrc/depth_sup.hip), for train.train_step(gt_depth=, w_depth=).
 
@@ -12,6 +13,7 @@ The nearest-view tables are per-frame constants and are computed on the host: `n
 tests/frames_ref.py restates the sampler's arithmetic in NumPy; the GPU results equal it bit for bit.
 """
 import ctypes
+import warnings
 
 import numpy as np
 import torch
@@ -84,6 +86,185 @@ def nearest_by_pose(query_c2w, query_intrinsic, query_ids, train_pos, train_dirs
             raise HnrError("nearest_by_pose: %d train cameras leave %d candidates, fewer than the %d views asked for" % (len(train_ids), len(idx2) - skip, V))
         rows.append(pick)
     return np.asarray(rows, dtype=np.int32).reshape(-1, V)
+
+
+# ---------------------------------------------------------------------------------------------------- raw frames to the bank's size (csrc/resize.hip)
+_TABLES, _DEV_TABLES = {}, {}
+
+
+def resize_tables(n_in, n_out, filter="lanczos"):
+    """hnr_resize_coeffs for one axis -> (ksize, bounds [n_out,2] int32, coef [n_out,ksize] int32), NumPy arrays on the host; Pillow's own integers
+    (tests/resize_ref.py).  Cached per (n_in, n_out, filter): a host function, no GPU is needed."""
+    if filter not in _lib.RESIZE_FILTERS:
+        raise HnrError("resize: filter must be one of %s, got %r (NEAREST is not a convolution filter and is not supported)" % (sorted(_lib.RESIZE_FILTERS), filter))
+    key = (int(n_in), int(n_out), _lib.RESIZE_FILTERS[filter])
+    t = _TABLES.get(key)
+    if t is None:
+        if key[0] < 1 or key[1] < 1:
+            raise HnrError("resize: sizes must be >= 1, got %d -> %d" % key[:2])
+        L = _lib.lib()
+        ksize = L.hnr_resize_coeffs(key[0], key[1], key[2], None, None, 0)
+        if ksize < 1:
+            raise HnrError("hnr_resize_coeffs failed (code %d): %s" % (ksize, L.hnr_last_error().decode("utf-8", "replace")))
+        bounds, coef = np.empty((key[1], 2), np.int32), np.empty((key[1], ksize), np.int32)
+        rc = L.hnr_resize_coeffs(key[0], key[1], key[2], bounds.ctypes.data_as(ctypes.c_void_p), coef.ctypes.data_as(ctypes.c_void_p), coef.size)
+        if rc != ksize:
+            raise HnrError("hnr_resize_coeffs failed (code %d): %s" % (rc, L.hnr_last_error().decode("utf-8", "replace")))
+        if len(_TABLES) > 64:
+            _TABLES.clear()
+        _TABLES[key] = t = (int(ksize), bounds, coef)
+    return t
+
+
+def _device_tables(n_in, n_out, filter, device):
+    """the tables of one axis on `device` (uploaded once per device and key): (ksize, bounds, coef)"""
+    ksize, bounds, coef = resize_tables(n_in, n_out, filter)
+    key = (str(device), int(n_in), int(n_out), filter)
+    t = _DEV_TABLES.get(key)
+    if t is None:
+        if len(_DEV_TABLES) > 64:
+            _DEV_TABLES.clear()
+        # (uploaded on whatever stream is current and read from any stream afterwards with no event: safe because .to() of pageable host
+        # memory returns only when the copy is done)
+        _DEV_TABLES[key] = t = (ksize, torch.from_numpy(bounds).to(device), torch.from_numpy(coef).to(device))
+    return t
+
+
+def _raw_frames(raw, what):
+    """[N,h,w,C] or [h,w,C] uint8, NumPy or torch, host or device -> (a torch tensor [N,h,w,C] where it is, whether a frame dimension was added)"""
+    t = raw
+    if isinstance(raw, np.ndarray):
+        with warnings.catch_warnings():                       # np.asarray(PIL image) is read-only; the tensor is only ever read
+            warnings.simplefilter("ignore", UserWarning)
+            t = torch.from_numpy(np.ascontiguousarray(raw))
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+        raise HnrError("%s: frames must be uint8 (NumPy or torch), got %s" % (what, getattr(raw, "dtype", type(raw).__name__)))
+    if t.dim() not in (3, 4):
+        raise HnrError("%s: frames must be [N,h,w,C] or [h,w,C], got %s" % (what, tuple(t.shape)))
+    single = t.dim() == 3
+    t = t[None] if single else t
+    if int(t.shape[3]) not in (1, 3, 4):
+        raise HnrError("%s: C must be 1, 3 or 4, got %d" % (what, int(t.shape[3])))
+    if min(int(s) for s in t.shape[:3]) < 1:
+        raise HnrError("%s: sizes must be >= 1, got %s" % (what, tuple(t.shape)))
+    return t, single
+
+
+def resize_form(raw_hw, size, channels=3, filter="lanczos"):
+    """Which form hnr_resize_u8 takes with form="auto" for frames of raw_hw = (h, w) -> size = (W, H): "fused" or "two_pass" (host only)."""
+    (h, w), (W, H) = (int(v) for v in raw_hw), (int(v) for v in size)
+    if min(h, w, H, W) < 1:
+        raise HnrError("resize_form: sizes must be >= 1")
+    kh = resize_tables(w, W, filter)[0] if w != W else 0
+    kv = resize_tables(h, H, filter)[0] if h != H else 0
+    rc = _lib.lib().hnr_resize_u8_form(h, w, int(channels), H, W, kh, kv)
+    if rc not in (1, 2):
+        raise HnrError("hnr_resize_u8_form failed (code %d): %s" % (rc, _lib.lib().hnr_last_error().decode("utf-8", "replace")))
+    return "fused" if rc == 1 else "two_pass"
+
+
+def resize_frames(raw, size, filter="lanczos", mode=None, out=None, form="auto", device=None):
+    """PIL.Image.resize(size, filter) of every frame, on the device, the same bytes (hnr_resize_u8; definitions in include/hnr.h, restated in
+    tests/resize_ref.py).  raw: [N,h,w,C] or [h,w,C] uint8, C = 1, 3 or 4, NumPy or torch, on the host (uploaded as it is) or on the device;
+    size = (W, H) as Pillow orders it; filter "box" | "bilinear" | "hamming" | "bicubic" | "lanczos".  mode="RGBA": what Pillow does to a
+    mode-RGBA image -- premultiply, resize, un-premultiply (the input is not modified); a same-size RGBA frame is a plain copy, as Pillow's.  Returns, or fills, a device uint8 tensor [N,H,W,C]
+    ([H,W,C] for one frame): `out` may be rows of a bank.  form "auto" | "fused" | "two_pass" (same bytes).  The device is raw's, else out's, else
+    `device`, else the current GPU.  Decoding (JPEG / PNG) stays the caller's; Pillow's box= and reducing_gap= are not covered."""
+    what = "resize_frames"
+    src, single = _raw_frames(raw, what)
+    try:
+        W, H = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise HnrError("%s: size must be (W, H), got %r" % (what, size))
+    if W < 1 or H < 1:
+        raise HnrError("%s: size must be >= 1, got %r" % (what, (W, H)))
+    if form not in _lib.RESIZE_FORMS:
+        raise HnrError("%s: form must be one of %s, got %r" % (what, sorted(_lib.RESIZE_FORMS), form))
+    N, h, w, C = (int(s) for s in src.shape)
+    if mode not in (None, "L", "RGB", "RGBA") or (mode is not None and len(mode) != C):
+        raise HnrError("%s: mode %r does not fit %d channels (None, 'L', 'RGB' or 'RGBA'; 'RGBA' needs four)" % (what, mode, C))
+    if filter not in _lib.RESIZE_FILTERS:
+        raise HnrError("%s: filter must be one of %s, got %r" % (what, sorted(_lib.RESIZE_FILTERS), filter))
+    if src.is_cuda:
+        dev = src.device
+    elif out is not None and isinstance(out, torch.Tensor):
+        dev = out.device
+    elif device is not None:
+        dev = torch.device(device)
+    else:
+        dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+    if dev.type != "cuda":
+        raise HnrError("%s: the device must be a GPU (the HIP path has no CPU fallback)" % what)
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.uint8 or not out.is_contiguous() or \
+                tuple(out.shape) not in ((N, H, W, C),) + (((H, W, C),) if N == 1 else ()):
+            raise HnrError("%s: out must be a contiguous uint8 tensor [%d,%d,%d,%d] on %s" % (what, N, H, W, C, dev))
+    else:
+        out = torch.empty((N, H, W, C), dtype=torch.uint8, device=dev)
+    L = _lib.lib()
+    own = not src.is_cuda
+    src = src.to(dev).contiguous()
+    kh, bh, ch = _device_tables(w, W, filter, dev) if w != W else (0, None, None)
+    kv, bv, cv = _device_tables(h, H, filter, dev) if h != H else (0, None, None)
+    with torch.cuda.device(dev):
+        rgba = mode == "RGBA" and (w != W or h != H)        # Image.resize returns a copy of a same-size image BEFORE it converts RGBA -> RGBa
+        if rgba:
+            pre = src if own else torch.empty_like(src)
+            _lib.check(L.hnr_rgba_premultiply(_lib.ptr(src), _lib.ptr(pre), N * h * w, _lib.stream()), "hnr_rgba_premultiply")
+            src = pre
+        scratch = None
+        if form == "two_pass" or (form == "auto" and L.hnr_resize_u8_form(h, w, C, H, W, kh, kv) == 2):
+            nbytes = int(L.hnr_resize_u8_scratch_bytes(N, h, w, C, H, W))
+            if nbytes < 0:
+                raise HnrError("hnr_resize_u8_scratch_bytes: %s" % L.hnr_last_error().decode("utf-8", "replace"))
+            scratch = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
+        _lib.check(L.hnr_resize_u8(_lib.ptr(src), N, h, w, C, _lib.ptr(out), H, W, _lib.ptr(bh), _lib.ptr(ch), kh, _lib.ptr(bv), _lib.ptr(cv), kv,
+                                   _lib.RESIZE_FORMS[form], _lib.ptr(scratch), 0 if scratch is None else int(scratch.numel()), _lib.stream()),
+                   "hnr_resize_u8")
+        if rgba:
+            _lib.check(L.hnr_rgba_unpremultiply(_lib.ptr(out), _lib.ptr(out), N * H * W, _lib.stream()), "hnr_rgba_unpremultiply")
+    mark_written([out])
+    return out[0] if single and out.dim() == 4 else out
+
+
+def compose_rgba(rgba8, white=True, black=False, alpha=True, mask=False):
+    """nerf_synth360_ft_dataset.py:532-536 on resized RGBA frames (hnr_rgba_compose): rgba8 [N,H,W,4] (or [H,W,4]) uint8 on the device -> a dict of
+    the float32 tensors asked for: "white" = c a + (1 - a) and "black" = c a [N,H,W,3] (what a FrameBank holds for a synthetic scene), "alpha" = a
+    and "mask" = (a > 0.1) [N,H,W] (what cloud_init.AlphaMasks / alpha_masking take), c, a = u8 / 255.  The bits of the torch expressions on the CPU."""
+    t, single = _raw_frames(rgba8, "compose_rgba")
+    if not t.is_cuda:
+        raise HnrError("compose_rgba: rgba8 must be on the GPU (the HIP path has no CPU fallback)")
+    if int(t.shape[3]) != 4:
+        raise HnrError("compose_rgba: rgba8 must have four channels, got %d" % int(t.shape[3]))
+    if not (white or black or alpha or mask):
+        raise HnrError("compose_rgba: no output asked for")
+    t = t.contiguous()
+    N, H, W = (int(s) for s in t.shape[:3])
+    f = lambda *s: torch.empty(s, dtype=torch.float32, device=t.device)
+    res = {}
+    if white:
+        res["white"] = f(N, H, W, 3)
+    if black:
+        res["black"] = f(N, H, W, 3)
+    if alpha:
+        res["alpha"] = f(N, H, W)
+    if mask:
+        res["mask"] = f(N, H, W)
+    with torch.cuda.device(t.device):
+        _lib.check(_lib.lib().hnr_rgba_compose(_lib.ptr(t), N * H * W, _lib.ptr(res.get("white")), _lib.ptr(res.get("black")), _lib.ptr(res.get("alpha")),
+                                               _lib.ptr(res.get("mask")), _lib.stream()), "hnr_rgba_compose")
+    return {k: v[0] for k, v in res.items()} if single else res
+
+
+def scaled_intrinsic(intrinsic_raw, raw_wh, wh):
+    """data/scannet_ft_dataset.py:178-179: the raw frames' intrinsic for frames resized from raw_wh = (w, h) to wh = (W, H) -- row 0 times W / w,
+    row 1 times H / h, the float32 array times a Python float.  [3,3] or [F,3,3]; the input is not modified."""
+    K = np.array(intrinsic_raw.detach().cpu() if isinstance(intrinsic_raw, torch.Tensor) else intrinsic_raw, dtype=np.float32)
+    if K.shape[-2:] != (3, 3) or K.ndim not in (2, 3):
+        raise HnrError("scaled_intrinsic: the intrinsic must be [3,3] or [F,3,3], got %s" % (K.shape,))
+    K[..., 0, :] *= (wh[0] / raw_wh[0])
+    K[..., 1, :] *= (wh[1] / raw_wh[1])
+    return K
 
 
 class FrameBank:
@@ -190,6 +371,68 @@ class FrameBank:
             raise HnrError("FrameBank.set_nearest: a nearest row is outside the reference bank (0 .. %d)" % (ref.F - 1))
         self.nearest = torch.from_numpy(np.ascontiguousarray(t, dtype=np.int32)).to(self.device)
         self.reference, self.V = ref, int(t.shape[1])
+        return self
+
+    @classmethod
+    def from_raw(cls, raw_images, c2w, intrinsic_raw, size, device, filter="lanczos", chunk=16, form="auto", **kwargs):
+        """A uint8 bank from the frames as decoded: what `Image.open(...).resize(size, Image.LANCZOS)` per frame and the scaling of the intrinsic
+        (scannet_ft_dataset.py:178-179, 742) give, with the resize on the device.  raw_images: [F,h,w,3] uint8 (NumPy or torch, host or device) or
+        a sequence of [h,w,3] frames of one size; size = (W, H); intrinsic_raw: the RAW frames' intrinsic, [3,3] or [F,3,3].  The bank's image
+        tensor is allocated once; the raw frames go through in chunks of `chunk` -- host -> device copy, then hnr_resize_u8 straight into the
+        bank's rows -- so the device never holds the raw set.  Everything else (ids, weights, depth, ...) is the constructor's."""
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise HnrError("FrameBank.from_raw: device must be a GPU (the HIP path has no CPU fallback)")
+        try:
+            W, H = (int(v) for v in size)
+        except (TypeError, ValueError):
+            raise HnrError("FrameBank.from_raw: size must be (W, H), got %r" % (size,))
+        chunk = int(chunk)
+        if W < 1 or H < 1 or chunk < 1:
+            raise HnrError("FrameBank.from_raw: size and chunk must be >= 1")
+        seq = isinstance(raw_images, (list, tuple))
+        F = len(raw_images) if seq else (int(raw_images.shape[0]) if getattr(raw_images, "ndim", 0) == 4 else 0)
+        if F < 1:
+            raise HnrError("FrameBank.from_raw: raw_images must be [F,h,w,3] or a non-empty sequence of [h,w,3] frames")
+        first = raw_images[0]
+        if getattr(first, "ndim", 0) != 3 or int(first.shape[2]) != 3:
+            raise HnrError("FrameBank.from_raw: frames must be [h,w,3], got %s" % (tuple(getattr(first, "shape", ())),))
+        h_raw, w_raw = int(first.shape[0]), int(first.shape[1])
+        K = scaled_intrinsic(intrinsic_raw, (w_raw, h_raw), (W, H))
+        images = torch.empty((F, H, W, 3), dtype=torch.uint8, device=dev)
+        for i in range(0, F, chunk):
+            part = raw_images[i:i + chunk]
+            if seq:
+                if len({tuple(p.shape) for p in part}) != 1:
+                    raise HnrError("FrameBank.from_raw: frames %d .. %d are not of one size" % (i, i + len(part) - 1))
+                part = torch.stack(list(part)) if isinstance(part[0], torch.Tensor) else np.stack([np.asarray(p) for p in part])
+            if tuple(part.shape[1:]) != (h_raw, w_raw, 3):
+                raise HnrError("FrameBank.from_raw: frames %d .. are %s, the first frame is %s" % (i, tuple(part.shape[1:]), (h_raw, w_raw, 3)))
+            resize_frames(part, (W, H), filter=filter, out=images[i:i + int(part.shape[0])], form=form, device=dev)
+        return cls(images, c2w, K, dev, **kwargs)
+
+    def ingest(self, rows, raw, filter="lanczos", form="auto"):
+        """Replaces rows of a uint8 bank with raw frames resized to the bank's size (a caller that decodes one frame at a time): rows an int or a
+        list of ints, raw [h,w,3] or [n,h,w,3] uint8, one frame per row.  The same kernels as from_raw; poses and intrinsics stay as they are."""
+        if self.images.dtype != torch.uint8:
+            raise HnrError("FrameBank.ingest: the bank holds float32 images; only a uint8 bank takes raw frames")
+        src, _ = _raw_frames(raw, "FrameBank.ingest")
+        rows = [int(r) for r in np.asarray(rows).reshape(-1)]
+        if len(rows) != int(src.shape[0]) or int(src.shape[3]) != 3:
+            raise HnrError("FrameBank.ingest: %d rows for frames of shape %s ([n,h,w,3], one per row)" % (len(rows), tuple(src.shape)))
+        if not rows:
+            raise HnrError("FrameBank.ingest: no rows given")
+        if min(rows) < 0 or max(rows) >= self.F:
+            raise HnrError("FrameBank.ingest: a row is outside the bank (0 .. %d)" % (self.F - 1))
+        if src.is_cuda and src.device != self.device:
+            raise HnrError("FrameBank.ingest: raw is on %s, the bank on %s" % (src.device, self.device))
+        i = 0
+        while i < len(rows):                                   # runs of consecutive rows go in one call
+            j = i + 1
+            while j < len(rows) and rows[j] == rows[j - 1] + 1:
+                j += 1
+            resize_frames(src[i:j], (self.W, self.H), filter=filter, out=self.images[rows[i]:rows[i] + (j - i)], form=form, device=self.device)
+            i = j
         return self
 
 

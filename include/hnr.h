@@ -28,7 +28,8 @@
  *              hnr_alpha_pack, hnr_visual_hull_select*, hnr_point_occlusion*, hnr_point_view_attrs_vis,
  *              hnr_frame_batch*, hnr_frame_item, hnr_ray_miss_rank, hnr_raft_flow*, hnr_blur_score_pair* (hnr_blur_edges and the other hnr_raft_*
  *              entries are STAGE), hnr_adam_plan, hnr_adam_step, hnr_frame_depth_rays, hnr_depth_loss, hnr_depth_metrics (and the HNR_DM_* row layout),
- *              hnr_ssim_loss, hnr_ssim_loss_scratch_bytes, hnr_pose_views, hnr_path_item, hnr_frame_store.
+ *              hnr_ssim_loss, hnr_ssim_loss_scratch_bytes, hnr_pose_views, hnr_path_item, hnr_frame_store,
+ *              hnr_resize_coeffs, hnr_resize_u8 (+ _scratch_bytes, _form), hnr_rgba_premultiply, hnr_rgba_unpremultiply, hnr_rgba_compose.
  *   STAGE   -- everything else (hnr_chain_*, hnr_mlp3_*, hnr_merge*, hnr_mixup_stage, hnr_proj_*, hnr_h2*, hnr_linear_*, hnr_gather_*, hnr_ksum*,
  *              hnr_segment_*, hnr_absmax, hnr_div_probe, hnr_image_features_bwd_bbox, the glue kernels of the training backward -- hnr_final_color_bwd*,
  *              hnr_ksum_bwd_rows8, hnr_extras_dgrad, hnr_point_small_grads, hnr_point_rows_bwd, hnr_dleaky_add, hnr_sum_views, hnr_unique_points*,
@@ -1170,6 +1171,65 @@ int hnr_path_item(const hnr_frame_bank *reference, const float *d_poses, int P, 
  * R = 0 only clears.  Replaces torch.zeros + index-put + a separate quantisation per frame. */
 int hnr_frame_store(const float *d_color, const float *d_pixel_idx, const float *d_depth, int64_t R, int h, int w, uint8_t *d_img8, float *d_image,
                     float *d_depth_image, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Raw frames to the bank's size (csrc/resize.hip): Pillow's convolution resize for 8-bit images, bit for bit.  Replaces the per-frame
+ * `Image.open(...).resize(self.img_wh, Image.LANCZOS)` of data/scannet_ft_dataset.py:742,824 and data/nerf_synth360_ft_dataset.py:531,762, decoding
+ * aside (that stays on the host), and the images of nerf_synth360_ft_dataset.py:532-536.  tests/resize_ref.py restates all of it in NumPy;
+ * tests/test_resize.py holds that text to PIL.Image.resize, the GPU tests hold the kernels to Pillow.  Not covered: Pillow's box= and reducing_gap=
+ * arguments, NEAREST, 16-bit and float images.
+ *
+ * hnr_resize_coeffs -- HOST function, no GPU call: the tables of one axis, `n_in` -> `n_out` elements, as Pillow's precompute_coeffs +
+ * normalize_coeffs_8bpc compute them (double arithmetic, libm):
+ *   S = 0.5 (box), 1 (bilinear), 1 (hamming), 2 (bicubic, a = -0.5), 3 (lanczos: sinc(x) sinc(x / 3) on -3 <= x < 3)
+ *   scale = n_in / n_out, fs = max(scale, 1), support = S fs, ksize = 2 ceil(support) + 1, ss = 1 / fs; for output xx:
+ *   centre = (xx + 0.5) scale, xmin = max((int)(centre - support + 0.5), 0), xmax = min((int)(centre + support + 0.5), n_in) - xmin,
+ *   w[x] = filter((x + xmin - centre + 0.5) ss) for x < xmax, divided by their sum in index order (when it is not 0),
+ *   coef[xx][x] = (int)(w 2^22 + 0.5) for w >= 0, (int)(w 2^22 - 0.5) otherwise; 0 for xmax <= x < ksize; bounds[xx] = (xmin, xmax).
+ * Returns ksize (> 0), or a negative error.  bounds = coef = NULL: only ksize (to size the tables); otherwise both, host memory, coef_elems >= n_out ksize. */
+#define HNR_RESIZE_BOX      0
+#define HNR_RESIZE_BILINEAR 1
+#define HNR_RESIZE_HAMMING  2
+#define HNR_RESIZE_BICUBIC  3
+#define HNR_RESIZE_LANCZOS  4
+int hnr_resize_coeffs(int n_in, int n_out, int filter, int32_t *bounds, int32_t *coef, int64_t coef_elems);
+
+/* hnr_resize_u8 -- N frames d_src [N,h,w,C] uint8 -> d_dst [N,H,W,C] uint8, C = 1, 3 or 4 (channels are independent).  d_src may start at any
+ * byte; d_dst may be rows of a larger bank.  Tables: d_bounds_h [W,2], d_coef_h [W,ksize_h] for the width, d_bounds_v [H,2], d_coef_v [H,ksize_v]
+ * for the height -- hnr_resize_coeffs' output copied to the device (bounds 8-byte aligned); those of an axis whose size does not change are not read.
+ *   pass     out = clip8((2^21 + sum_{x < xmax} in[xmin + x] coef[x]) >> 22): int32 sum, arithmetic shift, clamp to 0 .. 255
+ *   order    horizontal first when w != W, its result ROUNDED TO uint8; vertical on that when h != H; neither: a copy
+ *   form     HNR_RESIZE_FUSED: one launch, a workgroup per HNR_RESIZE_TILE_W x HNR_RESIZE_TILE_H output pixels, the input footprint and the uint8
+ *            intermediate of the tile in LDS (the intermediate never reaches memory); HNR_ERR_BADARG when a tile's footprint (static + dynamic LDS)
+ *            exceeds HNR_RESIZE_LDS_BUDGET bytes.  HNR_RESIZE_TWO_PASS: two launches through d_scratch [N,h,W,C], one lane per output byte.  Both give the
+ *            same bytes.  HNR_RESIZE_AUTO: fused when the footprint fits, else two-pass; hnr_resize_u8_form tells which (host only, from sizes).
+ *   scratch  hnr_resize_u8_scratch_bytes(...) bytes (0 unless both sizes change); read and written by the two-pass form only.
+ * Stream-ordered, nothing is allocated or read back; bounds from the tables are clamped, so bad tables cannot reach outside the buffers.
+ * Limits: 1 <= N <= 65535, h w and H W <= 2^26, N max(h, H) max(w, W) <= 2^36. */
+#define HNR_RESIZE_AUTO     0
+#define HNR_RESIZE_FUSED    1
+#define HNR_RESIZE_TWO_PASS 2
+#define HNR_RESIZE_TILE_W   64
+#define HNR_RESIZE_TILE_H   16
+#define HNR_RESIZE_LDS_BUDGET 65536
+int64_t hnr_resize_u8_scratch_bytes(int N, int h, int w, int C, int H, int W);
+int hnr_resize_u8_form(int h, int w, int C, int H, int W, int ksize_h, int ksize_v);
+int hnr_resize_u8(const uint8_t *d_src, int N, int h, int w, int C, uint8_t *d_dst, int H, int W, const int32_t *d_bounds_h, const int32_t *d_coef_h,
+                  int ksize_h, const int32_t *d_bounds_v, const int32_t *d_coef_v, int ksize_v, int form, void *d_scratch, int64_t scratch_bytes,
+                  void *stream);
+
+/* The two element-wise steps of Image.resize on a mode-RGBA image (RGBA -> RGBa, resize the four channels, RGBa -> RGBA), n_pixels x 4 bytes,
+ * in place (d_dst = d_src) or not, any byte alignment.  Pillow returns a copy of a SAME-SIZE image before the conversion: a caller skips both steps then
+ * (frames.resize_frames does), or colours under partial alpha change:
+ *   premultiply    c' = ((t >> 8) + t) >> 8, t = c a + 128; a kept
+ *   unpremultiply  c = c' when a is 0 or 255, else min(255 c' / a, 255) with integer division; a kept */
+int hnr_rgba_premultiply(const uint8_t *d_src, uint8_t *d_dst, int64_t n_pixels, void *stream);
+int hnr_rgba_unpremultiply(const uint8_t *d_src, uint8_t *d_dst, int64_t n_pixels, void *stream);
+
+/* hnr_rgba_compose -- nerf_synth360_ft_dataset.py:532-536 on resized RGBA frames d_rgba [n_pixels,4] uint8: with c, a = (float) u8 / 255.0f,
+ * d_black [n,3] = c a, d_white [n,3] = c a + (1 - a), d_alpha [n] = a, d_mask [n] = a > 0.1f ? 1 : 0, float32; any non-NULL subset.  Every operation
+ * is rounded on its own in the order divide, multiply, subtract, add: the bits of the torch expressions on the CPU. */
+int hnr_rgba_compose(const uint8_t *d_rgba, int64_t n_pixels, float *d_white, float *d_black, float *d_alpha, float *d_mask, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Depth supervision from resident sensor depth (csrc/depth_sup.hip): the per-ray ground-truth depth of a batch, the depth term of the training loss
