@@ -90,11 +90,19 @@ class TrainCloudGrads(ctypes.Structure):
     _fields_ = [("d_emb", _P), ("d_conf", _P), ("d_dir", _P), ("d_color", _P)]
 
 
+# hnr_train_weights in struct order (include/hnr.h): (field stem, the reference's PointAggregator layer -- a string: one pointer; a list: an array of them);
+# every stem is two fields, `_w` (the layers' .weight) and then `_b` (their .bias)
+_TRAIN_LAYERS = (("block1_0", "block1.0"), ("block1_2", "block1.2"), ("block3_0", "block3.0"), ("block3_2", "block3.2"), ("alpha", "alpha_branch.0"),
+                 ("cf", ["color_feature_branch.%d" % l for l in (0, 2, 4)]), ("mw", ["aux_merge_weight_block.%d" % l for l in (0, 2, 4, 6)]),
+                 ("mx", ["color_mixup_block.%d" % l for l in (0, 2, 4)]), ("fin", "color_final_block.0"),
+                 ("conv", ["aux_block_s%d.%d" % (s, l) for s in (1, 2, 3) for l in (0, 2)]))
+# (struct field, parameter name or list of parameter names), the one table train._SLOTS and torch_ops.TRAIN_WEIGHT_NAMES are read from
+TRAIN_WEIGHTS = tuple((stem + f, layer + p if isinstance(layer, str) else [l + p for l in layer]) for stem, layer in _TRAIN_LAYERS for f, p in (("_w", ".weight"), ("_b", ".bias")))
+
+
 class TrainWeights(ctypes.Structure):
     """hnr_train_weights: raw parameter pointers under the reference's names; the gradient block has the same layout."""
-    _fields_ = [(n, _P) for n in ("block1_0_w", "block1_0_b", "block1_2_w", "block1_2_b", "block3_0_w", "block3_0_b", "block3_2_w", "block3_2_b", "alpha_w", "alpha_b")] + \
-               [("cf_w", _P * 3), ("cf_b", _P * 3), ("mw_w", _P * 4), ("mw_b", _P * 4), ("mx_w", _P * 3), ("mx_b", _P * 3), ("fin_w", _P), ("fin_b", _P),
-                ("conv_w", _P * 6), ("conv_b", _P * 6)]
+    _fields_ = [(f, _P if isinstance(names, str) else _P * len(names)) for f, names in TRAIN_WEIGHTS]
 
 
 class TrainViews(ctypes.Structure):

@@ -12,7 +12,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _raycall
 from ._cache import Derived, tensor_key
 from ._lib import HnrError, CNT
 from . import querier as Q
@@ -313,20 +313,19 @@ class HybridRenderer:
           # memory guard (the per-layer path keeps 3360 B per neighbour row, the fused chain 296 B per neighbour SLOT + ~3 KB per sample):
           # a frame that cannot fit is refused with the remedy named instead of dying in the allocator
           need = (n_valid * 8 * 296 + n_valid * 6000) if fused else (n_rows * 3400 + n_valid * 6000)
-          free, _tot = torch.cuda.mem_get_info(dev)
-          cached = torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
-          if need > 0.9 * (free + cached):
+          avail = _raycall.available_bytes(dev)
+          if need > 0.9 * avail:
               raise HnrError("render_rays: this launch needs ~%.1f GB of workspace for %d valid samples / %d neighbour rows but only %.1f GB are "
-                             "free; render the frame in chunks (driver.render_image(chunk_rays=...), bench.py --chunk)" % (need / 1e9, n_valid, n_rows, (free + cached) / 1e9))
+                             "free; render the frame in chunks (driver.render_image(chunk_rays=...), bench.py --chunk)" % (need / 1e9, n_valid, n_rows, avail / 1e9))
+          w_out = c_out = None
+          if want_weights:
+              c_out = _raycall.empty_slot_conf(cloud, R, SR, K)
+              w_out = torch.zeros_like(c_out)
           if fused:
             # the fused chain: gather + geometry + PE -> operand image, then block1 -> block3 -> alpha + K-sums in one kernel
             ws = torch.empty((int(L.hnr_chain_workspace_bytes(n_valid)),), dtype=torch.uint8, device=dev)
             X5 = _f32((n_valid, 280), dev)
             sigma = _f32((n_valid,), dev)
-            w_out = c_out = None
-            if want_weights:
-                w_out = torch.zeros((R, SR, K), dtype=torch.float32, device=dev)
-                c_out = cloud.conf[0].clamp(0.0001, 1.0).expand(R, SR, K).contiguous()
             ptab = self.point_table(cloud)
             with T("chain_gather"):
               if parts is None:
@@ -352,11 +351,6 @@ class HybridRenderer:
             Xd = _f32((n_rows, 64), dev) if split else None      # PE5(dists6), 60 columns used
             row_pid = _i32(n_rows, dev) if split else None
             ptab = self.point_table(cloud) if split else None
-            w_out = c_out = None
-            if want_weights:
-                w_out = torch.zeros((R, SR, K), dtype=torch.float32, device=dev)
-                # empty slots read point 0 in the reference (index clamp, neural_points.py:711): same value here
-                c_out = cloud.conf[0].clamp(0.0001, 1.0).expand(R, SR, K).contiguous()
             _lib.check(L.hnr_gather_rows(p(cloud.xyz), p(cloud.emb), p(cloud.conf), p(cloud.dir), p(cloud.color), cloud.F,
                                          p(pidx), p(loc_w), p(raydir), p(campos), p(camrot), p(vs_item), p(vs_off), p(vs_cnt),
                                          p(counts), SR, K, n_valid, p(Xd) if split else p(A), 64 if split else 284, p(C), 264, p(wagg),
@@ -492,23 +486,11 @@ class HybridRenderer:
         opt, dev = self.opt, raydir.device
         R, SR, K = raydir.shape[0], int(opt.SR), int(opt.K)
         V = 0 if fm is None else int(fm.shape[0])
-        prm = _lib.RenderParams()
-        prm.R, prm.SR, prm.K, prm.D = R, SR, K, int(tmid.shape[-1])
-        prm.tmid_stride = 0 if tmid.dim() == 1 else int(tmid.shape[1])
-        for i in range(3):
-            prm.kernel_size[i] = int(opt.kernel_size[i])
-        prm.radius2, prm.vsize_z = float(radius2), float(np.float32(opt.vsize[2]))
-        prm.raydist_mode_unit, prm.V = int(getattr(opt, "raydist_mode_unit", 0) > 0), V
-        cap = R * SR
-        prm.cap_samples = cap
-        prm.knn_order = 1 if self.knn_order == "sorted" else 0
+        prm = _raycall.fill_params_opt(_lib.RenderParams(), opt, R, K, tmid, radius2, V, R * SR, 1 if self.knn_order == "sorted" else 0)
         nbytes = int(L.hnr_render_workspace_bytes(ctypes.byref(prm)))
-        free, _total = torch.cuda.mem_get_info(dev)
-        cached = torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
-        if nbytes > 0.6 * (free + cached):
+        if nbytes > 0.6 * _raycall.available_bytes(dev):
             return None                                   # the worst case does not fit: the staged path sizes its buffers exactly
-        ws = torch.empty((nbytes + 256,), dtype=torch.uint8, device=dev)
-        off = (-ws.data_ptr()) % 256
+        ws, ws_ptr = _raycall.workspace(nbytes, dev)
         pk, agg = self.agg.packed(), self.agg
         m3 = agg.packed_mlp3()
         ptab = self.point_table(cloud)
@@ -524,37 +506,27 @@ class HybridRenderer:
         if V > 0:
             vw = _lib.RenderViews(p(w2c_nearest), p(intrinsic_nearest), p(campos_nearest), p(fm), int(fm.shape[1]), int(fm.shape[2]),
                                   p(fw) if fw is not None else None, ctypes.c_void_p(fm_ready.cuda_event) if fm_ready is not None else None)
-        col, opa, isbg = _f32((R, 3), dev), _f32((R, SR), dev), _f32((R,), dev)
-        bw = _f32((R, SR), dev) if (want_weights or want_depth) else None
-        mask = torch.empty((R,), dtype=torch.int8, device=dev)
-        decoded = _f32((R, SR, 4), dev)
-        pidx = torch.empty((R, SR, K), dtype=torch.int32, device=dev)
-        loc = _f32((R, SR, 3), dev)
-        nsamp = torch.empty((R,), dtype=torch.int32, device=dev)
-        counts = torch.empty((_lib.NCOUNTS,), dtype=torch.int64, device=dev)
-        status = torch.empty((2,), dtype=torch.int32, device=dev)
-        w_out = c_out = None
+        # blend_weight only where it is read (weights, depth); weight / conf_coefficient pre-filled with what an empty slot holds, the library writes the rest
+        o = _raycall.RayOutputs.alloc(R, SR, K, dev, blend=want_weights or want_depth, weights=False)
         if want_weights:
-            w_out = torch.zeros((R, SR, K), dtype=torch.float32, device=dev)
-            c_out = cloud.conf[0].clamp(0.0001, 1.0).expand(R, SR, K).contiguous()     # empty slots read point 0 in the reference (:711)
+            o.t["conf_coefficient"] = _raycall.empty_slot_conf(cloud, R, SR, K)
+            o.t["weight"] = torch.zeros_like(o.t["conf_coefficient"])
         ev = None
         if timers is not None:
             ev = _lib.StageEvents()
             timers.setdefault("_stage_events", []).append(ev)
-        out = _lib.RenderOutputs(p(col), p(opa), p(isbg), p(bw) if bw is not None else None, p(mask), p(decoded), p(pidx), p(loc), p(nsamp), p(counts),
-                                 p(status), p(w_out) if w_out is not None else None, p(c_out) if c_out is not None else None,
-                                 ev.arr if ev is not None else None)
         with torch.cuda.device(dev):
             _lib.check(L.hnr_render_forward(grid.handle, ctypes.byref(prm), ctypes.byref(cl), ctypes.byref(wt), ctypes.byref(cam),
-                                            ctypes.byref(vw) if vw is not None else None, ctypes.c_void_p(ws.data_ptr() + off), nbytes,
-                                            ctypes.byref(out), _lib.stream()), "hnr_render_forward")
+                                            ctypes.byref(vw) if vw is not None else None, ws_ptr, nbytes,
+                                            ctypes.byref(o.struct(ev.arr if ev is not None else None)), _lib.stream()), "hnr_render_forward")
         self._keepalive = (ws, fw)             # the launches are asynchronous: the workspace must outlive them (next call replaces it)
-        res = dict(coarse_raycolor=col, coarse_point_opacity=opa, coarse_is_background=isbg, blend_weight=bw if want_weights else None, ray_mask=mask,
-                   decoded=decoded, sample_pidx=pidx, sample_loc_w=loc, ray_nsamp=nsamp, counts=counts, status=status)
-        if want_weights:
-            res.update(weight=w_out, conf_coefficient=c_out)
+        res = o.as_dict()
+        bw = res["blend_weight"]
+        if not want_weights:
+            res["blend_weight"] = None
+            del res["weight"], res["conf_coefficient"]
         if want_depth:
-            res["coarse_depth"] = ray_depth(bw, loc, nsamp, mask, campos, camrot)      # (the query outputs are un-padded: nsamp bounds the slots read)
+            res["coarse_depth"] = ray_depth(bw, res["sample_loc_w"], res["ray_nsamp"], res["ray_mask"], campos, camrot)      # (the query outputs are un-padded: nsamp bounds the slots read)
         return res
 
     @staticmethod
@@ -582,17 +554,9 @@ class HybridRenderer:
         coarse_is_background [R], ray_mask [R] i8, decoded [R,SR,4] + the query tensors.
         want_depth: also coarse_depth [R], the expected camera-space depth of every ray (ray_depth; 0 where ray_mask = 0) -- one more launch
         after the composite; every other output is what the call without it returns."""
-        g = _lib.require_gpu
-        raydir = g(raydir, "raydir", torch.float32).reshape(-1, 3)
-        campos = g(campos, "campos", torch.float32).reshape(3)
-        camrot = g(camrot, "camrotc2w", torch.float32).reshape(3, 3)
-        bg_color = g(bg_color, "bg_color", torch.float32).reshape(3)
-        c2w_nearest = g(c2w_nearest, "c2w_nearest", torch.float32).reshape(-1, 4, 4)
-        campos_nearest = g(campos_nearest, "campos_nearest", torch.float32).reshape(-1, 3)
-        intrinsic_nearest = g(intrinsic_nearest, "intrinsic_nearest", torch.float32).reshape(3, 3)
-        if w2c_nearest is None:
-            w2c_nearest = torch.inverse(c2w_nearest)          # 4x4 plumbing op (:250); V matrices per frame
-        w2c_nearest = w2c_nearest.contiguous()
+        # (images_nearest goes to feature_map as it came: the map is cached by that tensor)
+        raydir, campos, camrot, bg_color, _c2w, campos_nearest, intrinsic_nearest, _img, w2c_nearest, _fw = _raycall.ray_inputs(
+            raydir, campos, camrot, bg_color, c2w_nearest, campos_nearest, intrinsic_nearest, w2c_nearest=w2c_nearest)
         q = self.querier
         grid, hp = q._grid_for(cloud.xyz[None])
         tmid = q._tmid_for(float(near), float(far), self.opt.z_depth_dim, raydir.shape[0], raydir.device)

@@ -16,27 +16,15 @@ import numpy as np
 import torch
 
 from ._lib import HnrError
-from . import _lib
+from . import _lib, _raycall
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libhnr_torch.so")
 _loaded = False
 
-# hnr_train_weights in struct order (include/hnr.h): parameter names of the reference's PointAggregator
-TRAIN_WEIGHT_NAMES = (
-    ["block1.0.weight", "block1.0.bias", "block1.2.weight", "block1.2.bias", "block3.0.weight", "block3.0.bias", "block3.2.weight", "block3.2.bias",
-     "alpha_branch.0.weight", "alpha_branch.0.bias"]
-    + ["color_feature_branch.%d.weight" % l for l in (0, 2, 4)] + ["color_feature_branch.%d.bias" % l for l in (0, 2, 4)]
-    + ["aux_merge_weight_block.%d.weight" % l for l in (0, 2, 4, 6)] + ["aux_merge_weight_block.%d.bias" % l for l in (0, 2, 4, 6)]
-    + ["color_mixup_block.%d.weight" % l for l in (0, 2, 4)] + ["color_mixup_block.%d.bias" % l for l in (0, 2, 4)]
-    + ["color_final_block.0.weight", "color_final_block.0.bias"]
-    + ["aux_block_s%d.%d.weight" % (s, l) for s in (1, 2, 3) for l in (0, 2)] + ["aux_block_s%d.%d.bias" % (s, l) for s in (1, 2, 3) for l in (0, 2)])
-FORWARD_OUTPUTS = ("coarse_raycolor", "coarse_point_opacity", "coarse_is_background", "ray_mask", "decoded", "sample_pidx", "sample_loc_w", "ray_nsamp",
-                   "counts", "status")
-TRAIN_OUTPUTS = ("coarse_raycolor", "coarse_point_opacity", "coarse_is_background", "blend_weight", "ray_mask", "decoded", "sample_pidx", "sample_loc_w",
-                 "ray_nsamp", "counts", "status", "weight", "conf_coefficient")
-
-
+# hnr_train_weights in struct order (_lib.TRAIN_WEIGHTS): parameter names of the reference's PointAggregator; the ops' output lists (_raycall.RAY_OUTPUTS)
+TRAIN_WEIGHT_NAMES = [n for _f, names in _lib.TRAIN_WEIGHTS for n in ([names] if isinstance(names, str) else names)]
+FORWARD_OUTPUTS, TRAIN_OUTPUTS = _raycall.FORWARD_OUTPUTS, _raycall.TRAIN_OUTPUTS
 NCOUNTS = _lib.NCOUNTS
 
 
@@ -53,16 +41,11 @@ def _register_fakes():
     @torch.library.register_fake("hnr::render_forward")
     def _(grid, xyz, conf, dir, color, point_table, point_records, packed, campos, camrot, raydir, tmid, bg_color, w2c, intrinsic, campos_nearest, featmap,
           frame_w, SR, K, kernel_size, radius2, vsize_z, raydist_mode_unit, knn_order, slope, cap_samples):
-        R, e = raydir.shape[0], raydir.new_empty
-        return [e((R, 3), dtype=f32), e((R, SR), dtype=f32), e((R,), dtype=f32), e((R,), dtype=torch.int8), e((R, SR, 4), dtype=f32), e((R, SR, K), dtype=i32),
-                e((R, SR, 3), dtype=f32), e((R,), dtype=i32), e((NCOUNTS,), dtype=torch.int64), e((2,), dtype=i32)]
+        o = _raycall.RayOutputs.alloc(raydir.shape[0], SR, K, None, blend=False, weights=False, empty=raydir.new_empty)
+        return [o.t[k] for k in FORWARD_OUTPUTS]
 
     def train_outs(inputs, SR):
-        raydir = inputs[7]
-        R, K, e = raydir.shape[0], 8, raydir.new_empty
-        return [e((R, 3), dtype=f32), e((R, SR), dtype=f32), e((R,), dtype=f32), e((R, SR), dtype=f32), e((R,), dtype=torch.int8), e((R, SR, 4), dtype=f32),
-                e((R, SR, K), dtype=i32), e((R, SR, 3), dtype=f32), e((R,), dtype=i32), e((NCOUNTS,), dtype=torch.int64), e((2,), dtype=i32),
-                e((R, SR, K), dtype=f32), e((R, SR, K), dtype=f32)]
+        return list(_raycall.RayOutputs.alloc(inputs[7].shape[0], SR, 8, None, empty=inputs[7].new_empty).t.values())
 
     @torch.library.register_fake("hnr::render_train")
     def _(grid, inputs, weights, drop_lut, ray_drop, SR, kernel_size, radius2, vsize_z, raydist_mode_unit, knn_order, slope, cap_samples):
@@ -70,23 +53,12 @@ def _register_fakes():
 
     @torch.library.register_fake("hnr::render_train_fwd")
     def _(grid, inputs, weights, drop_lut, ray_drop, SR, kernel_size, radius2, vsize_z, raydist_mode_unit, knn_order, slope, cap_samples):
-        import ctypes
         raydir, tmid, img = inputs[7], inputs[8], inputs[13]
-        prm = _lib.TrainParams()                                # the workspace size is a host-side function of the shapes (no kernel runs)
-        prm.R, prm.SR, prm.K, prm.D = int(raydir.shape[0]), int(SR), 8, int(tmid.shape[-1])
-        prm.tmid_stride = 0 if tmid.dim() == 1 else int(tmid.shape[1])
-        if img is not None and img.numel() > 0:
-            prm.V, prm.H, prm.W = int(img.shape[0]), int(img.shape[1]), int(img.shape[2])
-        for i in range(3):
-            prm.kernel_size[i] = int(kernel_size[i])
-        prm.radius2, prm.vsize_z, prm.raydist_mode_unit = float(radius2), float(vsize_z), int(raydist_mode_unit)
-        prm.knn_order, prm.slope = int(knn_order), float(slope)
-        prm.n_points = int(inputs[0].shape[-2])
-        prm.cap_samples = int(cap_samples) if cap_samples > 0 else prm.R * prm.SR
-        nbytes = int(_lib.lib().hnr_render_train_workspace_bytes(ctypes.byref(prm)))
-        if nbytes < 0:
-            raise HnrError("hnr_render_train_workspace_bytes: %s" % _lib.lib().hnr_last_error().decode("utf-8", "replace"))
-        return train_outs(inputs, SR) + [raydir.new_empty((nbytes + 256,), dtype=torch.uint8)]
+        V, H, W = (int(img.shape[0]), int(img.shape[1]), int(img.shape[2])) if img is not None and img.numel() > 0 else (0, 0, 0)
+        # the workspace size is a host-side function of the shapes (no kernel runs)
+        prm = _raycall.fill_params(_lib.TrainParams(), raydir.shape[0], SR, 8, tmid, kernel_size, radius2, vsize_z, raydist_mode_unit, V, max(int(cap_samples), 0), knn_order)
+        prm.H, prm.W, prm.n_points, prm.slope = H, W, int(inputs[0].shape[-2]), float(slope)
+        return train_outs(inputs, SR) + [raydir.new_empty((_raycall.train_workspace_bytes(prm) + _raycall.WS_ALIGN,), dtype=torch.uint8)]
 
     @torch.library.register_fake("hnr::render_train_bwd")
     def _(inputs, weights, fwd, g_raycolor, g_conf_coefficient, SR, kernel_size, radius2, vsize_z, raydist_mode_unit, knn_order, slope, cap_samples):
@@ -190,26 +162,18 @@ def render_forward(renderer, cloud, raydir, campos, camrot, bg_color, near, far,
     opt, agg = renderer.opt, renderer.agg
     if getattr(cloud, "parts", None) is not None:
         raise _lib.HnrError("torch.ops.hnr.render_forward takes no Rw2c (per-point rotations of an edited scene); use HybridRenderer.render_rays")
-    g = _lib.require_gpu
-    raydir = g(raydir, "raydir", torch.float32).reshape(-1, 3)
-    campos, camrot, bg_color = g(campos, "campos", torch.float32).reshape(3), g(camrot, "camrotc2w", torch.float32).reshape(3, 3), g(bg_color, "bg_color", torch.float32).reshape(3)
+    views = getattr(opt, "use_nearest", 4) != 0
+    inp = _raycall.ray_inputs(raydir, campos, camrot, bg_color, c2w_nearest, campos_nearest, intrinsic_nearest, None, w2c_nearest, frame_weight, views=views)
     grid, hp = renderer.querier._grid_for(cloud.xyz[None])
-    tmid = renderer.querier._tmid_for(float(near), float(far), opt.z_depth_dim, raydir.shape[0], raydir.device)
-    fm = w2c = None
-    if getattr(opt, "use_nearest", 4) != 0:
-        fm = renderer.feature_map(images_nearest)
-        c2w = g(c2w_nearest, "c2w_nearest", torch.float32).reshape(-1, 4, 4)
-        w2c = (torch.inverse(c2w) if w2c_nearest is None else w2c_nearest).contiguous()
+    tmid = renderer.querier._tmid_for(float(near), float(far), opt.z_depth_dim, inp.raydir.shape[0], inp.raydir.device)
+    fm = renderer.feature_map(images_nearest) if views else None
     pk, m3 = agg.packed(), agg.packed_mlp3()
     packed = [agg.packed_chain(), m3["cf"].packed, m3["mw"].packed, m3["mx"].packed, pk["mw_last_w"], pk["mw_last_b"], pk["fin_w"], pk["fin_b"]]
     packed = [t if t.dtype == torch.float32 else t.view(torch.uint8) for t in packed]
     out = ops.render_forward(_handle(grid), cloud.xyz, cloud.conf, cloud.dir, cloud.color, renderer.point_table(cloud), renderer.point_records(cloud), packed,
-                             campos, camrot, raydir, tmid, bg_color, w2c,
-                             None if fm is None else g(intrinsic_nearest, "intrinsic_nearest", torch.float32).reshape(3, 3),
-                             None if fm is None else g(campos_nearest, "campos_nearest", torch.float32).reshape(-1, 3), fm,
-                             None if frame_weight is None else g(frame_weight, "frame_weight", torch.float32).reshape(-1),
-                             int(opt.SR), int(opt.K), [int(k) for k in opt.kernel_size], float(np.float32(hp[0] ** 2)), float(np.float32(opt.vsize[2])),
-                             int(getattr(opt, "raydist_mode_unit", 0) > 0), 1 if renderer.knn_order == "sorted" else 0, float(pk["slope"]), 0)
+                             inp.campos, inp.camrot, inp.raydir, tmid, inp.bg_color, inp.w2c, inp.intrinsic, inp.campos_nearest, fm, inp.frame_w,
+                             int(opt.SR), int(opt.K), [int(k) for k in opt.kernel_size], *_raycall.opt_scalars(opt, hp[0] ** 2),
+                             1 if renderer.knn_order == "sorted" else 0, float(pk["slope"]), 0)
     return dict(zip(FORWARD_OUTPUTS, out))
 
 
@@ -220,25 +184,15 @@ def render_train(renderer, aggregator, xyz, emb, conf, pdir, color, raydir, camp
     coarse_raycolor and conf_coefficient are attached to the autograd graph.  drop_lut: train.drop_lut(opt, R, device) for the patch-drop pattern."""
     ops = load()
     opt = renderer.opt
-    g = _lib.require_gpu
-    raydir = g(raydir, "raydir", torch.float32).reshape(-1, 3)
-    R = raydir.shape[0]
+    inp = _raycall.ray_inputs(raydir, campos, camrot, bg_color, c2w_nearest, campos_nearest, intrinsic_nearest, images_nearest, None, frame_weight_nearest,
+                              "frame_weight_nearest", views=getattr(opt, "use_nearest", 4) != 0)
     grid, hp = renderer.querier._grid_for(xyz.detach()[None] if xyz.dim() == 2 else xyz.detach())
     if tmid is None:
-        tmid = renderer.querier._tmid_for(float(near), float(far), opt.z_depth_dim, R, raydir.device)
-    views = getattr(opt, "use_nearest", 4) != 0
-    img = w2c = intr = camn = None
-    if views:
-        img = g(images_nearest, "images_nearest", torch.float32)
-        img = img[0] if img.dim() == 5 else img
-        w2c = torch.inverse(g(c2w_nearest, "c2w_nearest", torch.float32).reshape(-1, 4, 4)).contiguous()
-        intr, camn = g(intrinsic_nearest, "intrinsic_nearest", torch.float32).reshape(3, 3), g(campos_nearest, "campos_nearest", torch.float32).reshape(-1, 3)
-    inputs = [xyz.reshape(-1, 3), emb, conf, pdir, color, g(campos, "campos", torch.float32).reshape(3), g(camrot, "camrotc2w", torch.float32).reshape(3, 3), raydir,
-              g(tmid, "tmid", torch.float32), g(bg_color, "bg_color", torch.float32).reshape(3), w2c, intr, camn, img,
-              None if frame_weight_nearest is None else g(frame_weight_nearest, "frame_weight_nearest", torch.float32).reshape(-1)]
+        tmid = renderer.querier._tmid_for(float(near), float(far), opt.z_depth_dim, inp.raydir.shape[0], inp.raydir.device)
+    inputs = [xyz.reshape(-1, 3), emb, conf, pdir, color, inp.campos, inp.camrot, inp.raydir, _lib.require_gpu(tmid, "tmid", torch.float32), inp.bg_color,
+              inp.w2c, inp.intrinsic, inp.campos_nearest, inp.images, inp.frame_w]
     out = ops.render_train(_handle(grid), inputs, train_weight_list(aggregator), drop_lut, ray_drop, int(opt.SR), [int(k) for k in opt.kernel_size],
-                           float(np.float32(hp[0] ** 2)), float(np.float32(opt.vsize[2])), int(getattr(opt, "raydist_mode_unit", 0) > 0), 0,
-                           float(aggregator.block1[1].negative_slope), 0)
+                           *_raycall.opt_scalars(opt, hp[0] ** 2), 0, float(aggregator.block1[1].negative_slope), 0)
     return dict(zip(TRAIN_OUTPUTS, out))
 
 

@@ -19,7 +19,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _raycall
 from ._lib import HnrError
 from . import querier as Q
 from .render import _f32, PointCloud, ray_depth
@@ -75,25 +75,8 @@ def ray_drop_flags(opt, ray_mask):
     return (m & lut[row.clamp(min=0).long()]).to(torch.uint8).contiguous()
 
 
-# parameter name -> (field of hnr_train_weights, index or None)
-def _weight_slots():
-    slots = {}
-    for nm, fld in (("block1.0", "block1_0"), ("block1.2", "block1_2"), ("block3.0", "block3_0"), ("block3.2", "block3_2"), ("alpha_branch.0", "alpha"),
-                    ("color_final_block.0", "fin")):
-        slots[nm + ".weight"] = (fld + "_w", None)
-        slots[nm + ".bias"] = (fld + "_b", None)
-    for i, l in enumerate((0, 2, 4)):
-        slots["color_feature_branch.%d.weight" % l] = ("cf_w", i); slots["color_feature_branch.%d.bias" % l] = ("cf_b", i)
-        slots["color_mixup_block.%d.weight" % l] = ("mx_w", i); slots["color_mixup_block.%d.bias" % l] = ("mx_b", i)
-    for i, l in enumerate((0, 2, 4, 6)):
-        slots["aux_merge_weight_block.%d.weight" % l] = ("mw_w", i); slots["aux_merge_weight_block.%d.bias" % l] = ("mw_b", i)
-    for lvl in (1, 2, 3):
-        for j, l in enumerate((0, 2)):
-            slots["aux_block_s%d.%d.weight" % (lvl, l)] = ("conv_w", 2 * (lvl - 1) + j); slots["aux_block_s%d.%d.bias" % (lvl, l)] = ("conv_b", 2 * (lvl - 1) + j)
-    return slots
-
-
-_SLOTS = _weight_slots()
+# parameter name -> (field of hnr_train_weights, index or None), from the struct's table
+_SLOTS = {n: (f, i) for f, names in _lib.TRAIN_WEIGHTS for i, n in ([(None, names)] if isinstance(names, str) else enumerate(names))}
 
 
 def _fill_weights(tensors):
@@ -110,7 +93,23 @@ def _fill_weights(tensors):
 
 
 class _Saved:
-    pass
+    """One forward's state, as `out["_saved"]` of train_step and the second result of TrainPath.forward."""
+    __slots__ = (
+        "flat",             # all weight gradients of the step as ONE fp32 buffer (set by backward): one all-reduce when the batch is sharded over ranks
+        "flat_payload",     # number of floats of `flat` that hold gradients (a spare tail follows)
+        "prm",              # the step's hnr_train_params
+        "ws",               # the workspace tensor (uint8) with the kept activations; touched_points returns views into it
+        "ws_ptr",           # its 256-byte aligned void* as the library got it
+        "nbytes",           # hnr_render_train_workspace_bytes(prm)
+        "dev",              # the batch's device
+        "R", "SR", "K",     # rays, samples per ray, neighbours per sample
+        # what the backward passes on, and references that keep the memory behind the blocks' pointers alive until then
+        "V", "no_views", "wt", "weights", "cloud_t", "cl", "inp", "tmid", "cam", "vw", "out", "outs", "keep")
+
+    def __init__(self, **fields):
+        self.flat = self.flat_payload = None
+        for k, v in fields.items():
+            setattr(self, k, v)
 
 
 def _no_rotation(who, Rw2c, xyz):
@@ -146,16 +145,11 @@ class TrainPath:
         """w2c_nearest [V,4,4]: inverse(c2w_nearest) computed by the caller (torch.inverse may synchronise the host: a captured step passes it in).
         want_depth: the outputs also hold coarse_depth [R] (render.ray_depth over the padded query outputs and the blend weights; 0 where
         ray_mask = 0) -- one launch after the forward call; the backward takes its gradient (backward(g_depth=...))."""
-        L = _lib.lib()
+        L, p = _lib.lib(), _lib.ptr
         r, opt = self.r, self.opt
-        g, p = _lib.require_gpu, _lib.ptr
-        raydir = g(raydir, "raydir", torch.float32).reshape(-1, 3)
-        campos = g(campos, "campos", torch.float32).reshape(3)
-        camrot = g(camrot, "camrotc2w", torch.float32).reshape(3, 3)
-        bg_color = g(bg_color, "bg_color", torch.float32).reshape(3)
-        c2w_nearest = g(c2w_nearest, "c2w_nearest", torch.float32).reshape(-1, 4, 4)
-        campos_nearest = g(campos_nearest, "campos_nearest", torch.float32).reshape(-1, 3)
-        intrinsic_nearest = g(intrinsic_nearest, "intrinsic_nearest", torch.float32).reshape(3, 3)
+        inp = _raycall.ray_inputs(raydir, campos, camrot, bg_color, c2w_nearest, campos_nearest, intrinsic_nearest, images_nearest, w2c_nearest,
+                                  frame_weight, "frame_weight_nearest", invert=getattr(opt, "use_nearest", 4) != 0)
+        raydir, campos, img, fw = inp.raydir, inp.campos, inp.images, inp.frame_w
         dev = raydir.device
         if getattr(cloud, "parts", None) is not None:
             raise HnrError("TrainPath: the cloud carries Rw2c (per-point rotations of an edited scene), which the training path does not support")
@@ -167,67 +161,36 @@ class TrainPath:
         grid, hp = r.querier._grid_for(cloud.xyz[None])
         if tmid is None:
             tmid = r.querier._tmid_for(float(near), float(far), opt.z_depth_dim, R, dev)
-        tmid = g(tmid, "tmid", torch.float32)
+        tmid = _lib.require_gpu(tmid, "tmid", torch.float32)
         no_views = getattr(opt, "use_nearest", 4) == 0        # scene241.sh: image branch off, merged = 0 (point_aggregators.py:1257-1258)
-        img = g(images_nearest, "images_nearest", torch.float32)
-        if img.dim() == 5:
-            img = img[0]
         V, H, W = (0, 0, 0) if no_views else (int(img.shape[0]), int(img.shape[1]), int(img.shape[2]))
-        S = _Saved()
-        prm = _lib.TrainParams()
-        prm.R, prm.SR, prm.K, prm.D = R, SR, K, int(tmid.shape[-1])
-        prm.tmid_stride = 0 if tmid.dim() == 1 else int(tmid.shape[1])
-        for i in range(3):
-            prm.kernel_size[i] = int(opt.kernel_size[i])
-        prm.radius2, prm.vsize_z = float(np.float32(hp[0] ** 2)), float(np.float32(opt.vsize[2]))
-        prm.raydist_mode_unit = int(getattr(opt, "raydist_mode_unit", 0) > 0)
-        prm.V, prm.H, prm.W = V, H, W
-        prm.n_points = int(cloud.xyz.shape[0])
-        prm.cap_samples = int(self.cap_samples) if self.cap_samples else R * SR
-        prm.knn_order = 0
-        prm.slope = float(self.agg.block1[1].negative_slope)
-        nbytes = int(L.hnr_render_train_workspace_bytes(ctypes.byref(prm)))
-        if nbytes < 0:
-            raise HnrError("hnr_render_train_workspace_bytes: %s" % L.hnr_last_error().decode("utf-8", "replace"))
-        capturing = torch.cuda.is_current_stream_capturing()
-        free, _total = (1 << 62, 0) if capturing else torch.cuda.mem_get_info(dev)
-        cached = torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
-        if nbytes > 0.9 * (free + cached):
+        prm = _raycall.fill_params_opt(_lib.TrainParams(), opt, R, K, tmid, hp[0] ** 2, V, self.cap_samples, 0)
+        prm.H, prm.W, prm.n_points, prm.slope = H, W, int(cloud.xyz.shape[0]), float(self.agg.block1[1].negative_slope)
+        nbytes = _raycall.train_workspace_bytes(prm)
+        avail = _raycall.available_bytes(dev, capturing=torch.cuda.is_current_stream_capturing())
+        if nbytes > 0.9 * avail:
             raise HnrError("render_train: the workspace for %d rays x SR %d (%.1f GB) does not fit the %.1f GB that are free; set TrainPath.cap_samples to the "
-                           "number of valid shading samples a batch can produce" % (R, SR, nbytes / 1e9, (free + cached) / 1e9))
+                           "number of valid shading samples a batch can produce" % (R, SR, nbytes / 1e9, avail / 1e9))
+        ws, ws_ptr = _raycall.workspace(nbytes, dev, reuse=self.workspace)
         if self.reuse_outputs and self.workspace is None:
-            self.workspace = torch.empty((nbytes + 256,), dtype=torch.uint8, device=dev)     # (one step in flight at a time: the same workspace every step)
-        ws = self.workspace if (self.workspace is not None and self.workspace.numel() >= nbytes + 256) else torch.empty((nbytes + 256,), dtype=torch.uint8, device=dev)
-        off = (-ws.data_ptr()) % 256
+            self.workspace = ws                                  # (one step in flight at a time: the same workspace every step)
         # parameters as contiguous fp32 tensors under the reference's names (views of the nn.Parameters); the tensors and the ctypes block are kept
         # while the parameters stay where they are (an optimiser updates them in place): ~0.1 ms of Python per step otherwise
         pkey = tuple((n, q.data_ptr()) for n, q in self.agg.named_parameters() if n in _SLOTS)
         if self._wcache.get("key") != pkey:
-            wt = {n: g(q.detach(), n, torch.float32) for n, q in self.agg.named_parameters() if n in _SLOTS}
+            wt = {n: _lib.require_gpu(q.detach(), n, torch.float32) for n, q in self.agg.named_parameters() if n in _SLOTS}
             self._wcache = dict(key=pkey, wt=wt, weights=_fill_weights(wt))
-        wt = self._wcache["wt"]
-        S.wt, S.weights = wt, self._wcache["weights"]
-        S.cloud_t = (cloud.xyz, cloud.emb, cloud.conf, cloud.dir, cloud.color)
-        S.cl = _lib.TrainCloud(p(cloud.xyz), p(cloud.emb), p(cloud.conf), p(cloud.dir), p(cloud.color))
-        S.cam_t = (campos, camrot, raydir, tmid, bg_color)
-        S.cam = _lib.RenderCamera(p(campos), p(camrot), p(raydir), p(tmid), p(bg_color))
-        S.vw, S.vw_t = None, None
+        vw = None
         if V > 0:
-            if w2c_nearest is not None:
-                w2c = g(w2c_nearest, "w2c_nearest", torch.float32).reshape(-1, 4, 4)
-            else:
-                w2c = torch.inverse(c2w_nearest).contiguous()      # 4x4 plumbing op (neural_points_volumetric_model.py:250)
-            fw = None if frame_weight is None else g(frame_weight, "frame_weight_nearest", torch.float32).reshape(-1)
             if fw is not None and fw.numel() != V:
                 raise HnrError("frame_weight_nearest must hold one weight per reference view (%d), got %d values -- the item's scalar loss weight "
                                "`frame_weight` is a different input (train_step(frame_weight=...))" % (V, fw.numel()))
-            S.vw_t = (w2c, intrinsic_nearest, campos_nearest, img, fw)
-            S.vw = _lib.TrainViews(p(w2c), p(intrinsic_nearest), p(campos_nearest), p(img), p(fw) if fw is not None else None)
+            vw = _lib.TrainViews(p(inp.w2c), p(inp.intrinsic), p(inp.campos_nearest), p(img), p(fw))
         lut = flags = None
         mode = _drop_mode(opt)
         if ray_drop is not None:
             # explicit [R] flags (a rank's slice of the batch-wide drop pattern when the batch is sharded over GPUs)
-            flags = g(ray_drop, "ray_drop", torch.uint8).reshape(-1)
+            flags = _lib.require_gpu(ray_drop, "ray_drop", torch.uint8).reshape(-1)
         elif mode == "patch" and V > 0:
             key = (R, str(opt.dilation_setup), float(opt.drop_ratio), str(dev))
             if self._lut.get("key") != key:                      # (a host -> device copy: once per batch shape, never inside a captured step)
@@ -237,39 +200,28 @@ class TrainPath:
             # the random subset needs the ray mask first: one extra query launch (no host read), then explicit flags
             q0 = Q.march_query(grid, campos, raydir, tmid, SR, K, np.float32(hp[0] ** 2), opt.kernel_size, pad=True)
             flags = ray_drop_flags(opt, q0["ray_mask"])
+        # all thirteen outputs, uninitialised; under reuse_outputs the same tensors (and their block) for every step of this batch shape
         okey = ("fwd", R, SR, K, str(dev))
-        if self.reuse_outputs and okey in self._ocache:
-            col, opa, isbg, bw, mask, decoded, pidx, loc, nsamp, counts, status, w_out, c_out = self._ocache[okey]
-        else:
-            col, opa, isbg, bw = _f32((R, 3), dev), _f32((R, SR), dev), _f32((R,), dev), _f32((R, SR), dev)
-            mask = torch.empty((R,), dtype=torch.int8, device=dev)
-            decoded = _f32((R, SR, 4), dev)
-            pidx = torch.empty((R, SR, K), dtype=torch.int32, device=dev)
-            loc = _f32((R, SR, 3), dev)
-            nsamp = torch.empty((R,), dtype=torch.int32, device=dev)
-            counts = torch.empty((_lib.NCOUNTS,), dtype=torch.int64, device=dev)
-            status = torch.empty((2,), dtype=torch.int32, device=dev)
-            w_out, c_out = _f32((R, SR, K), dev), _f32((R, SR, K), dev)
+        o = self._ocache.get(okey) if self.reuse_outputs else None
+        if o is None:
+            o = _raycall.RayOutputs.alloc(R, SR, K, dev)
             if self.reuse_outputs:
-                self._ocache[okey] = (col, opa, isbg, bw, mask, decoded, pidx, loc, nsamp, counts, status, w_out, c_out)
-        S.out = _lib.RenderOutputs(p(col), p(opa), p(isbg), p(bw), p(mask), p(decoded), p(pidx), p(loc), p(nsamp), p(counts), p(status), p(w_out), p(c_out), None)
-        S.prm, S.ws, S.ws_ptr, S.nbytes, S.dev = prm, ws, ctypes.c_void_p(ws.data_ptr() + off), nbytes, dev
+                self._ocache[okey] = o
+        ev = None
         if self.timers is not None:
             ev = _lib.StageEvents(_lib.TRAIN_FWD_STAGES)
             self.timers.setdefault("fwd", []).append(ev)
-            S.out.stage_events = ev.arr
-        S.R, S.SR, S.K, S.V, S.no_views = R, SR, K, V, no_views
+        out = o.as_dict()
+        S = _Saved(prm=prm, ws=ws, ws_ptr=ws_ptr, nbytes=nbytes, dev=dev, R=R, SR=SR, K=K, V=V, no_views=no_views, wt=self._wcache["wt"],
+                   weights=self._wcache["weights"], cloud_t=(cloud.xyz, cloud.emb, cloud.conf, cloud.dir, cloud.color),
+                   cl=_lib.TrainCloud(p(cloud.xyz), p(cloud.emb), p(cloud.conf), p(cloud.dir), p(cloud.color)), inp=inp, tmid=tmid, cam=inp.camera(tmid),
+                   vw=vw, out=o.struct(ev.arr if ev is not None else None), outs=out, keep=(lut, flags, grid))
         with torch.cuda.device(dev):
             _lib.check(L.hnr_render_train_forward(grid.handle, ctypes.byref(prm), ctypes.byref(S.cl), ctypes.byref(S.weights), ctypes.byref(S.cam),
-                                                  ctypes.byref(S.vw) if S.vw is not None else None, p(lut) if lut is not None else None,
-                                                  p(flags) if flags is not None else None, S.ws_ptr, nbytes, ctypes.byref(S.out), _lib.stream()),
-                       "hnr_render_train_forward")
-        S.keep = (lut, flags, grid)
-        out = dict(coarse_raycolor=col, coarse_point_opacity=opa, coarse_is_background=isbg, blend_weight=bw, ray_mask=mask, decoded=decoded,
-                   sample_pidx=pidx, sample_loc_w=loc, ray_nsamp=nsamp, counts=counts, status=status, weight=w_out, conf_coefficient=c_out)
+                                                  ctypes.byref(vw) if vw is not None else None, p(lut), p(flags), ws_ptr, nbytes, ctypes.byref(S.out),
+                                                  _lib.stream()), "hnr_render_train_forward")
         if want_depth:
-            out["coarse_depth"] = ray_depth(bw, loc, None, mask, campos, camrot)
-        S.outs = out
+            out["coarse_depth"] = ray_depth(out["blend_weight"], out["sample_loc_w"], None, out["ray_mask"], campos, inp.camrot)
         self.last_step = (prm, nbytes)     # tools (bisect_train_forward.py): the step's parameter block and workspace size
         return out, S
 
@@ -328,18 +280,12 @@ class TrainPath:
             ev = _lib.StageEvents(_lib.TRAIN_BWD_STAGES)
             self.timers.setdefault("bwd", []).append(ev)
             S.out.stage_events = ev.arr
+        # hnr_render_train_backward_depth: the same call with the depth gradient behind the two others
+        name = "hnr_render_train_backward" if g_depth is None else "hnr_render_train_backward_depth"
         with torch.cuda.device(dev):
-            if g_depth is None:
-                _lib.check(L.hnr_render_train_backward(ctypes.byref(S.prm), ctypes.byref(S.cl), ctypes.byref(S.weights), ctypes.byref(S.cam),
-                                                       ctypes.byref(S.vw) if S.vw is not None else None, S.ws_ptr, S.nbytes, ctypes.byref(S.out), p(g_raycolor),
-                                                       p(g_conf_out) if g_conf_out is not None else None, ctypes.byref(cg), ctypes.byref(gw), _lib.stream()),
-                           "hnr_render_train_backward")
-            else:
-                _lib.check(L.hnr_render_train_backward_depth(ctypes.byref(S.prm), ctypes.byref(S.cl), ctypes.byref(S.weights), ctypes.byref(S.cam),
-                                                             ctypes.byref(S.vw) if S.vw is not None else None, S.ws_ptr, S.nbytes, ctypes.byref(S.out),
-                                                             p(g_raycolor), p(g_conf_out) if g_conf_out is not None else None, p(g_depth), ctypes.byref(cg),
-                                                             ctypes.byref(gw), _lib.stream()),
-                           "hnr_render_train_backward_depth")
+            _lib.check(getattr(L, name)(ctypes.byref(S.prm), ctypes.byref(S.cl), ctypes.byref(S.weights), ctypes.byref(S.cam),
+                                        ctypes.byref(S.vw) if S.vw is not None else None, S.ws_ptr, S.nbytes, ctypes.byref(S.out), p(g_raycolor), p(g_conf_out),
+                                        *(() if g_depth is None else (p(g_depth),)), ctypes.byref(cg), ctypes.byref(gw), _lib.stream()), name)
         return pg, ag
 
 

@@ -607,7 +607,7 @@ def test_workspace_carve_at_other_view_counts_stays_inside_its_bytes(V):
     """The canary arrangement of tests/test_render_forward_gpu.py::test_workspace_capacity_overflow_is_reported_not_overrun with the un-fused carve
     (V != 4: four more buffers): a workspace of exactly hnr_render_workspace_bytes bytes with 0xAB behind it, once with cap_samples = the number of
     valid samples (complete frame) and once 100 below it (overflow reported, nothing overrun)."""
-    from hybridneuralrendering_amd import _lib
+    from hybridneuralrendering_amd import _lib, _raycall
     d, ti, opt, cloud, rnd = _render_setup(V)
     vc, vd = _views_for(d, V, _dev())
     full = _render_v(rnd, cloud, ti, d, vd)
@@ -630,24 +630,15 @@ def test_workspace_carve_at_other_view_counts_stays_inside_its_bytes(V):
     cam = _lib.RenderCamera(p(campos), p(camrot), p(raydir), p(tmid), p(bg))
     vw = _lib.RenderViews(p(vd["w2c"]), p(vd["K"]), p(vd["campos_n"]), p(fm), int(fm.shape[1]), int(fm.shape[2]), None)
     for cap in (n_valid, n_valid - 100):
-        prm = _lib.RenderParams()
-        prm.R, prm.SR, prm.K, prm.D, prm.tmid_stride = R, SR, K, int(tmid.shape[-1]), 0
-        for i in range(3):
-            prm.kernel_size[i] = int(opt.kernel_size[i])
-        prm.radius2, prm.vsize_z, prm.raydist_mode_unit, prm.V, prm.cap_samples = float(np.float32(hp[0] ** 2)), float(np.float32(opt.vsize[2])), 1, V, cap
+        prm = _raycall.fill_params(_lib.RenderParams(), R, SR, K, tmid, opt.kernel_size, float(np.float32(hp[0] ** 2)), float(np.float32(opt.vsize[2])), 1, V, cap, 0)
+        assert prm.tmid_stride == 0 and prm.cap_samples == cap
         nbytes = int(L.hnr_render_workspace_bytes(ctypes.byref(prm)))
         guard = 4096
-        ws = torch.zeros((nbytes + 256 + guard,), dtype=torch.uint8, device=dev)
-        off = (-ws.data_ptr()) % 256
+        ws, ws_ptr = _raycall.workspace(nbytes + guard, dev)
+        off = ws_ptr.value - ws.data_ptr()
         ws[off + nbytes:] = 0xAB
-        f = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
-        col, opa, isbg, dec, loc = f(R, 3), f(R, SR), f(R), f(R, SR, 4), f(R, SR, 3)
-        mask = torch.empty((R,), dtype=torch.int8, device=dev)
-        pidx = torch.empty((R, SR, K), dtype=torch.int32, device=dev)
-        nsamp = torch.empty((R,), dtype=torch.int32, device=dev)
-        counts = torch.empty((_lib.NCOUNTS,), dtype=torch.int64, device=dev)
-        status = torch.empty((2,), dtype=torch.int32, device=dev)
-        o = _lib.RenderOutputs(p(col), p(opa), p(isbg), None, p(mask), p(dec), p(pidx), p(loc), p(nsamp), p(counts), p(status), None, None, None)
+        outs = _raycall.RayOutputs.alloc(R, SR, K, dev, blend=False, weights=False)
+        col, opa, counts, status, o = outs.t["coarse_raycolor"], outs.t["coarse_point_opacity"], outs.t["counts"], outs.t["status"], outs.struct()
         _lib.check(L.hnr_render_forward(grid.handle, ctypes.byref(prm), ctypes.byref(cl), ctypes.byref(wt), ctypes.byref(cam), ctypes.byref(vw),
                                         ctypes.c_void_p(ws.data_ptr() + off), nbytes, ctypes.byref(o), _lib.stream()), "hnr_render_forward")
         torch.cuda.synchronize()

@@ -57,7 +57,7 @@ def test_single_call_renders_the_reference_golden_and_equals_the_staged_path(tag
 
 
 def test_workspace_capacity_overflow_is_reported_not_overrun():
-    from hybridneuralrendering_amd import _lib
+    from hybridneuralrendering_amd import _lib, _raycall
     d, ti, opt, cloud, rnd = _setup("scannet_small")
     full = _render(rnd, cloud, ti, d)
     torch.cuda.synchronize()
@@ -71,15 +71,12 @@ def test_workspace_capacity_overflow_is_reported_not_overrun():
     tmid = rnd.querier._tmid_for(float(near), float(far), opt.z_depth_dim, R, dev)
     fm = rnd.feature_map(ti["images_nearest"][0])
     cap = n_valid - 100
-    prm = _lib.RenderParams()
-    prm.R, prm.SR, prm.K, prm.D, prm.tmid_stride = R, SR, K, int(tmid.shape[-1]), 0
-    for i in range(3):
-        prm.kernel_size[i] = int(opt.kernel_size[i])
-    prm.radius2, prm.vsize_z, prm.raydist_mode_unit, prm.V, prm.cap_samples = float(np.float32(hp[0] ** 2)), float(np.float32(opt.vsize[2])), 1, 4, cap
+    prm = _raycall.fill_params(_lib.RenderParams(), R, SR, K, tmid, opt.kernel_size, float(np.float32(hp[0] ** 2)), float(np.float32(opt.vsize[2])), 1, 4, cap, 0)
+    assert prm.tmid_stride == 0 and prm.cap_samples == cap
     nbytes = int(L.hnr_render_workspace_bytes(ctypes.byref(prm)))
     guard = 4096
-    ws = torch.zeros((nbytes + 256 + guard,), dtype=torch.uint8, device=dev)
-    off = (-ws.data_ptr()) % 256
+    ws, ws_ptr = _raycall.workspace(nbytes + guard, dev)
+    off = ws_ptr.value - ws.data_ptr()
     ws[off + nbytes:] = 0xAB
     pk, agg, m3, ptab = rnd.agg.packed(), rnd.agg, rnd.agg.packed_mlp3(), rnd.point_table(cloud)
     w2c = torch.inverse(ti["c2w_nearest"][0].cpu()).to(dev).contiguous()
@@ -88,14 +85,8 @@ def test_workspace_capacity_overflow_is_reported_not_overrun():
                             p(pk["mw_last_w"]), p(pk["mw_last_b"]), p(pk["fin_w"]), p(pk["fin_b"]), float(pk["slope"]))
     cam = _lib.RenderCamera(p(ti["campos"][0].contiguous()), p(ti["camrotc2w"][0].contiguous()), p(raydir), p(tmid), p(ti["bg_color"][0].contiguous()))
     vw = _lib.RenderViews(p(w2c), p(ti["intrinsic_nearest"][0].contiguous()), p(ti["campos_nearest"][0].contiguous()), p(fm), int(fm.shape[1]), int(fm.shape[2]), None)
-    f = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
-    col, opa, isbg, dec, loc = f(R, 3), f(R, SR), f(R), f(R, SR, 4), f(R, SR, 3)
-    mask = torch.empty((R,), dtype=torch.int8, device=dev)
-    pidx = torch.empty((R, SR, K), dtype=torch.int32, device=dev)
-    nsamp = torch.empty((R,), dtype=torch.int32, device=dev)
-    counts = torch.empty((_lib.NCOUNTS,), dtype=torch.int64, device=dev)
-    status = torch.empty((2,), dtype=torch.int32, device=dev)
-    out = _lib.RenderOutputs(p(col), p(opa), p(isbg), None, p(mask), p(dec), p(pidx), p(loc), p(nsamp), p(counts), p(status), None, None, None)
+    o = _raycall.RayOutputs.alloc(R, SR, K, dev, blend=False, weights=False)
+    col, counts, status, out = o.t["coarse_raycolor"], o.t["counts"], o.t["status"], o.struct()
     _lib.check(L.hnr_render_forward(grid.handle, ctypes.byref(prm), ctypes.byref(cl), ctypes.byref(wt), ctypes.byref(cam), ctypes.byref(vw),
                                     ctypes.c_void_p(ws.data_ptr() + off), nbytes, ctypes.byref(out), _lib.stream()), "hnr_render_forward")
     torch.cuda.synchronize()

@@ -5,7 +5,7 @@ import ctypes, os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
-from hybridneuralrendering_amd import scenes, _lib  # noqa: E402
+from hybridneuralrendering_amd import scenes, _lib, _raycall  # noqa: E402
 from hybridneuralrendering_amd.train import TrainPath, train_step  # noqa: E402
 
 sys.argv = [sys.argv[0]]
@@ -34,11 +34,11 @@ def step():
     return out
 out = step()                                                        # sizes the workspace
 prm_, nbytes = path.last_step
-path.workspace = torch.empty((nbytes + 256,), dtype=torch.uint8, device=dev)
+path.workspace, ws_ptr = _raycall.workspace(nbytes, dev)
 lay = (ctypes.c_int64 * 64)()
 n = _lib.lib().hnr_render_train_debug_layout(ctypes.byref(prm_), lay, 32)
 assert n == len(NAMES), n
-off0 = (-path.workspace.data_ptr()) % 256
+off0 = ws_ptr.value - path.workspace.data_ptr()
 reg = {NAMES[i]: (off0 + lay[2 * i], lay[2 * i + 1]) for i in range(n)}
 def snap():
     return {k: path.workspace[o:o + b].clone() for k, (o, b) in reg.items()}
