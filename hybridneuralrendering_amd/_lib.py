@@ -409,10 +409,13 @@ def lib():
     return L
 
 
+def last_error():
+    return lib().hnr_last_error().decode("utf-8", "replace")
+
+
 def check(rc, what):
     if rc != 0:
-        msg = lib().hnr_last_error().decode("utf-8", "replace")
-        raise HnrError("%s failed (code %d): %s" % (what, rc, msg))
+        raise HnrError("%s failed (code %d): %s" % (what, rc, last_error()))
 
 
 def ptr(t):
@@ -428,6 +431,83 @@ def ptr(t):
 
 def stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+class Strided:
+    """Marks a tensor argument of `call` that goes with a leading stride of its own (an lda/ldc operand): no contiguity check."""
+    __slots__ = ("t",)
+
+    def __init__(self, t):
+        self.t = t
+
+
+STREAM = object()        # written where the prototype has `void *stream`: the current stream of the call's device
+_INT_BITS = {ctypes.c_int: 31, ctypes.c_int64: 63}
+
+
+def _invoke(name, args, device=None):
+    """What the library function returns for `args`, translated as `call` documents, with the arguments' device current."""
+    fn = getattr(lib(), name, None) if name in SIGNATURES else None
+    if fn is None:
+        raise HnrError("libhnr_hip.so has no function %s" % name)
+    c, dev, at = list(args), None, -1
+    for i, a in enumerate(args):
+        if a is None or type(a) in (int, float):
+            continue
+        if a is STREAM:
+            at = i
+        elif isinstance(a, (torch.Tensor, Strided)):
+            t = a if isinstance(a, torch.Tensor) else a.t
+            if not t.is_cuda:
+                raise HnrError("%s: argument %d must be a tensor on the GPU, got device=%s" % (name, i, t.device))
+            if t is a and not t.is_contiguous():
+                raise HnrError("%s: argument %d must be a contiguous tensor (_lib.Strided marks one with a stride of its own)" % (name, i))
+            if dev is None:
+                dev = t.device
+            elif t.device != dev:
+                raise HnrError("%s: argument %d is on %s, the tensors before it on %s" % (name, i, t.device, dev))
+            c[i] = ctypes.c_void_p(t.data_ptr())
+        elif isinstance(a, ctypes.Structure):
+            c[i] = ctypes.byref(a)
+    if dev is None:
+        dev = device
+    if dev is None:
+        if at >= 0:
+            raise HnrError("%s: a stream needs a device: no tensor argument and no device=" % name)
+        return fn(*c)
+    with torch.cuda.device(dev):
+        if at >= 0:
+            c[at] = stream()
+        return fn(*c)
+
+
+def call(name, *args, device=None, ok=()):
+    """One call into the library; `args` stand one to one in the header's order.  A tensor becomes its device pointer (on the GPU and contiguous;
+    `Strided(t)` skips the contiguity check), a ctypes.Structure its byref, None is NULL, STREAM the current stream of the call's device, anything
+    else passes through.  The device is the one device of all tensor arguments (`device=` when there is none) and is current during the call.
+    Returns the status: 0, or one of `ok`; any other raises HnrError with the library's error text."""
+    rc = _invoke(name, args, device)
+    if rc not in ok:
+        check(rc, name)
+    return rc
+
+
+def size(name, *args, what=None):
+    """The value of an entry point that returns a size or a count, not a status (the `*_scratch_bytes`, `*_elems`, `*_packed_*` and
+    `*_workspace_bytes` families, hnr_adam_plan, hnr_resize_coeffs, hnr_resize_u8_form, hnr_chain_classes) as an int; arguments as in `call`.
+    A negative value (a shape the library refuses) and an int argument outside its C type's range raise HnrError(`what`, or a default text)."""
+    types = SIGNATURES[name][1] if name in SIGNATURES else ()
+    fits = all(-1 << _INT_BITS[t] <= a < 1 << _INT_BITS[t] for a, t in zip(args, types) if type(a) is int and t in _INT_BITS)
+    n = int(_invoke(name, args)) if fits else -1
+    if n < 0:
+        shown = ", ".join(repr(a) if isinstance(a, (int, float)) else type(a).__name__ for a in args)
+        raise HnrError(what or "%s(%s) refused: %s" % (name, shown, last_error() if fits else "an argument is outside its C type's range"))
+    return n
+
+
+def scratch(name, *args, device, dtype=torch.uint8, what=None):
+    """A fresh tensor of `size(name, *args)` elements of `dtype` on `device`."""
+    return torch.empty((size(name, *args, what=what),), dtype=dtype, device=device)
 
 
 def require_gpu(t, name, dtype=None):

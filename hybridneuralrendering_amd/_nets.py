@@ -19,11 +19,6 @@ def host_f32(t):
     return t.detach().float().cpu()
 
 
-def same_device(what, *ts):
-    if any(t.device != ts[0].device for t in ts):
-        raise HnrError("%s: every tensor must be on the same device" % what)
-
-
 class NormParams(nn.Module):
     """Parameter holder with the names of nn.BatchNorm and InPlaceABN; the arithmetic lives in the convolution kernels' epilogue or is folded into the
     packed weights (each net's pack_host)."""

@@ -49,7 +49,6 @@ class DepthFusion:
     def __init__(self, capacity, device, intrinsic, frame_vox_res=100, depth_div=1000., depth_min=0.3, depth_max=8.0):
         if int(capacity) < 1:
             raise HnrError("DepthFusion: capacity must be at least 1")
-        self.L = _lib.lib()
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise HnrError("DepthFusion: device must be a GPU (the HIP path has no CPU fallback)")
@@ -81,15 +80,11 @@ class DepthFusion:
         depth = depth.to(self.device).contiguous()
         H, W = int(depth.shape[0]), int(depth.shape[1])
         if self._shape != (H, W):
-            nbytes = int(self.L.hnr_depth_fuse_scratch_bytes(H, W))
-            if nbytes < 0:
-                raise HnrError("DepthFusion.add: unsupported frame size %dx%d" % (H, W))
-            self._scratch, self._shape = torch.empty((nbytes,), dtype=torch.uint8, device=self.device), (H, W)
+            self._scratch = _lib.scratch("hnr_depth_fuse_scratch_bytes", H, W, device=self.device, what="DepthFusion.add: unsupported frame size %dx%d" % (H, W))
+            self._shape = (H, W)
         M = _host_f32(c2w, (4, 4), "c2w")
-        with torch.cuda.device(self.device):
-            _lib.check(self.L.hnr_depth_fuse_frame(_lib.ptr(depth), u16, H, W, _cf(self.Ki), _cf(M), self.depth_div, self.depth_min, self.depth_max,
-                                                   self.frame_vox_res, _lib.ptr(self.cloud), self.capacity, _lib.ptr(self.count), _lib.ptr(self.status),
-                                                   _lib.ptr(self._scratch), int(self._scratch.numel()), _lib.stream()), "hnr_depth_fuse_frame")
+        _lib.call("hnr_depth_fuse_frame", depth, u16, H, W, _cf(self.Ki), _cf(M), self.depth_div, self.depth_min, self.depth_max, self.frame_vox_res,
+                  self.cloud, self.capacity, self.count, self.status, self._scratch, int(self._scratch.numel()), _lib.STREAM)
         self.frames += 1
         return self
 
@@ -103,7 +98,6 @@ class DepthFusion:
 def range_crop(xyz, ranges, count=None):
     """xyz [n,3] -> (buffer [n,3], device count [1] int64): the points with ranges[:3] <= p <= ranges[3:], in order (train_ft.py:713-716).
     `count` (device int64 [1]) limits the input to xyz[:count] without a host read.  ranges[0] <= -99 keeps everything."""
-    L = _lib.lib()
     xyz = _lib.require_gpu(xyz, "xyz", torch.float32)
     n, dev = int(xyz.shape[0]), xyz.device
     out = torch.empty_like(xyz)
@@ -113,19 +107,13 @@ def range_crop(xyz, ranges, count=None):
     if count is None:
         count = torch.full((1,), n, dtype=torch.int64, device=dev)
     r = _host_f32(ranges, (6,), "ranges")
-    nbytes = int(L.hnr_range_crop_scratch_bytes(n))
-    if nbytes < 0:
-        raise HnrError("range_crop: too many points (%d)" % n)
-    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(L.hnr_range_crop(_lib.ptr(xyz), _lib.ptr(count), n, _cf(r), _lib.ptr(out), _lib.ptr(n_out), _lib.ptr(scratch), nbytes, _lib.stream()),
-                   "hnr_range_crop")
+    scratch = _lib.scratch("hnr_range_crop_scratch_bytes", n, device=dev, what="range_crop: too many points (%d)" % n)
+    _lib.call("hnr_range_crop", xyz, count, n, _cf(r), out, n_out, scratch, scratch.numel(), _lib.STREAM)
     return out, n_out
 
 
 def nearest_view_ids(campos, raydir, xyz):
     """int32 [N]: the camera of every point (hnr_nearest_view)."""
-    L = _lib.lib()
     xyz = _lib.require_gpu(xyz, "xyz", torch.float32).reshape(-1, 3)
     campos = _lib.require_gpu(campos, "campos", torch.float32).reshape(-1, 3)
     raydir = _lib.require_gpu(raydir, "raydir", torch.float32).reshape(-1, 3)
@@ -133,9 +121,7 @@ def nearest_view_ids(campos, raydir, xyz):
         raise HnrError("nearest_view: campos and raydir must both be [M,3], M > 0")
     out = torch.empty((xyz.shape[0],), dtype=torch.int32, device=xyz.device)
     if xyz.shape[0] > 0:
-        with torch.cuda.device(xyz.device):
-            _lib.check(L.hnr_nearest_view(_lib.ptr(xyz), int(xyz.shape[0]), _lib.ptr(campos), _lib.ptr(raydir), int(campos.shape[0]), _lib.ptr(out),
-                                          _lib.stream()), "hnr_nearest_view")
+        _lib.call("hnr_nearest_view", xyz, int(xyz.shape[0]), campos, raydir, int(campos.shape[0]), out, _lib.STREAM)
     return out
 
 
@@ -153,7 +139,6 @@ def cam_pos_cam(c2w, w2c):
 def point_view_attrs(xyz, w2c, c2w, cpc, intrinsic, H, W, feat=None, want_dir=True, want_mask=True, visible=None):
     """hnr_point_view_attrs: (features [n,C] or None, dir [n,3] or None, mask [n] uint8 or None) of world points seen from one view.
     visible [n] uint8 (point_occlusion's flags, hnr_point_view_attrs_vis): where it is 0 the point counts as outside the frame."""
-    L = _lib.lib()
     xyz = _lib.require_gpu(xyz, "xyz", torch.float32).reshape(-1, 3)
     n, dev = int(xyz.shape[0]), xyz.device
     C = Hl = Wl = 0
@@ -172,14 +157,11 @@ def point_view_attrs(xyz, w2c, c2w, cpc, intrinsic, H, W, feat=None, want_dir=Tr
             raise HnrError("point_view_attrs: visible must hold one flag per point, on xyz's device")
     if n > 0:
         a = [_host_f32(w2c, (4, 4), "w2c"), _host_f32(c2w, (4, 4), "c2w"), _host_f32(cpc, (3,), "cam_pos_cam"), _host_f32(intrinsic, (3, 3), "intrinsic")]
-        with torch.cuda.device(dev):
-            if visible is not None:
-                _lib.check(L.hnr_point_view_attrs_vis(_lib.ptr(xyz), n, _cf(a[0]), _cf(a[1]), _cf(a[2]), _cf(a[3]), int(H), int(W), _lib.ptr(feat), C, Hl, Wl,
-                                                      _lib.ptr(visible), _lib.ptr(out_f), _lib.ptr(out_d), _lib.ptr(out_m), _lib.stream()),
-                           "hnr_point_view_attrs_vis")
-                return out_f, out_d, out_m
-            _lib.check(L.hnr_point_view_attrs(_lib.ptr(xyz), n, _cf(a[0]), _cf(a[1]), _cf(a[2]), _cf(a[3]), int(H), int(W), _lib.ptr(feat), C, Hl, Wl,
-                                              _lib.ptr(out_f), _lib.ptr(out_d), _lib.ptr(out_m), _lib.stream()), "hnr_point_view_attrs")
+        head = (xyz, n, _cf(a[0]), _cf(a[1]), _cf(a[2]), _cf(a[3]), int(H), int(W), feat, C, Hl, Wl)
+        if visible is not None:
+            _lib.call("hnr_point_view_attrs_vis", *head, visible, out_f, out_d, out_m, _lib.STREAM)
+        else:
+            _lib.call("hnr_point_view_attrs", *head, out_f, out_d, out_m, _lib.STREAM)
     return out_f, out_d, out_m
 
 
@@ -216,29 +198,23 @@ def query_point_attributes(xyz, image_chw, c2w, w2c, intrinsic, feature_maps=Non
 def point_occlusion(xyz, w2c, intrinsic, H, W, tolerate=0.1):
     """hnr_point_occlusion: uint8 [n], 1 where a world point is inside the H x W frame of the view (w2c, intrinsic) and at most `tolerate` behind the
     nearest point of its pixel cell -- the mask `homo_warp_nongrid_occ` returns (mvs_utils.py:333-369) for the points of one view."""
-    L = _lib.lib()
     xyz = _lib.require_gpu(xyz, "xyz", torch.float32).reshape(-1, 3)
     n, dev = int(xyz.shape[0]), xyz.device
     vis = torch.empty((n,), dtype=torch.uint8, device=dev)
     if n == 0:
         return vis
     H, W = int(H), int(W)
-    nbytes = int(L.hnr_point_occlusion_scratch_bytes(H, W)) if max(H, W) < 2 ** 31 else -1
-    if nbytes < 0:
-        raise HnrError("point_occlusion: unsupported frame %dx%d (2 <= H, W <= 32768, H*W <= 2^24)" % (H, W))
+    scratch = _lib.scratch("hnr_point_occlusion_scratch_bytes", H, W, device=dev,
+                           what="point_occlusion: unsupported frame %dx%d (2 <= H, W <= 32768, H*W <= 2^24)" % (H, W))
     if not float(tolerate) >= 0.0:
         raise HnrError("point_occlusion: tolerate must not be negative")
-    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
     E, K = _host_f32(w2c, (4, 4), "w2c"), _host_f32(intrinsic, (3, 3), "intrinsic")
-    with torch.cuda.device(dev):
-        _lib.check(L.hnr_point_occlusion(_lib.ptr(xyz), n, _cf(E), _cf(K), H, W, float(tolerate), _lib.ptr(vis), _lib.ptr(scratch), nbytes, _lib.stream()),
-                   "hnr_point_occlusion")
+    _lib.call("hnr_point_occlusion", xyz, n, _cf(E), _cf(K), H, W, float(tolerate), vis, scratch, scratch.numel(), _lib.STREAM)
     return vis
 
 
 def alpha_pack(alphas):
     """hnr_alpha_pack: alphas [M,H,W] fp32 on the GPU -> int32 [M,H,(W+31)//32], one bit per pixel (alpha > 0.1), as uint32 bit patterns."""
-    L = _lib.lib()
     alphas = _lib.require_gpu(alphas, "alphas", torch.float32)
     if alphas.dim() != 3 or alphas.numel() == 0:
         raise HnrError("alpha_pack: alphas must be [M,H,W], got %s" % (tuple(alphas.shape),))
@@ -246,8 +222,7 @@ def alpha_pack(alphas):
     if M > 65535 or H > 32768 or W > 32768:
         raise HnrError("alpha_pack: alphas %s outside M <= 65535, H, W <= 32768" % (tuple(alphas.shape),))
     bits = torch.empty((M, H, (W + 31) // 32), dtype=torch.int32, device=alphas.device)
-    with torch.cuda.device(alphas.device):
-        _lib.check(L.hnr_alpha_pack(_lib.ptr(alphas), M, H, W, _lib.ptr(bits), _lib.stream()), "hnr_alpha_pack")
+    _lib.call("hnr_alpha_pack", alphas, M, H, W, bits, _lib.STREAM)
     return bits
 
 
@@ -316,7 +291,6 @@ def visual_hull_select(xyz, masks, near_far=None, range_mask=False, conf=None, v
     """hnr_visual_hull_select.  xyz [n,3] (n > 0) on the GPU, masks: an AlphaMasks there; near_far: (near, far) or None; conf [n] fp32 / view [n] int32:
     carried along.  Returns dict(mask [n] uint8 or None, xyz [cap,3], conf [cap] or None, view [cap] or None, count [1] int64, status [1] int32 -- all on
     the device -- and capacity).  Nothing is read back.  capacity None: n rows, which cannot overflow; compact=False: the mask alone."""
-    L = _lib.lib()
     xyz = _lib.require_gpu(xyz, "xyz", torch.float32).reshape(-1, 3)
     n, dev = int(xyz.shape[0]), xyz.device
     if not isinstance(masks, AlphaMasks) or masks.device != dev:
@@ -337,15 +311,10 @@ def visual_hull_select(xyz, masks, near_far=None, range_mask=False, conf=None, v
     out = dict(mask=e((n,), torch.uint8) if want_mask else None, xyz=e((rows, 3), torch.float32) if compact else None,
                conf=e((rows,), torch.float32) if compact and conf is not None else None, view=e((rows,), torch.int32) if compact and view is not None else None,
                count=torch.zeros((1,), dtype=torch.int64, device=dev), status=torch.zeros((1,), dtype=torch.int32, device=dev), capacity=cap)
-    nbytes = int(L.hnr_visual_hull_select_scratch_bytes(n))
-    if nbytes < 0:
-        raise HnrError("visual_hull_select: too many points (%d)" % n)
-    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(L.hnr_visual_hull_select(_lib.ptr(xyz), _lib.ptr(conf), _lib.ptr(view), n, _lib.ptr(masks.bits), _lib.ptr(masks.cams), masks.M, masks.H,
-                                            masks.W, None if nf is None else _cf(nf), 1 if range_mask else 0, _lib.ptr(out["mask"]), _lib.ptr(out["xyz"]),
-                                            _lib.ptr(out["conf"]), _lib.ptr(out["view"]), cap, _lib.ptr(out["count"]), _lib.ptr(out["status"]),
-                                            _lib.ptr(scratch), nbytes, _lib.stream()), "hnr_visual_hull_select")
+    scratch = _lib.scratch("hnr_visual_hull_select_scratch_bytes", n, device=dev, what="visual_hull_select: too many points (%d)" % n)
+    _lib.call("hnr_visual_hull_select", xyz, conf, view, n, masks.bits, masks.cams, masks.M, masks.H, masks.W, None if nf is None else _cf(nf),
+              1 if range_mask else 0, out["mask"], out["xyz"], out["conf"], out["view"], cap, out["count"], out["status"], scratch, scratch.numel(),
+              _lib.STREAM)
     return out
 
 
@@ -376,15 +345,12 @@ def point_conf(n, default_conf, device):
 def group_by_view(view_ids):
     """Stable grouping (hnr_sort_rows_by_key): (perm [N] int64, sorted ids [N] int32) -- ascending view id, the original order inside a view
     (train_ft.py:741-743: one boolean-mask pass per used view)."""
-    L = _lib.lib()
     keys = _lib.require_gpu(view_ids, "view_ids", torch.int32).reshape(-1)
     n, dev = int(keys.shape[0]), keys.device
     ks, perm = torch.empty_like(keys), torch.empty_like(keys)
     if n > 0:
-        nbytes = int(L.hnr_sort_rows_scratch_bytes(n))
-        scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.hnr_sort_rows_by_key(_lib.ptr(keys), n, _lib.ptr(ks), _lib.ptr(perm), _lib.ptr(scratch), nbytes, _lib.stream()), "hnr_sort_rows_by_key")
+        scratch = _lib.scratch("hnr_sort_rows_scratch_bytes", n, device=dev)
+        _lib.call("hnr_sort_rows_by_key", keys, n, ks, perm, scratch, scratch.numel(), _lib.STREAM)
     return perm.long(), ks
 
 

@@ -173,7 +173,6 @@ def render_path(renderer, cloud, sampler, frames=None, depth=False, chunk_rays=0
             raise HnrError("render_path: frames must be a non-empty list of frame numbers 0 .. %d" % (sampler.P - 1))
     n = sampler.P if frames is None else len(frames)
     dev, h, w = sampler.bank.device, sampler.bank.H, sampler.bank.W
-    L = _lib.lib()
     clip8 = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
     clipd = torch.empty((n, h, w), dtype=torch.float32, device=dev) if depth else None
     clipf = torch.empty((n, h, w, 3), dtype=torch.float32, device=dev) if keep_float else None
@@ -184,8 +183,6 @@ def render_path(renderer, cloud, sampler, frames=None, depth=False, chunk_rays=0
         col = rows[:, :3].contiguous()
         d = rows[:, 4].contiguous() if depth else None
         hits[k] = rows[:, 3].sum().to(torch.int64)
-        with torch.cuda.device(dev):
-            _lib.check(L.hnr_frame_store(_lib.ptr(col), _lib.ptr(pix.contiguous()), _lib.ptr(d), int(col.shape[0]), h, w, _lib.ptr(clip8[k]),
-                                         _lib.ptr(clipf[k]) if keep_float else None, _lib.ptr(clipd[k]) if depth else None, _lib.stream()),
-                       "hnr_frame_store")
+        _lib.call("hnr_frame_store", col, pix.contiguous(), d, int(col.shape[0]), h, w, clip8[k], clipf[k] if keep_float else None,
+                  clipd[k] if depth else None, _lib.STREAM)
     return Clip(clip8, hits, depth=clipd, images=clipf)

@@ -41,35 +41,28 @@ def pyramid_shapes(h, w):
 def encoder(images, packed, norm):
     """hnr_raft_encoder: images [N,3,H,W] (0..255), N = 1 or 2 -> [N,256,H/8,W/8].  norm: 0 instance norm, 1 folded batch norm, 2 folded batch norm
     then tanh | relu on the two halves of the channels."""
-    L = _lib.lib()
     images = gpu_f32(images, "images")
     if images.dim() != 4 or images.shape[1] != 3 or images.shape[0] not in (1, 2):
         raise HnrError("encoder: images must be [1 or 2,3,H,W], got %s" % (tuple(images.shape),))
     N, _, H, W = (int(s) for s in images.shape)
     check_shape(H, W, "encoder")
-    packed = gpu_f32(packed, "packed", (int(L.hnr_raft_encoder_packed_elems()),))
-    ns = int(L.hnr_raft_encoder_scratch_elems(N, H, W))
+    packed = gpu_f32(packed, "packed", (_lib.size("hnr_raft_encoder_packed_elems"),))
+    scratch = _lib.scratch("hnr_raft_encoder_scratch_elems", N, H, W, device=images.device, dtype=torch.float32)
     out = torch.empty((N, 256, H // 8, W // 8), dtype=torch.float32, device=images.device)
-    scratch = torch.empty((ns,), dtype=torch.float32, device=images.device)
-    with torch.cuda.device(images.device):
-        _lib.check(L.hnr_raft_encoder(_lib.ptr(images), N, H, W, _lib.ptr(packed), int(norm), _lib.ptr(out), _lib.ptr(scratch), ns, _lib.stream()),
-                   "hnr_raft_encoder")
+    _lib.call("hnr_raft_encoder", images, N, H, W, packed, int(norm), out, scratch, scratch.numel(), _lib.STREAM)
     return out
 
 
 def corr_pyramid(fmap1, fmap2):
     """hnr_raft_corr_pyramid: fmap1, fmap2 [256,h,w] -> the four levels [h*w,h_l,w_l] as views of one buffer."""
-    L = _lib.lib()
     fmap1, fmap2 = gpu_f32(fmap1, "fmap1"), gpu_f32(fmap2, "fmap2", tuple(fmap1.shape))
     if fmap1.dim() != 3 or fmap1.shape[0] != 256:
         raise HnrError("corr_pyramid: fmap1 must be [256,h,w], got %s" % (tuple(fmap1.shape),))
     h, w = int(fmap1.shape[1]), int(fmap1.shape[2])
     check_shape(8 * h, 8 * w, "corr_pyramid")
-    n, ns = int(L.hnr_raft_pyramid_elems(h, w)), int(L.hnr_raft_pyramid_scratch_elems(h, w))
-    buf = torch.empty((n,), dtype=torch.float32, device=fmap1.device)
-    scratch = torch.empty((ns,), dtype=torch.float32, device=fmap1.device)
-    with torch.cuda.device(fmap1.device):
-        _lib.check(L.hnr_raft_corr_pyramid(_lib.ptr(fmap1), _lib.ptr(fmap2), h, w, _lib.ptr(buf), _lib.ptr(scratch), ns, _lib.stream()), "hnr_raft_corr_pyramid")
+    buf = _lib.scratch("hnr_raft_pyramid_elems", h, w, device=fmap1.device, dtype=torch.float32)
+    scratch = _lib.scratch("hnr_raft_pyramid_scratch_elems", h, w, device=fmap1.device, dtype=torch.float32)
+    _lib.call("hnr_raft_corr_pyramid", fmap1, fmap2, h, w, buf, scratch, scratch.numel(), _lib.STREAM)
     return buf
 
 
@@ -83,50 +76,43 @@ def pyramid_levels(buf, h, w):
 
 def lookup(pyramid, coords):
     """hnr_raft_lookup: the pyramid buffer of corr_pyramid, coords [2,h,w] (x, y) -> [324,h,w]."""
-    L = _lib.lib()
     pyramid, coords = gpu_f32(pyramid, "pyramid"), gpu_f32(coords, "coords")
     if coords.dim() != 3 or coords.shape[0] != 2:
         raise HnrError("lookup: coords must be [2,h,w], got %s" % (tuple(coords.shape),))
     h, w = int(coords.shape[1]), int(coords.shape[2])
     check_shape(8 * h, 8 * w, "lookup")
-    if pyramid.numel() != int(L.hnr_raft_pyramid_elems(h, w)):
+    if pyramid.numel() != _lib.size("hnr_raft_pyramid_elems", h, w):
         raise HnrError("lookup: the pyramid does not belong to a %dx%d map" % (h, w))
     out = torch.empty((CORR_PLANES, h, w), dtype=torch.float32, device=coords.device)
-    with torch.cuda.device(coords.device):
-        _lib.check(L.hnr_raft_lookup(_lib.ptr(pyramid), _lib.ptr(coords), h, w, _lib.ptr(out), _lib.stream()), "hnr_raft_lookup")
+    _lib.call("hnr_raft_lookup", pyramid, coords, h, w, out, _lib.STREAM)
     return out
 
 
 def update(packed, pyramid, net, inp, coords, want_mask=False):
     """hnr_raft_update, one iteration: net [128,h,w], inp [128,h,w], coords [2,h,w] -> (net, coords, delta_flow [2,h,w], mask [576,h,w] or None); the
     inputs are left as they are."""
-    L = _lib.lib()
     net, inp, coords = gpu_f32(net, "net").clone(), gpu_f32(inp, "inp", tuple(net.shape)), gpu_f32(coords, "coords").clone()
     if net.dim() != 3 or net.shape[0] != 128 or tuple(coords.shape) != (2,) + tuple(net.shape[1:]):
         raise HnrError("update: net and inp must be [128,h,w] and coords [2,h,w]")
     h, w = int(net.shape[1]), int(net.shape[2])
     check_shape(8 * h, 8 * w, "update")
-    packed, pyramid = gpu_f32(packed, "packed", (int(L.hnr_raft_update_packed_elems()),)), gpu_f32(pyramid, "pyramid", (int(L.hnr_raft_pyramid_elems(h, w)),))
-    ns = int(L.hnr_raft_update_scratch_elems(h, w))
+    packed = gpu_f32(packed, "packed", (_lib.size("hnr_raft_update_packed_elems"),))
+    pyramid = gpu_f32(pyramid, "pyramid", (_lib.size("hnr_raft_pyramid_elems", h, w),))
     delta = torch.empty((2, h, w), dtype=torch.float32, device=net.device)
     mask = torch.empty((576, h, w), dtype=torch.float32, device=net.device) if want_mask else None
-    scratch = torch.empty((ns,), dtype=torch.float32, device=net.device)
-    with torch.cuda.device(net.device):
-        _lib.check(L.hnr_raft_update(_lib.ptr(packed), _lib.ptr(pyramid), _lib.ptr(net), _lib.ptr(inp), _lib.ptr(coords), h, w, _lib.ptr(delta),
-                                     _lib.ptr(mask), _lib.ptr(scratch), ns, _lib.stream()), "hnr_raft_update")
+    scratch = _lib.scratch("hnr_raft_update_scratch_elems", h, w, device=net.device, dtype=torch.float32)
+    _lib.call("hnr_raft_update", packed, pyramid, net, inp, coords, h, w, delta, mask, scratch, scratch.numel(), _lib.STREAM)
     return net, coords, delta, mask
 
 
 def upsample(flow, mask):
     """hnr_raft_upsample: flow [2,h,w], mask [576,h,w] -> [2,8h,8w]."""
-    L = _lib.lib()
     flow, mask = gpu_f32(flow, "flow"), gpu_f32(mask, "mask")
     if flow.dim() != 3 or flow.shape[0] != 2 or tuple(mask.shape) != (576,) + tuple(flow.shape[1:]) or flow.shape[1] * flow.shape[2] > 16384:
         raise HnrError("upsample: flow must be [2,h,w] and mask [576,h,w], h*w <= 16384")
     h, w = int(flow.shape[1]), int(flow.shape[2])
     out = torch.empty((2, 8 * h, 8 * w), dtype=torch.float32, device=flow.device)
-    with torch.cuda.device(flow.device):
-        _lib.check(L.hnr_raft_upsample(_lib.ptr(flow), _lib.ptr(mask), h, w, _lib.ptr(out), _lib.stream()), "hnr_raft_upsample")
+    _lib.call("hnr_raft_upsample", flow, mask, h, w, out, _lib.STREAM)
     return out
 
 
@@ -264,9 +250,8 @@ class RAFT(PackedWeights, nn.Module):
 
     def pack_host(self):
         """(fnet, cnet, update_block) fp32 on the CPU, the packed images of include/hnr.h."""
-        L = _lib.lib()
         f, c, u = self.fnet.pack_host(), self.cnet.pack_host(), self.update_block.pack_host()
-        assert f.numel() == c.numel() == int(L.hnr_raft_encoder_packed_elems()) and u.numel() == int(L.hnr_raft_update_packed_elems())
+        assert f.numel() == c.numel() == _lib.size("hnr_raft_encoder_packed_elems") and u.numel() == _lib.size("hnr_raft_update_packed_elems")
         return f, c, u
 
     def forward(self, image1, image2, iters=20, flow_init=None, upsample=True, test_mode=True):
@@ -293,22 +278,13 @@ class RAFT(PackedWeights, nn.Module):
 
     def flow_pair(self, pair, iters=20):
         """pair [2,3,H,W] fp32 on the device -> (flow_low [2,h,w], flow_up [2,H,W]): hnr_raft_flow."""
-        L = _lib.lib()
         dev = self.fnet.conv1.weight.device
         if dev != pair.device:
             raise HnrError("RAFT: the module is on %s, the images on %s" % (dev, pair.device))
         H, W = int(pair.shape[2]), int(pair.shape[3])
         fn, cn, ub = self.packed()
-        ns = int(L.hnr_raft_flow_scratch_elems(H, W))
         low = torch.empty((2, H // 8, W // 8), dtype=torch.float32, device=dev)
         up = torch.empty((2, H, W), dtype=torch.float32, device=dev)
-        scratch = torch.empty((ns,), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.hnr_raft_flow(_lib.ptr(pair), ctypes_offset(pair, 3 * H * W), H, W, _lib.ptr(fn), _lib.ptr(cn), _lib.ptr(ub), int(iters),
-                                       _lib.ptr(low), _lib.ptr(up), _lib.ptr(scratch), ns, _lib.stream()), "hnr_raft_flow")
+        scratch = _lib.scratch("hnr_raft_flow_scratch_elems", H, W, device=dev, dtype=torch.float32)
+        _lib.call("hnr_raft_flow", pair, pair[1], H, W, fn, cn, ub, int(iters), low, up, scratch, scratch.numel(), _lib.STREAM)
         return low, up
-
-
-def ctypes_offset(t, elems):
-    import ctypes
-    return ctypes.c_void_p(t.data_ptr() + elems * t.element_size())

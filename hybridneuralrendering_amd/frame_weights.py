@@ -33,26 +33,22 @@ def gray_from_rgb(images_u8):
 
 def blur_edges(gray_u8):
     """hnr_blur_edges: grey planes [P,H,W] uint8 -> Laplacian of the 5x5 box mean [P,H,W] fp64 (`detect_blurry`, demo_content_aware_weights.py:78-92)."""
-    L = _lib.lib()
     gray_u8 = _u8(gray_u8, "gray_u8", 3)
     P, H, W = (int(s) for s in gray_u8.shape)
     if P < 1 or min(H, W) < 8:
         raise HnrError("blur_edges: gray_u8 must be [P >= 1, H >= 8, W >= 8], got %s" % (tuple(gray_u8.shape),))
     out = torch.empty((P, H, W), dtype=torch.float64, device=gray_u8.device)
-    with torch.cuda.device(gray_u8.device):
-        _lib.check(L.hnr_blur_edges(_lib.ptr(gray_u8), P, H, W, _lib.ptr(out), _lib.stream()), "hnr_blur_edges")
+    _lib.call("hnr_blur_edges", gray_u8, P, H, W, out, _lib.STREAM)
     return out
 
 
-def _score_into(L, e1, e2, flow, H, W, border, row, pick, used, scratch):
-    _lib.check(L.hnr_blur_score_pair(_lib.ptr(e1), _lib.ptr(e2), _lib.ptr(flow), H, W, border, _lib.ptr(row), _lib.ptr(pick), _lib.ptr(used), _lib.ptr(scratch),
-                                     scratch.numel(), _lib.stream()), "hnr_blur_score_pair")
+def _score_into(e1, e2, flow, H, W, border, row, pick, used, scratch):
+    _lib.call("hnr_blur_score_pair", e1, e2, flow, H, W, border, row, pick, used, scratch, scratch.numel(), _lib.STREAM)
 
 
 def blur_score_pair(edge1, edge2, flow_up, border=20, want_maps=False):
     """hnr_blur_score_pair: edge1, edge2 [H,W] fp64, flow_up [2,H,W] (or [1,2,H,W]) fp32 -> row [3] fp64 on the device = (variance of edge 1, variance of
     the warped edge 2, used-pixel count); with want_maps also (pick [H,W] int32: picked pixel index or -1, used [H,W] bool)."""
-    L = _lib.lib()
     edge1, edge2 = _lib.require_gpu(edge1, "edge1", torch.float64).detach(), _lib.require_gpu(edge2, "edge2", torch.float64).detach()
     flow_up = _lib.require_gpu(flow_up, "flow_up", torch.float32).detach()
     if flow_up.dim() == 4 and flow_up.shape[0] == 1:
@@ -66,16 +62,14 @@ def blur_score_pair(edge1, edge2, flow_up, border=20, want_maps=False):
     row = torch.empty((3,), dtype=torch.float64, device=dev)
     pick = torch.empty((H, W), dtype=torch.int32, device=dev) if want_maps else None
     used = torch.empty((H, W), dtype=torch.uint8, device=dev) if want_maps else None
-    scratch = torch.empty((int(L.hnr_blur_score_pair_scratch_bytes(H, W)),), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _score_into(L, edge1, edge2, flow_up.contiguous(), H, W, border, row, pick, used, scratch)
+    scratch = _lib.scratch("hnr_blur_score_pair_scratch_bytes", H, W, device=dev)
+    _score_into(edge1, edge2, flow_up.contiguous(), H, W, border, row, pick, used, scratch)
     return (row, pick, used.bool()) if want_maps else row
 
 
 def score_table(images_u8, gray_u8, raft, border=20, iters=20, want_flows=False):
     """The device table [F,3] fp64 of a scene: row f = blur_score_pair of frames (f, f+1) under RAFT's flow f -> f+1; the last frame pairs with itself
     (demo_content_aware_weights.py:130-133).  Nothing is read back."""
-    L = _lib.lib()
     images_u8, gray_u8 = _u8(images_u8, "images_u8", 4), _u8(gray_u8, "gray_u8", 3)
     if images_u8.shape[-1] != 3 or tuple(gray_u8.shape) != tuple(images_u8.shape[:3]) or images_u8.shape[0] < 1:
         raise HnrError("content_aware_weights: images_u8 must be [F,H,W,3] and gray_u8 [F,H,W], got %s and %s" % (tuple(images_u8.shape), tuple(gray_u8.shape)))
@@ -90,16 +84,15 @@ def score_table(images_u8, gray_u8, raft, border=20, iters=20, want_flows=False)
     dev = images_u8.device
     edges = blur_edges(gray_u8)
     table = torch.empty((F, 3), dtype=torch.float64, device=dev)
-    scratch = torch.empty((int(L.hnr_blur_score_pair_scratch_bytes(H, W)),), dtype=torch.uint8, device=dev)
+    scratch = _lib.scratch("hnr_blur_score_pair_scratch_bytes", H, W, device=dev)
     flows = []
-    with torch.cuda.device(dev):
-        for f in range(F):
-            g = min(f + 1, F - 1)
-            pair = images_u8[[f, g]].permute(0, 3, 1, 2).float().contiguous()
-            _, up = raft.flow_pair(pair, iters)
-            _score_into(L, edges[f], edges[g], up, H, W, border, table[f], None, None, scratch)
-            if want_flows:
-                flows.append(up)
+    for f in range(F):
+        g = min(f + 1, F - 1)
+        pair = images_u8[[f, g]].permute(0, 3, 1, 2).float().contiguous()
+        _, up = raft.flow_pair(pair, iters)
+        _score_into(edges[f], edges[g], up, H, W, border, table[f], None, None, scratch)
+        if want_flows:
+            flows.append(up)
     return (table, flows) if want_flows else table
 
 

@@ -102,14 +102,9 @@ def resize_tables(n_in, n_out, filter="lanczos"):
     if t is None:
         if key[0] < 1 or key[1] < 1:
             raise HnrError("resize: sizes must be >= 1, got %d -> %d" % key[:2])
-        L = _lib.lib()
-        ksize = L.hnr_resize_coeffs(key[0], key[1], key[2], None, None, 0)
-        if ksize < 1:
-            raise HnrError("hnr_resize_coeffs failed (code %d): %s" % (ksize, L.hnr_last_error().decode("utf-8", "replace")))
+        ksize = _lib.size("hnr_resize_coeffs", key[0], key[1], key[2], None, None, 0)
         bounds, coef = np.empty((key[1], 2), np.int32), np.empty((key[1], ksize), np.int32)
-        rc = L.hnr_resize_coeffs(key[0], key[1], key[2], bounds.ctypes.data_as(ctypes.c_void_p), coef.ctypes.data_as(ctypes.c_void_p), coef.size)
-        if rc != ksize:
-            raise HnrError("hnr_resize_coeffs failed (code %d): %s" % (rc, L.hnr_last_error().decode("utf-8", "replace")))
+        _lib.size("hnr_resize_coeffs", key[0], key[1], key[2], bounds.ctypes.data_as(ctypes.c_void_p), coef.ctypes.data_as(ctypes.c_void_p), coef.size)
         if len(_TABLES) > 64:
             _TABLES.clear()
         _TABLES[key] = t = (int(ksize), bounds, coef)
@@ -157,10 +152,7 @@ def resize_form(raw_hw, size, channels=3, filter="lanczos"):
         raise HnrError("resize_form: sizes must be >= 1")
     kh = resize_tables(w, W, filter)[0] if w != W else 0
     kv = resize_tables(h, H, filter)[0] if h != H else 0
-    rc = _lib.lib().hnr_resize_u8_form(h, w, int(channels), H, W, kh, kv)
-    if rc not in (1, 2):
-        raise HnrError("hnr_resize_u8_form failed (code %d): %s" % (rc, _lib.lib().hnr_last_error().decode("utf-8", "replace")))
-    return "fused" if rc == 1 else "two_pass"
+    return "fused" if _lib.size("hnr_resize_u8_form", h, w, int(channels), H, W, kh, kv) == 1 else "two_pass"
 
 
 def resize_frames(raw, size, filter="lanczos", mode=None, out=None, form="auto", device=None):
@@ -201,28 +193,22 @@ def resize_frames(raw, size, filter="lanczos", mode=None, out=None, form="auto",
             raise HnrError("%s: out must be a contiguous uint8 tensor [%d,%d,%d,%d] on %s" % (what, N, H, W, C, dev))
     else:
         out = torch.empty((N, H, W, C), dtype=torch.uint8, device=dev)
-    L = _lib.lib()
     own = not src.is_cuda
     src = src.to(dev).contiguous()
     kh, bh, ch = _device_tables(w, W, filter, dev) if w != W else (0, None, None)
     kv, bv, cv = _device_tables(h, H, filter, dev) if h != H else (0, None, None)
-    with torch.cuda.device(dev):
-        rgba = mode == "RGBA" and (w != W or h != H)        # Image.resize returns a copy of a same-size image BEFORE it converts RGBA -> RGBa
-        if rgba:
-            pre = src if own else torch.empty_like(src)
-            _lib.check(L.hnr_rgba_premultiply(_lib.ptr(src), _lib.ptr(pre), N * h * w, _lib.stream()), "hnr_rgba_premultiply")
-            src = pre
-        scratch = None
-        if form == "two_pass" or (form == "auto" and L.hnr_resize_u8_form(h, w, C, H, W, kh, kv) == 2):
-            nbytes = int(L.hnr_resize_u8_scratch_bytes(N, h, w, C, H, W))
-            if nbytes < 0:
-                raise HnrError("hnr_resize_u8_scratch_bytes: %s" % L.hnr_last_error().decode("utf-8", "replace"))
-            scratch = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
-        _lib.check(L.hnr_resize_u8(_lib.ptr(src), N, h, w, C, _lib.ptr(out), H, W, _lib.ptr(bh), _lib.ptr(ch), kh, _lib.ptr(bv), _lib.ptr(cv), kv,
-                                   _lib.RESIZE_FORMS[form], _lib.ptr(scratch), 0 if scratch is None else int(scratch.numel()), _lib.stream()),
-                   "hnr_resize_u8")
-        if rgba:
-            _lib.check(L.hnr_rgba_unpremultiply(_lib.ptr(out), _lib.ptr(out), N * H * W, _lib.stream()), "hnr_rgba_unpremultiply")
+    rgba = mode == "RGBA" and (w != W or h != H)        # Image.resize returns a copy of a same-size image BEFORE it converts RGBA -> RGBa
+    if rgba:
+        pre = src if own else torch.empty_like(src)
+        _lib.call("hnr_rgba_premultiply", src, pre, N * h * w, _lib.STREAM)
+        src = pre
+    scratch = None
+    if form == "two_pass" or (form == "auto" and _lib.size("hnr_resize_u8_form", h, w, C, H, W, kh, kv) == 2):
+        scratch = torch.empty((max(_lib.size("hnr_resize_u8_scratch_bytes", N, h, w, C, H, W), 16),), dtype=torch.uint8, device=dev)
+    _lib.call("hnr_resize_u8", src, N, h, w, C, out, H, W, bh, ch, kh, bv, cv, kv, _lib.RESIZE_FORMS[form], scratch,
+              0 if scratch is None else int(scratch.numel()), _lib.STREAM)
+    if rgba:
+        _lib.call("hnr_rgba_unpremultiply", out, out, N * H * W, _lib.STREAM)
     mark_written([out])
     return out[0] if single and out.dim() == 4 else out
 
@@ -250,9 +236,7 @@ def compose_rgba(rgba8, white=True, black=False, alpha=True, mask=False):
         res["alpha"] = f(N, H, W)
     if mask:
         res["mask"] = f(N, H, W)
-    with torch.cuda.device(t.device):
-        _lib.check(_lib.lib().hnr_rgba_compose(_lib.ptr(t), N * H * W, _lib.ptr(res.get("white")), _lib.ptr(res.get("black")), _lib.ptr(res.get("alpha")),
-                                               _lib.ptr(res.get("mask")), _lib.stream()), "hnr_rgba_compose")
+    _lib.call("hnr_rgba_compose", t, N * H * W, res.get("white"), res.get("black"), res.get("alpha"), res.get("mask"), _lib.STREAM)
     return {k: v[0] for k, v in res.items()} if single else res
 
 
@@ -533,7 +517,6 @@ class BatchSampler(_Sampler):
             raise HnrError("BatchSampler: mode must be one of %s (random2, proportional_random and dynamic_nearest are not supported)" % sorted(MODES))
         if near is None or far is None:
             raise HnrError("BatchSampler: near and far (the item's depth range) are required")
-        self.L = _lib.lib()
         self.bank, self.mode, self.margin = bank, mode, int(margin)
         self.near, self.far = float(near), float(far)
         H, W, m = bank.H, bank.W, self.margin
@@ -565,9 +548,7 @@ class BatchSampler(_Sampler):
         self.seed = seed
         self.prm = _lib.FrameBatchParams(MODES[mode], S, pn, ps, dlo, dhi, m, self.dir_norm, int(bg_random), self.downweight, (ctypes.c_float * 3)(*self.bg), seed)
         dev = bank.device
-        nbytes = int(self.L.hnr_frame_batch_scratch_bytes(MODES[mode], pn))
-        if nbytes < 0:
-            raise HnrError("BatchSampler: unsupported mode / patch count")
+        nbytes = _lib.size("hnr_frame_batch_scratch_bytes", MODES[mode], pn, what="BatchSampler: unsupported mode / patch count")
         self._scratch = torch.zeros((max(nbytes, 16),), dtype=torch.uint8, device=dev)
         self._item_scratch = torch.zeros((16,), dtype=torch.uint8, device=dev)
         self.step = torch.zeros((1,), dtype=torch.int64, device=dev)          # the step counter (read and advanced by the header kernel)
@@ -615,13 +596,11 @@ class BatchSampler(_Sampler):
     def _depth_rays(self, dep, R):
         """gt_depth of the item just written: one launch behind the batch's, reading its frame_row / pixel_idx on the device"""
         row, pix, K, gt = dep
-        _lib.check(self.L.hnr_frame_depth_rays(ctypes.byref(self.bank._dc), _lib.ptr(row), _lib.ptr(pix),
-                                               _lib.ptr(K) if self.bank.depth_intrinsic is not None else None, R, _lib.ptr(gt), _lib.stream()),
-                   "hnr_frame_depth_rays")
+        _lib.call("hnr_frame_depth_rays", self.bank._dc, row, pix, K if self.bank.depth_intrinsic is not None else None, R, gt, _lib.STREAM)
 
     def _views(self):
         b = self.bank
-        return (ctypes.byref(b.reference._c) if b.V > 0 else None), (_lib.ptr(b.nearest) if b.V > 0 else None), b.V
+        return (b.reference._c if b.V > 0 else None), (b.nearest if b.V > 0 else None), b.V
 
     # ------------------------------------------------------------------------------------------------ the interface
     def set_schedule(self, rows):
@@ -647,12 +626,10 @@ class BatchSampler(_Sampler):
             raise HnrError("BatchSampler.next: no schedule (set_schedule(rows) first)")
         res, (o, dep) = self._next_outputs(out)
         ref, nearest, V = self._views()
-        with torch.cuda.device(self.bank.device):
-            _lib.check(self.L.hnr_frame_batch(ctypes.byref(self.bank._c), ref, nearest, V, ctypes.byref(self.prm), _lib.ptr(self.schedule), self._n_schedule,
-                                              _lib.ptr(self.step), ctypes.byref(o), _lib.ptr(self._scratch), int(self._scratch.numel()), _lib.stream()),
-                       "hnr_frame_batch")
-            if dep is not None:
-                self._depth_rays(dep, self.R)
+        _lib.call("hnr_frame_batch", self.bank._c, ref, nearest, V, self.prm, self.schedule, self._n_schedule, self.step, o, self._scratch,
+                  int(self._scratch.numel()), _lib.STREAM)
+        if dep is not None:
+            self._depth_rays(dep, self.R)
         return res
 
     def item(self, row, pixels=None):
@@ -672,12 +649,10 @@ class BatchSampler(_Sampler):
         t = self._alloc(R)
         o, dep = self._bind(t, "BatchSampler.item", R)
         ref, nearest, V = self._views()
-        with torch.cuda.device(dev):
-            _lib.check(self.L.hnr_frame_item(ctypes.byref(self.bank._c), ref, nearest, V, row, _lib.ptr(pixels), R, self.margin, self.dir_norm,
-                                             (ctypes.c_float * 3)(*self.bg), self.downweight, ctypes.byref(o), _lib.ptr(self._item_scratch), 16, _lib.stream()),
-                       "hnr_frame_item")
-            if dep is not None:
-                self._depth_rays(dep, R)                      # (the row travels through the item's own frame_row word on the device)
+        _lib.call("hnr_frame_item", self.bank._c, ref, nearest, V, row, pixels, R, self.margin, self.dir_norm, (ctypes.c_float * 3)(*self.bg),
+                  self.downweight, o, self._item_scratch, 16, _lib.STREAM)
+        if dep is not None:
+            self._depth_rays(dep, R)                      # (the row travels through the item's own frame_row word on the device)
         return self._finish(t)
 
 
@@ -734,7 +709,6 @@ class PathSampler(_Sampler):
             K = torch.from_numpy(np.ascontiguousarray(intrinsic, dtype=np.float32))
         if tuple(K.shape) not in ((3, 3), (self.P, 3, 3)):
             raise HnrError("PathSampler: intrinsic must be [3,3] or [%d,3,3], got %s" % (self.P, tuple(K.shape)))
-        self.L = _lib.lib()
         dev = bank.device
         self.poses, self.intrinsic = poses.to(dev).contiguous().clone(), K.to(dev).contiguous().clone()      # the sampler's own tables
         self._K_per_pose = 1 if K.dim() == 3 else 0
@@ -775,10 +749,8 @@ class PathSampler(_Sampler):
         return self._bind_outputs(tensors, self._shapes(), what)
 
     def _launch(self, o, step, i):
-        with torch.cuda.device(self.bank.device):
-            _lib.check(self.L.hnr_path_item(ctypes.byref(self.bank._c), _lib.ptr(self.poses), self.P, _lib.ptr(self.intrinsic), self._K_per_pose, self.V, self.n1,
-                                            step, i, self.margin, self.dir_norm, (ctypes.c_float * 3)(*self.bg), self.downweight, ctypes.byref(o),
-                                            _lib.ptr(self._scratch), int(self._scratch.numel()), _lib.stream()), "hnr_path_item")
+        _lib.call("hnr_path_item", self.bank._c, self.poses, self.P, self.intrinsic, self._K_per_pose, self.V, self.n1, step, i, self.margin, self.dir_norm,
+                  (ctypes.c_float * 3)(*self.bg), self.downweight, o, self._scratch, int(self._scratch.numel()), _lib.STREAM)
 
     # ------------------------------------------------------------------------------------------------ the interface
     def set_poses(self, poses):
@@ -808,16 +780,14 @@ class PathSampler(_Sampler):
                 raise HnrError("PathSampler.views: exclude_rows must be [%d], got %s" % (Q, tuple(ex.shape)))
             ex = ex.to(dev).contiguous()
         out = torch.empty((Q, self.V), dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(self.L.hnr_pose_views(ctypes.byref(self.bank._c), _lib.ptr(p), Q, _lib.ptr(self.intrinsic), self._K_per_pose, _lib.ptr(ex), self.V, self.n1,
-                                             _lib.ptr(out), _lib.stream()), "hnr_pose_views")
+        _lib.call("hnr_pose_views", self.bank._c, p, Q, self.intrinsic, self._K_per_pose, ex, self.V, self.n1, out, _lib.STREAM)
         return out
 
     def next(self, out=None):
         """The item of frame step % P; step += 1 on the device.  out=None: the sampler's own static tensors; out = a dict: the outputs whose keys
         are present in it ("camrot" or "camrotc2w" for the rotation) are written into those tensors and no others are touched."""
         res, o = self._next_outputs(out)
-        self._launch(o, _lib.ptr(self.step), 0)
+        self._launch(o, self.step, 0)
         return res
 
     def item(self, i):

@@ -58,7 +58,6 @@ def _tables(intrinsics, extrinsics, device):
 def geometric_consistency(depth, intrinsics, extrinsics=None):
     """depth [V,H,W] fp32 on the GPU; intrinsics [V,3,3] and extrinsics [V,4,4] (world to camera; host arrays or tensors), or a CameraTables.
     Returns (count [V,H,W] int32: the source views consistent with each pixel, depth_averaged [V,H,W]) -- hnr_geo_consistency."""
-    L = _lib.lib()
     depth = _lib.require_gpu(depth, "depth", torch.float32)
     if depth.dim() != 3:
         raise HnrError("geometric_consistency: depth must be [V,H,W]")
@@ -68,9 +67,7 @@ def geometric_consistency(depth, intrinsics, extrinsics=None):
         raise HnrError("geometric_consistency: %d depth maps but %d cameras (or cameras on another device)" % (V, tab.V))
     count = torch.empty((V, H, W), dtype=torch.int32, device=depth.device)
     avg = torch.empty_like(depth)
-    with torch.cuda.device(depth.device):
-        _lib.check(L.hnr_geo_consistency(_lib.ptr(depth), V, H, W, _lib.ptr(tab.K), _lib.ptr(tab.Kinv), _lib.ptr(tab.E), _lib.ptr(tab.Einv), _lib.ptr(count),
-                                         _lib.ptr(avg), _lib.stream()), "hnr_geo_consistency")
+    _lib.call("hnr_geo_consistency", depth, V, H, W, tab.K, tab.Kinv, tab.E, tab.Einv, count, avg, _lib.STREAM)
     return count, avg
 
 
@@ -83,7 +80,6 @@ def select_points(cam_xyz, conf, points_mask, count, depth_avg, tables, conf_thr
     """hnr_geo_filter_select.  cam_xyz [V,H,W,3], conf [V,H,W] fp32, points_mask [V,H,W] uint8, count / depth_avg from geometric_consistency.
     Returns dict(world [cap,3], cam [cap,3], conf [cap], view [cap] int32, meta [V+1] int64 on the device: per-view counts, then the total,
     status [1] int32, capacity).  Nothing is read back here.  capacity None: V*H*W rows (32 bytes each), which cannot overflow."""
-    L = _lib.lib()
     cam_xyz = _lib.require_gpu(cam_xyz, "cam_xyz", torch.float32)
     dev = cam_xyz.device
     if cam_xyz.dim() != 4 or cam_xyz.shape[3] != 3:
@@ -107,17 +103,10 @@ def select_points(cam_xyz, conf, points_mask, count, depth_avg, tables, conf_thr
     out = dict(world=torch.empty((rows, 3), dtype=torch.float32, device=dev), cam=torch.empty((rows, 3), dtype=torch.float32, device=dev),
                conf=torch.empty((rows,), dtype=torch.float32, device=dev), view=torch.empty((rows,), dtype=torch.int32, device=dev),
                meta=torch.zeros((V + 1,), dtype=torch.int64, device=dev), status=torch.zeros((1,), dtype=torch.int32, device=dev), capacity=cap)
-    with torch.cuda.device(dev):
-        nbytes = int(L.hnr_geo_filter_select_scratch_bytes(V, H, W))
-        if nbytes < 0:
-            raise HnrError("select_points: unsupported shape V=%d, %dx%d" % (V, H, W))
-        scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        fp = lambda a: None if a is None else a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
-        _lib.check(L.hnr_geo_filter_select(_lib.ptr(cam_xyz), _lib.ptr(conf), _lib.ptr(pm), _lib.ptr(count), _lib.ptr(avg), V, H, W, _lib.ptr(tables.Einv),
-                                           float(conf_thresh), int(geo_cnsst_num), fp(r), fp(table), _lib.ptr(out["world"]), _lib.ptr(out["cam"]),
-                                           _lib.ptr(out["conf"]), _lib.ptr(out["view"]), cap, ctypes.c_void_p(out["meta"].data_ptr()),
-                                           ctypes.c_void_p(out["meta"].data_ptr() + 8 * V), _lib.ptr(out["status"]), _lib.ptr(scratch), nbytes, _lib.stream()),
-                   "hnr_geo_filter_select")
+    scratch = _lib.scratch("hnr_geo_filter_select_scratch_bytes", V, H, W, device=dev, what="select_points: unsupported shape V=%d, %dx%d" % (V, H, W))
+    fp = lambda a: None if a is None else a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+    _lib.call("hnr_geo_filter_select", cam_xyz, conf, pm, count, avg, V, H, W, tables.Einv, float(conf_thresh), int(geo_cnsst_num), fp(r), fp(table),
+              out["world"], out["cam"], out["conf"], out["view"], cap, out["meta"], out["meta"][V:], out["status"], scratch, scratch.numel(), _lib.STREAM)
     return out
 
 

@@ -25,7 +25,6 @@ from ._lib import HnrError
 def probe_select(output, pixel_idx, gt_image, bg_color, height, width, far_thresh=0.0, opacity_thresh=0.7):
     """Indices (into the frame's rays) of the pixels that become new points, in the reference's order (row-major over the image).
     output: the prob == 1 output dict of one frame ([1, R, C] tensors; ray_mask [1, R]); pixel_idx [1, R, 2] (x, y); gt_image [R, 3]."""
-    L, p = _lib.lib(), _lib.ptr
     g = lambda t, n: _lib.require_gpu(t.to(torch.float32), n, torch.float32)
     pix = g(pixel_idx, "pixel_idx").reshape(-1, 2)
     R = pix.shape[0]
@@ -40,9 +39,8 @@ def probe_select(output, pixel_idx, gt_image, bg_color, height, width, far_thres
     bg = (ctypes.c_float * 3)(*[float(v) for v in torch.as_tensor(bg_color).reshape(-1)[:3].tolist()])
     miss = torch.empty((height * width,), dtype=torch.int32, device=dev)
     sel = torch.empty((height * width,), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(L.hnr_probe_select(p(pix), p(rm), p(gt), p(col), bg, p(far), p(opa), R, int(height), int(width), float(far_thresh),
-                                      float(opacity_thresh), p(miss), p(sel), _lib.stream()), "hnr_probe_select")
+    _lib.call("hnr_probe_select", pix, rm, gt, col, bg, far, opa, R, int(height), int(width), float(far_thresh), float(opacity_thresh), miss, sel,
+              _lib.STREAM)
     return sel[sel > 0].long() - 1                    # boolean indexing walks the map in row-major order, like the reference's mask indexing (:551)
 
 
@@ -103,7 +101,6 @@ class RayMissRanking:
         if self.n > 1024:
             raise HnrError("RayMissRanking: a table of %d frames (train_len // prob_num_step + 1) is beyond the kernel's 1024" % self.n)
         self.prob_tiers, self.prob_kernel_size = prob_tiers, prob_kernel_size
-        self.L = _lib.lib()
         self._ids0 = torch.arange(self.n, dtype=torch.int32, device=self.device)
         self.ids = self._ids0.clone()
         self.losses = torch.zeros((self.n,), dtype=torch.float32, device=self.device)
@@ -150,10 +147,7 @@ class RayMissRanking:
             row = self._row.fill_(int(frame_row))
         if color.device != self.device or gt.device != self.device or mask.device != self.device or row.device != self.device:
             raise HnrError("RayMissRanking.update: every tensor must live on %s" % self.device)
-        p = _lib.ptr
-        with torch.cuda.device(self.device):
-            _lib.check(self.L.hnr_ray_miss_rank(p(color), p(gt), p(mask), R, p(row), p(self.ids), p(self.losses), self.n, p(self.last), _lib.stream()),
-                       "hnr_ray_miss_rank")
+        _lib.call("hnr_ray_miss_rank", color, gt, mask, R, row, self.ids, self.losses, self.n, self.last, _lib.STREAM)
         return self.last
 
     def worst(self):

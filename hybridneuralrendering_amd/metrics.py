@@ -51,7 +51,6 @@ def frame_metrics(render_out, frame, win=11, data_range=2.0, out=None, row=0, im
     from, with gt_image [R,3] (batch dim optional).  out / row: a [capacity, NCOLS] float64 device table and the row to fill (default: a
     fresh [1, NCOLS] table).  images8: optional pair of [h,w,3] uint8 device tensors that receive the quantised image and ground truth
     (the bytes of the reference's PNGs).  Returns the table; columns are FM[...]; derive() turns rows into the reported numbers."""
-    L = _lib.lib()
     img = _lib.require_gpu(render_out["image"], "image", torch.float32)
     dev = img.device
     if img.dim() != 3 or img.shape[2] != 3:
@@ -79,14 +78,9 @@ def frame_metrics(render_out, frame, win=11, data_range=2.0, out=None, row=0, im
         for t in (a8, b8):
             if not (t.is_cuda and t.dtype == torch.uint8 and tuple(t.shape) == (h, w, 3) and t.is_contiguous()):
                 raise HnrError("frame_metrics: images8 must be two contiguous [h, w, 3] uint8 tensors on the GPU")
-    nbytes = int(L.hnr_frame_metrics_scratch_bytes(h, w, int(win)))
-    if nbytes < 0:
-        _lib.check(nbytes, "hnr_frame_metrics_scratch_bytes")
-    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    p = _lib.ptr
-    with torch.cuda.device(dev):
-        _lib.check(L.hnr_frame_metrics(p(img), p(gt_full), h, w, p(col) if R else None, p(gt) if R else None, p(mask) if R else None, R, int(win),
-                                       float(data_range), p(out[row]), p(a8), p(b8), p(scratch), _lib.stream()), "hnr_frame_metrics")
+    scratch = _lib.scratch("hnr_frame_metrics_scratch_bytes", h, w, int(win), device=dev)
+    _lib.call("hnr_frame_metrics", img, gt_full, h, w, col if R else None, gt if R else None, mask if R else None, R, int(win), float(data_range),
+              out[row], a8, b8, scratch, _lib.STREAM)
     return out
 
 
@@ -114,7 +108,6 @@ def depth_frame_metrics(render_out, frame, out=None, row=0):
     (ray_mask > 0) and a measurement (gt_depth > 0), {n, sum |e|, sum e^2, sum |e| / d, #(max(D / d, d / D) < 1.25)} with e = D - d in fp64.
     render_out: driver.render_image(depth=True)'s result (coarse_depth [R], ray_mask [R]); frame: the item with gt_depth [R] (metres, 0 = no
     measurement; frames.BatchSampler.item of a bank with depth frames).  out / row: a [capacity, DM_NCOLS] float64 device table."""
-    L = _lib.lib()
     if "coarse_depth" not in render_out:
         raise HnrError("depth_frame_metrics: the render has no coarse_depth (driver.render_image(..., depth=True))")
     if "gt_depth" not in frame:
@@ -133,9 +126,7 @@ def depth_frame_metrics(render_out, frame, out=None, row=0):
         raise HnrError("depth_frame_metrics: out must be a contiguous [capacity, %d] float64 table on the GPU" % DM_NCOLS)
     if not 0 <= row < out.shape[0]:
         raise HnrError("depth_frame_metrics: row %d outside the table (%d rows)" % (row, out.shape[0]))
-    p = _lib.ptr
-    with torch.cuda.device(D.device):
-        _lib.check(L.hnr_depth_metrics(p(D), p(d), p(mask), R, p(out[row]), _lib.stream()), "hnr_depth_metrics")
+    _lib.call("hnr_depth_metrics", D, d, mask, R, out[row], _lib.STREAM)
     return out
 
 

@@ -73,10 +73,7 @@ def ray_march(ray_dist, ray_valid, ray_features, render_func, blend_func, bg_col
         col, opa, acc, bw, bgt = f(R, 3), f(R, SR), f(R, SR), f(R, SR), f(R)
         bg = None if bg_color is None else _lib.require_gpu(bg_color.to(dev).float().reshape(-1, 3)[n if bg_color.numel() > 3 else 0],
                                                             "bg_color", torch.float32)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().hnr_ray_march(_lib.ptr(dist[n * R:(n + 1) * R]), _lib.ptr(valid[n * R:(n + 1) * R]), _lib.ptr(feats[n]),
-                                                _lib.ptr(bg) if bg is not None else None, R, SR, _lib.ptr(col), _lib.ptr(opa), _lib.ptr(acc),
-                                                _lib.ptr(bw), _lib.ptr(bgt), _lib.stream()), "hnr_ray_march")
+        _lib.call("hnr_ray_march", dist[n * R:(n + 1) * R], valid[n * R:(n + 1) * R], feats[n], bg, R, SR, col, opa, acc, bw, bgt, _lib.STREAM)
         out.append((col, opa, acc, bw, bgt))
     cat = lambda i: torch.stack([o[i] for o in out], dim=0)
     bg_t = cat(4)[..., None]
@@ -258,7 +255,6 @@ class NeuralPoints(nn.Module):
     def forward(self, inputs):
         """:702-733 -> the 14-tuple (sampled_color, sampled_Rw2c, sampled_dir, sampled_conf, sampled_embedding,
         sampled_xyz_pers, sampled_xyz, sample_pnt_mask, sample_loc, sample_loc_w, sample_ray_dirs, ray_mask, vsize, grid_vox_sz)."""
-        L = _lib.lib()
         camrot, campos = inputs["camrotc2w"], inputs["campos"]
         near, far = torch.min(inputs["near"]).item(), torch.max(inputs["far"]).item()
         pidx, loc, loc_w, dirs, ray_mask, vsize, _ = self.querier.query_points(
@@ -271,12 +267,8 @@ class NeuralPoints(nn.Module):
         o_color, o_dir, o_conf, o_emb = f(B, R, SR, K, 3), f(B, R, SR, K, 3), f(B, R, SR, K, 1), f(B, R, SR, K, c.F)
         o_pers, o_xyz = f(B, R, SR, K, 3), f(B, R, SR, K, 3)
         o_mask = torch.empty((B, R, SR, K), dtype=torch.uint8, device=dev)
-        p = _lib.ptr
-        with torch.cuda.device(dev):
-            _lib.check(L.hnr_gather_points(p(pidx), n, p(c.xyz), p(c.emb), p(c.conf), p(c.dir), p(c.color), c.F,
-                                           p(campos.reshape(3).contiguous()), p(camrot.reshape(3, 3).contiguous()), p(o_color),
-                                           p(o_dir), p(o_conf), p(o_emb), p(o_pers), p(o_xyz), p(o_mask), _lib.stream()),
-                       "hnr_gather_points")
+        _lib.call("hnr_gather_points", pidx, n, c.xyz, c.emb, c.conf, c.dir, c.color, c.F, campos.reshape(3).contiguous(),
+                  camrot.reshape(3, 3).contiguous(), o_color, o_dir, o_conf, o_emb, o_pers, o_xyz, o_mask, _lib.STREAM)
         sampled_Rw2c = self.Rw2c                                           # (:720) 2-D as it is, 3-D gathered per neighbour (empty slots read point 0)
         if self._parts is not None and not self._parts.uniform:
             sampled_Rw2c = self._parts.part_rot[self._parts.part[pidx.reshape(-1).clamp(min=0).long()].long()].view(B, R, SR, K, 3, 3)
@@ -373,13 +365,10 @@ class NeuralPointsRayMarching(nn.Module):
         dev = full["sample_pidx"].device
         f = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
         mo, loc, far, col, dr, cf, em = f(R), f(R, 3), f(R), f(R, 3), f(R, 3), f(R), f(R, cloud.F)
-        p = _lib.ptr
         g = lambda t: _lib.require_gpu(t.detach(), "probe input", torch.float32)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().hnr_probe_outputs(p(g(full["coarse_point_opacity"])), p(full["sample_loc_w"]), p(full["sample_pidx"]), p(g(full["weight"])),
-                                                    p(g(full["conf_coefficient"])), p(cloud.xyz), p(cloud.emb), p(cloud.conf), p(cloud.dir), p(cloud.color),
-                                                    cloud.F, R, SR, K, p(mo), p(loc), p(far), p(col), p(dr), p(cf), p(em), _lib.stream()),
-                       "hnr_probe_outputs")
+        _lib.call("hnr_probe_outputs", g(full["coarse_point_opacity"]), full["sample_loc_w"], full["sample_pidx"], g(full["weight"]),
+                  g(full["conf_coefficient"]), cloud.xyz, cloud.emb, cloud.conf, cloud.dir, cloud.color, cloud.F, R, SR, K, mo, loc, far, col, dr, cf, em,
+                  _lib.STREAM)
         sel = lambda t: t.index_select(0, rows)[None]
         return dict(ray_max_shading_opacity=sel(mo)[..., None], ray_max_sample_loc_w=sel(loc), ray_max_far_dist=sel(far)[..., None],
                     shading_avg_color=sel(col), shading_avg_dir=sel(dr), shading_avg_conf=sel(cf)[..., None], shading_avg_embedding=sel(em))

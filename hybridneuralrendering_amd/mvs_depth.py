@@ -16,7 +16,7 @@ from torch import nn
 
 from . import _lib
 from ._lib import HnrError
-from ._nets import NormParams, Packed, PackedWeights, filtered_state_dict, gpu_f32, host_f32, load_checked, load_checkpoint, same_device
+from ._nets import NormParams, Packed, PackedWeights, filtered_state_dict, gpu_f32, host_f32, load_checked, load_checkpoint
 
 EPS = 1e-5                                                       # nn.BatchNorm's eps
 NUM_DEPTH = 192                                                  # gen_points' depth planes
@@ -32,74 +32,56 @@ def feature_shape(H, W):
 
 def feature_forward(images, packed):
     """hnr_mvsnet_feature: images [V,3,H,W], packed [MVSNET_FEATURE_PACKED_ELEMS] -> [V,32,h,w]."""
-    L = _lib.lib()
     images, packed = gpu_f32(images, "images"), gpu_f32(packed, "packed", (_lib.MVSNET_FEATURE_PACKED_ELEMS,))
     if images.dim() != 4 or images.shape[1] != 3:
         raise HnrError("feature_forward: images must be [V,3,H,W], got %s" % (tuple(images.shape),))
-    same_device("feature_forward", images, packed)
     V, _, H, W = (int(s) for s in images.shape)
-    ns = int(L.hnr_mvsnet_feature_scratch_elems(V, H, W)) if max(V, H, W) < 2 ** 31 else -1
-    if ns < 0:
-        raise HnrError("feature_forward: unsupported shape V=%d H=%d W=%d (1 <= V <= 64, 4 <= H, W <= 32768)" % (V, H, W))
+    scratch = _lib.scratch("hnr_mvsnet_feature_scratch_elems", V, H, W, device=images.device, dtype=torch.float32,
+                           what="feature_forward: unsupported shape V=%d H=%d W=%d (1 <= V <= 64, 4 <= H, W <= 32768)" % (V, H, W))
     out = torch.empty((V, 32) + feature_shape(H, W), dtype=torch.float32, device=images.device)
-    scratch = torch.empty((ns,), dtype=torch.float32, device=images.device)
-    with torch.cuda.device(images.device):
-        _lib.check(L.hnr_mvsnet_feature(_lib.ptr(images), V, H, W, _lib.ptr(packed), _lib.ptr(out), _lib.ptr(scratch), ns, _lib.stream()), "hnr_mvsnet_feature")
+    _lib.call("hnr_mvsnet_feature", images, V, H, W, packed, out, scratch, scratch.numel(), _lib.STREAM)
     return out
 
 
 def cost_volume(features, proj, depth_values):
     """hnr_mvsnet_cost_volume for one reference view: features [V,32,h,w], proj [V,3,4] (or [V,4,4]), depth_values [D] -> [32,D,h,w]."""
-    L = _lib.lib()
     features, proj, depth_values = gpu_f32(features, "features"), gpu_f32(proj, "proj"), gpu_f32(depth_values, "depth_values")
     if features.dim() != 4 or features.shape[1] != 32:
         raise HnrError("cost_volume: features must be [V,32,h,w], got %s" % (tuple(features.shape),))
     V, _, h, w = (int(s) for s in features.shape)
     if proj.dim() != 3 or proj.shape[0] != V or tuple(proj.shape[1:]) not in ((3, 4), (4, 4)) or depth_values.dim() != 1:
         raise HnrError("cost_volume: proj must be [V,3,4] or [V,4,4] and depth_values [D]")
-    same_device("cost_volume", features, proj, depth_values)
     proj, D = proj[:, :3].contiguous(), int(depth_values.shape[0])
     if not (1 <= V <= 64 and 2 <= h <= 8192 and 2 <= w <= 8192 and 1 <= D <= 4096 and D * h * w <= 2 ** 26):
         raise HnrError("cost_volume: unsupported shape V=%d D=%d h=%d w=%d (V <= 64, 2 <= h, w <= 8192, D <= 4096, D*h*w <= 2^26)" % (V, D, h, w))
     out = torch.empty((32, D, h, w), dtype=torch.float32, device=features.device)
-    with torch.cuda.device(features.device):
-        _lib.check(L.hnr_mvsnet_cost_volume(_lib.ptr(features), V, h, w, _lib.ptr(proj), _lib.ptr(depth_values), D, _lib.ptr(out), _lib.stream()),
-                   "hnr_mvsnet_cost_volume")
+    _lib.call("hnr_mvsnet_cost_volume", features, V, h, w, proj, depth_values, D, out, _lib.STREAM)
     return out
 
 
 def cost_reg(volume, packed):
     """hnr_mvsnet_cost_reg: volume [32,D,h,w], packed [MVSNET_REG_PACKED_ELEMS] -> logits [D,h,w].  D, h and w must be multiples of 8."""
-    L = _lib.lib()
     volume, packed = gpu_f32(volume, "volume"), gpu_f32(packed, "packed", (_lib.MVSNET_REG_PACKED_ELEMS,))
     if volume.dim() != 4 or volume.shape[0] != 32:
         raise HnrError("cost_reg: volume must be [32,D,h,w], got %s" % (tuple(volume.shape),))
-    same_device("cost_reg", volume, packed)
     D, h, w = (int(s) for s in volume.shape[1:])
-    ns = int(L.hnr_mvsnet_cost_reg_scratch_elems(D, h, w))
-    if ns < 0:
-        raise HnrError("cost_reg: unsupported shape D=%d h=%d w=%d: each must be a multiple of 8 (the skip connections do not line up otherwise; the "
-                       "reference fails there too), D <= 4096, h, w <= 8192, D*h*w <= 2^26" % (D, h, w))
+    scratch = _lib.scratch("hnr_mvsnet_cost_reg_scratch_elems", D, h, w, device=volume.device, dtype=torch.float32,
+                           what="cost_reg: unsupported shape D=%d h=%d w=%d: each must be a multiple of 8 (the skip connections do not line up otherwise; the "
+                                "reference fails there too), D <= 4096, h, w <= 8192, D*h*w <= 2^26" % (D, h, w))
     out = torch.empty((D, h, w), dtype=torch.float32, device=volume.device)
-    scratch = torch.empty((ns,), dtype=torch.float32, device=volume.device)
-    with torch.cuda.device(volume.device):
-        _lib.check(L.hnr_mvsnet_cost_reg(_lib.ptr(volume), D, h, w, _lib.ptr(packed), _lib.ptr(out), _lib.ptr(scratch), ns, _lib.stream()), "hnr_mvsnet_cost_reg")
+    _lib.call("hnr_mvsnet_cost_reg", volume, D, h, w, packed, out, scratch, scratch.numel(), _lib.STREAM)
     return out
 
 
 def depth_head(logits, depth_values, want_prob=False):
     """hnr_mvsnet_depth_head: logits [D,h,w], depth_values [D] -> (depth [h,w], confidence [h,w], prob [D,h,w] or None)."""
-    L = _lib.lib()
     logits, depth_values = gpu_f32(logits, "logits"), gpu_f32(depth_values, "depth_values")
     if logits.dim() != 3 or tuple(depth_values.shape) != (logits.shape[0],):
         raise HnrError("depth_head: logits must be [D,h,w] and depth_values [D]")
-    same_device("depth_head", logits, depth_values)
     D, h, w = (int(s) for s in logits.shape)
     depth, conf = (torch.empty((h, w), dtype=torch.float32, device=logits.device) for _ in range(2))
     prob = torch.empty_like(logits) if want_prob else None
-    with torch.cuda.device(logits.device):
-        _lib.check(L.hnr_mvsnet_depth_head(_lib.ptr(logits), _lib.ptr(depth_values), D, h, w, _lib.ptr(depth), _lib.ptr(conf), _lib.ptr(prob), _lib.stream()),
-                   "hnr_mvsnet_depth_head")
+    _lib.call("hnr_mvsnet_depth_head", logits, depth_values, D, h, w, depth, conf, prob, _lib.STREAM)
     return depth, conf, prob
 
 
@@ -112,19 +94,16 @@ def kt_inverse(intrinsic):
 def depth_points(depth, confidence, H, W, near, far, intrinsic):
     """hnr_mvsnet_depth_points: depth, confidence [h,w] -> (cam_xyz [H,W,3], confidence [H,W], points_mask [H,W] bool)."""
     from .cloud_init import _cf
-    L = _lib.lib()
     depth, confidence = gpu_f32(depth, "depth"), gpu_f32(confidence, "confidence")
     if depth.dim() != 2 or confidence.shape != depth.shape:
         raise HnrError("depth_points: depth and confidence must be [h,w]")
-    same_device("depth_points", depth, confidence)
     h, w, H, W = int(depth.shape[0]), int(depth.shape[1]), int(H), int(W)
     M = kt_inverse(intrinsic)
     cam = torch.empty((H, W, 3), dtype=torch.float32, device=depth.device)
     conf = torch.empty((H, W), dtype=torch.float32, device=depth.device)
     mask = torch.empty((H, W), dtype=torch.uint8, device=depth.device)
-    with torch.cuda.device(depth.device):
-        _lib.check(L.hnr_mvsnet_depth_points(_lib.ptr(depth), _lib.ptr(confidence), h, w, H, W, float(np.float32(near)), float(np.float32(far)), _cf(M),
-                                             _lib.ptr(cam), _lib.ptr(conf), _lib.ptr(mask), _lib.stream()), "hnr_mvsnet_depth_points")
+    _lib.call("hnr_mvsnet_depth_points", depth, confidence, h, w, H, W, float(np.float32(near)), float(np.float32(far)), _cf(M), cam, conf, mask,
+              _lib.STREAM)
     return cam, conf, mask.bool()
 
 

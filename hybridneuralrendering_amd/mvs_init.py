@@ -38,22 +38,17 @@ class _ConvBnReLU(nn.Module):
 
 def featnet_forward(images, packed):
     """hnr_featnet_forward: images [V,3,H,W], packed [FEATNET_PACKED_ELEMS] -> (x1 [V,8,H,W], x2 [V,16,H2,W2], x3 [V,32,H4,W4])."""
-    L = _lib.lib()
     images, packed = _lib.require_gpu(images, "images", torch.float32), _lib.require_gpu(packed, "packed", torch.float32)
     if images.dim() != 4 or images.shape[1] != 3:
         raise HnrError("featnet_forward: images must be [V,3,H,W], got %s" % (tuple(images.shape),))
     if packed.numel() != _lib.FEATNET_PACKED_ELEMS or packed.device != images.device:
         raise HnrError("featnet_forward: packed must hold %d values on the images' device" % _lib.FEATNET_PACKED_ELEMS)
     V, _, H, W = (int(s) for s in images.shape)
-    ns = int(L.hnr_featnet_scratch_elems(V, H, W)) if max(V, H, W) < 2 ** 31 else -1
-    if ns < 0:
-        raise HnrError("featnet_forward: unsupported shape V=%d H=%d W=%d (1 <= V <= 4096, 4 <= H, W <= 32768)" % (V, H, W))
     dev = images.device
+    scratch = _lib.scratch("hnr_featnet_scratch_elems", V, H, W, device=dev, dtype=torch.float32,
+                           what="featnet_forward: unsupported shape V=%d H=%d W=%d (1 <= V <= 4096, 4 <= H, W <= 32768)" % (V, H, W))
     outs = [torch.empty((V, c, h, w), dtype=torch.float32, device=dev) for c, (h, w) in zip((8, 16, 32), pyramid_shape(H, W))]
-    scratch = torch.empty((ns,), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(L.hnr_featnet_forward(_lib.ptr(images), V, H, W, _lib.ptr(packed), _lib.ptr(outs[0]), _lib.ptr(outs[1]), _lib.ptr(outs[2]),
-                                         _lib.ptr(scratch), ns, _lib.stream()), "hnr_featnet_forward")
+    _lib.call("hnr_featnet_forward", images, V, H, W, packed, outs[0], outs[1], outs[2], scratch, scratch.numel(), _lib.STREAM)
     return tuple(outs)
 
 
@@ -62,7 +57,6 @@ def point_embed(xyz, w2c, c2w, cpc, intrinsic, image, x1, x2, x3, premlp, want_r
     conf [n] (optional): the photometric confidence premlp sees in the row's last column (hnr_point_embed_conf); None: ones.
     visible [n] uint8 (optional, cloud_init.point_occlusion's flags, hnr_point_embed_vis): where it is 0 the point counts as outside the frame."""
     from .cloud_init import _cf, _host_f32
-    L = _lib.lib()
     xyz = _lib.require_gpu(xyz, "xyz", torch.float32).reshape(-1, 3)
     image = _lib.require_gpu(image, "image", torch.float32)
     if image.dim() != 3 or image.shape[0] != 3:
@@ -90,19 +84,13 @@ def point_embed(xyz, w2c, c2w, cpc, intrinsic, image, x1, x2, x3, premlp, want_r
     row = torch.empty((n, 63), dtype=torch.float32, device=dev) if want_row else None
     if n > 0:
         a = [_host_f32(w2c, (4, 4), "w2c"), _host_f32(c2w, (4, 4), "c2w"), _host_f32(cpc, (3,), "cam_pos_cam"), _host_f32(intrinsic, (3, 3), "intrinsic")]
-        with torch.cuda.device(dev):
-            if visible is not None:
-                _lib.check(L.hnr_point_embed_vis(_lib.ptr(xyz), n, _cf(a[0]), _cf(a[1]), _cf(a[2]), _cf(a[3]), H, W, _lib.ptr(image), _lib.ptr(maps[0]),
-                                                 _lib.ptr(maps[1]), _lib.ptr(maps[2]), _lib.ptr(premlp), _lib.ptr(conf), _lib.ptr(visible), _lib.ptr(emb),
-                                                 _lib.ptr(color), _lib.ptr(pdir), _lib.ptr(row), _lib.stream()), "hnr_point_embed_vis")
-            elif conf is None:
-                _lib.check(L.hnr_point_embed(_lib.ptr(xyz), n, _cf(a[0]), _cf(a[1]), _cf(a[2]), _cf(a[3]), H, W, _lib.ptr(image), _lib.ptr(maps[0]),
-                                             _lib.ptr(maps[1]), _lib.ptr(maps[2]), _lib.ptr(premlp), _lib.ptr(emb), _lib.ptr(color), _lib.ptr(pdir), _lib.ptr(row),
-                                             _lib.stream()), "hnr_point_embed")
-            else:
-                _lib.check(L.hnr_point_embed_conf(_lib.ptr(xyz), n, _cf(a[0]), _cf(a[1]), _cf(a[2]), _cf(a[3]), H, W, _lib.ptr(image), _lib.ptr(maps[0]),
-                                                  _lib.ptr(maps[1]), _lib.ptr(maps[2]), _lib.ptr(premlp), _lib.ptr(conf), _lib.ptr(emb), _lib.ptr(color),
-                                                  _lib.ptr(pdir), _lib.ptr(row), _lib.stream()), "hnr_point_embed_conf")
+        head = (xyz, n, _cf(a[0]), _cf(a[1]), _cf(a[2]), _cf(a[3]), H, W, image, maps[0], maps[1], maps[2], premlp)
+        if visible is not None:
+            _lib.call("hnr_point_embed_vis", *head, conf, visible, emb, color, pdir, row, _lib.STREAM)
+        elif conf is None:
+            _lib.call("hnr_point_embed", *head, emb, color, pdir, row, _lib.STREAM)
+        else:
+            _lib.call("hnr_point_embed_conf", *head, conf, emb, color, pdir, row, _lib.STREAM)
     return emb, color, pdir, row
 
 

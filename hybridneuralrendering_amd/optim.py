@@ -137,7 +137,6 @@ class DeviceAdam:
     def _prepare(self, todo):
         """The device tables for this (parameter, gradient) set: the tensor table follows the pointers, the chunk table the sizes.  Rebuilt only
         when one of them changes (never under TrainPath.reuse_outputs or a captured step)."""
-        L = _lib.lib()
         if self.device.type != "cuda":
             raise HnrError("DeviceAdam.step: the parameters must be on the GPU (the HIP path has no CPU fallback)")
         tkey = tuple((p.data_ptr(), g.data_ptr(), gi) for p, g, gi in todo)
@@ -155,16 +154,12 @@ class DeviceAdam:
         ckey = tuple((p.numel(), gi) for p, g, gi in todo)
         ng = len(self.param_groups)
         if ckey != self._ckey:
-            nc = int(L.hnr_adam_plan(tab, n, ng, None, 0))
-            if nc < 0:
-                _lib.check(nc, "hnr_adam_plan")
+            nc = _lib.size("hnr_adam_plan", tab, n, ng, None, 0)
             chunks = np.zeros((max(nc, 1), 2), dtype=np.int32)
-            nc = int(L.hnr_adam_plan(tab, n, ng, chunks.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), nc))
-            if nc < 0:
-                _lib.check(nc, "hnr_adam_plan")
+            nc = _lib.size("hnr_adam_plan", tab, n, ng, chunks.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), nc)
             self._chunks, self._n_chunks, self._ckey = torch.from_numpy(chunks).to(self.device), nc, ckey
-        elif int(L.hnr_adam_plan(tab, n, ng, None, 0)) < 0:
-            _lib.check(-1, "hnr_adam_plan")
+        else:
+            _lib.size("hnr_adam_plan", tab, n, ng, None, 0)
         raw = np.frombuffer(tab, dtype=np.uint8).copy()
         self._tensors = torch.from_numpy(raw).to(self.device)          # (torch allocations are at least 256-byte aligned)
         self._n_tensors, self._tkey = n, tkey
@@ -175,7 +170,6 @@ class DeviceAdam:
         launch of the two kernels (on private one-element buffers: nothing of the optimiser's state moves)."""
         self._prepare(self._gradient_list(grads))
         if not self._warm:
-            L = _lib.lib()
             dev = self.device
             z = torch.zeros((4, 4), dtype=torch.float32, device=dev)
             t = (_lib.AdamTensor * 1)()
@@ -183,20 +177,16 @@ class DeviceAdam:
             dt = torch.from_numpy(np.frombuffer(t, dtype=np.uint8).copy()).to(dev)
             ch = torch.zeros((1, 2), dtype=torch.int32, device=dev)
             cnt, rows = torch.zeros((2,), dtype=torch.int64, device=dev), torch.zeros((1, _lib.ADAM_ROW_DOUBLES), dtype=torch.float64, device=dev)
-            with torch.cuda.device(dev):
-                _lib.check(L.hnr_adam_step(_lib.ptr(cnt), _lib.ptr(self._groups), 1, _lib.ptr(rows), _lib.ptr(dt), 1, _lib.ptr(ch), 1, _lib.stream()),
-                           "hnr_adam_step")
+            _lib.call("hnr_adam_step", cnt, self._groups, 1, rows, dt, 1, ch, 1, _lib.STREAM)
             torch.cuda.current_stream(dev).synchronize()            # (the private buffers die here)
             self._warm = True
 
     def step(self, grads=None):
         """One optimiser step on the current stream: the tick launch, then the update launch.  grads: a mapping (by the group's `names`, else by
         parameter) of gradient tensors read in place -- train_step's `pg` / `ag` dictionaries merged -- or None: the parameters' .grad fields."""
-        L = _lib.lib()
         self._prepare(self._gradient_list(grads))
-        with torch.cuda.device(self.device):
-            _lib.check(L.hnr_adam_step(_lib.ptr(self._counters), _lib.ptr(self._groups), len(self.param_groups), _lib.ptr(self._rows),
-                                       _lib.ptr(self._tensors), self._n_tensors, _lib.ptr(self._chunks), self._n_chunks, _lib.stream()), "hnr_adam_step")
+        _lib.call("hnr_adam_step", self._counters, self._groups, len(self.param_groups), self._rows, self._tensors, self._n_tensors, self._chunks,
+                  self._n_chunks, _lib.STREAM)
         self._warm = True
         self.mark_updated()
 

@@ -141,9 +141,9 @@ class LPIPS(PackedWeights, nn.Module):
         return super().packed()
 
     def check_packed(self, pk):
-        if pk.numel() != int(_lib.lib().hnr_lpips_packed_elems(NETS[self.net_name])):
-            raise HnrError("LPIPS: the packed image has %d elements, the library expects %d" % (
-                pk.numel(), int(_lib.lib().hnr_lpips_packed_elems(NETS[self.net_name]))))
+        n = _lib.size("hnr_lpips_packed_elems", NETS[self.net_name])
+        if pk.numel() != n:
+            raise HnrError("LPIPS: the packed image has %d elements, the library expects %d" % (pk.numel(), n))
 
     # ---- plumbing ----------------------------------------------------------------------------------------------------------------------------------
     def _net(self):
@@ -166,15 +166,13 @@ class LPIPS(PackedWeights, nn.Module):
         """The scratch of one image size, kept: [bytes] uint8 on the module's device."""
         key = (h, w, str(self.shift.device))
         if key not in self._scratch:
-            n = int(_lib.lib().hnr_lpips_scratch_bytes(self._net(), h, w))
-            if n < 0:
-                raise HnrError("hnr_lpips_scratch_bytes refused %s %dx%d" % (self.net_name, h, w))
-            self._scratch[key] = torch.empty((n,), dtype=torch.uint8, device=self.shift.device)
+            self._scratch[key] = _lib.scratch("hnr_lpips_scratch_bytes", self._net(), h, w, device=self.shift.device,
+                                              what="hnr_lpips_scratch_bytes refused %s %dx%d" % (self.net_name, h, w))
         return self._scratch[key]
 
     def tap_dims(self, h, w):
         dims = (ctypes.c_int * 15)()
-        _lib.check(_lib.lib().hnr_lpips_tap_dims(self._net(), h, w, dims), "hnr_lpips_tap_dims")
+        _lib.call("hnr_lpips_tap_dims", self._net(), h, w, dims)
         return [tuple(dims[3 * k:3 * k + 3]) for k in range(5)]
 
     def _images8(self, img8, gt8, what):
@@ -215,18 +213,14 @@ class LPIPS(PackedWeights, nn.Module):
         """hnr_lpips_prepare: two [h,w,3] uint8 RGB images -> [2,3,h,w] float32, the network's input."""
         h, w = self._images8(img8, gt8, "LPIPS.prepare8")
         x = torch.empty((2, 3, h, w), dtype=torch.float32, device=img8.device)
-        with torch.cuda.device(img8.device):
-            _lib.check(_lib.lib().hnr_lpips_prepare(_lib.ptr(img8), _lib.ptr(gt8), h, w, int(self.channel_order == "bgr"), _lib.ptr(self.packed()),
-                                                    _lib.ptr(x), _lib.stream()), "hnr_lpips_prepare")
+        _lib.call("hnr_lpips_prepare", img8, gt8, h, w, int(self.channel_order == "bgr"), self.packed(), x, _lib.STREAM)
         return x
 
     def prepare_f32(self, in0, in1):
         """hnr_lpips_prepare_f32: two [1,3,H,W] float images in [-1, 1] -> [2,3,H,W], the ScalingLayer's output."""
         a, b, h, w = self._images_f32(in0, in1, "LPIPS.prepare_f32")
         x = torch.empty((2, 3, h, w), dtype=torch.float32, device=a.device)
-        with torch.cuda.device(a.device):
-            _lib.check(_lib.lib().hnr_lpips_prepare_f32(_lib.ptr(a), _lib.ptr(b), h, w, _lib.ptr(self.packed()), _lib.ptr(x), _lib.stream()),
-                       "hnr_lpips_prepare_f32")
+        _lib.call("hnr_lpips_prepare_f32", a, b, h, w, self.packed(), x, _lib.STREAM)
         return x
 
     def tap_features(self, x):
@@ -240,9 +234,7 @@ class LPIPS(PackedWeights, nn.Module):
         taps = [torch.empty((2,) + d, dtype=torch.float32, device=x.device) for d in self.tap_dims(h, w)]
         ptrs = (ctypes.c_void_p * 5)(*[t.data_ptr() for t in taps])
         s = self.scratch(h, w)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().hnr_lpips_features(self._net(), _lib.ptr(x), h, w, _lib.ptr(self.packed()), ptrs, _lib.ptr(s), s.numel(), _lib.stream()),
-                       "hnr_lpips_features")
+        _lib.call("hnr_lpips_features", self._net(), x, h, w, self.packed(), ptrs, s, s.numel(), _lib.STREAM)
         return taps
 
     def score(self, taps, h, w, out=None, row=0):
@@ -256,9 +248,7 @@ class LPIPS(PackedWeights, nn.Module):
         out = self._table(out, row, "LPIPS.score")
         ptrs = (ctypes.c_void_p * 5)(*[t.data_ptr() for t in taps])
         s = self.scratch(h, w)
-        with torch.cuda.device(taps[0].device):
-            _lib.check(_lib.lib().hnr_lpips_score(self._net(), ptrs, h, w, _lib.ptr(self.packed()), _lib.ptr(out[row]), _lib.ptr(s), s.numel(), _lib.stream()),
-                       "hnr_lpips_score")
+        _lib.call("hnr_lpips_score", self._net(), ptrs, h, w, self.packed(), out[row], s, s.numel(), _lib.STREAM)
         return out
 
     # ---- the whole chain ---------------------------------------------------------------------------------------------------------------------------
@@ -269,9 +259,7 @@ class LPIPS(PackedWeights, nn.Module):
         self._check_size(h, w, "LPIPS.pair8")
         out = self._table(out, row, "LPIPS.pair8")
         s = self.scratch(h, w)
-        with torch.cuda.device(img8.device):
-            _lib.check(_lib.lib().hnr_lpips(self._net(), _lib.ptr(img8), _lib.ptr(gt8), h, w, int(self.channel_order == "bgr"), _lib.ptr(self.packed()),
-                                            _lib.ptr(out[row]), _lib.ptr(s), s.numel(), _lib.stream()), "hnr_lpips")
+        _lib.call("hnr_lpips", self._net(), img8, gt8, h, w, int(self.channel_order == "bgr"), self.packed(), out[row], s, s.numel(), _lib.STREAM)
         return out
 
     def forward(self, in0, in1, normalize=False, retPerLayer=False):
@@ -285,7 +273,5 @@ class LPIPS(PackedWeights, nn.Module):
             a, b = 2 * a - 1, 2 * b - 1
         out = torch.zeros((1, NROW), dtype=torch.float64, device=a.device)
         s = self.scratch(h, w)
-        with torch.cuda.device(a.device):
-            _lib.check(_lib.lib().hnr_lpips_f32(self._net(), _lib.ptr(a), _lib.ptr(b), h, w, _lib.ptr(self.packed()), _lib.ptr(out[0]), _lib.ptr(s), s.numel(),
-                                                _lib.stream()), "hnr_lpips_f32")
+        _lib.call("hnr_lpips_f32", self._net(), a, b, h, w, self.packed(), out[0], s, s.numel(), _lib.STREAM)
         return out[0, 0].to(torch.float32).reshape(1, 1, 1, 1)

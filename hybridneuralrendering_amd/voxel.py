@@ -25,7 +25,6 @@ def construct_vox_points_closest(xyz_val, vox_res, partition_xyz=None, space_min
     """xyz_val [N,3] fp32 on the GPU -> (xyz_centroid [V,3], sparse_grid_idx [V,3] int32 in torch.unique order, min_idx [V] int64)."""
     if partition_xyz is not None or space_min is not None or space_max is not None:
         raise HnrError("construct_vox_points_closest: only the shipped call form (xyz, vox_res) is implemented")
-    L = _lib.lib()
     xyz = _lib.require_gpu(xyz_val, "xyz_val", torch.float32)
     if xyz.dim() != 2 or xyz.shape[1] != 3:
         raise HnrError("xyz_val must be [N,3]")
@@ -33,8 +32,7 @@ def construct_vox_points_closest(xyz_val, vox_res, partition_xyz=None, space_min
     if n == 0:
         return xyz.new_zeros((0, 3)), torch.zeros((0, 3), dtype=torch.int32, device=dev), torch.zeros((0,), dtype=torch.int64, device=dev)
     b6 = torch.empty((6,), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(L.hnr_points_bounds(_lib.ptr(xyz), n, _lib.ptr(b6), _lib.stream()), "hnr_points_bounds")
+    _lib.call("hnr_points_bounds", xyz, n, b6, _lib.STREAM)
     b = b6.cpu().numpy()
     smin, vsz = space_of(b[:3], b[3:], vox_res)
     cen = torch.empty((n, 3), dtype=torch.float32, device=dev)
@@ -42,13 +40,9 @@ def construct_vox_points_closest(xyz_val, vox_res, partition_xyz=None, space_min
     midx = torch.empty((n,), dtype=torch.int32, device=dev)
     inv = torch.empty((n,), dtype=torch.int32, device=dev) if return_inverse else None
     cnt = torch.zeros((1,), dtype=torch.int64, device=dev)
-    nbytes = int(L.hnr_voxel_downsample_scratch_bytes(n))
-    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    scratch = _lib.scratch("hnr_voxel_downsample_scratch_bytes", n, device=dev)
     sm = (ctypes.c_float * 3)(*[float(v) for v in smin])
-    with torch.cuda.device(dev):
-        _lib.check(L.hnr_voxel_downsample(_lib.ptr(xyz), n, sm, float(vsz), _lib.ptr(cen), _lib.ptr(gidx), _lib.ptr(midx),
-                                          _lib.ptr(inv) if inv is not None else None, _lib.ptr(cnt), _lib.ptr(scratch), nbytes, _lib.stream()),
-                   "hnr_voxel_downsample")
+    _lib.call("hnr_voxel_downsample", xyz, n, sm, float(vsz), cen, gidx, midx, inv, cnt, scratch, scratch.numel(), _lib.STREAM)
     v = int(cnt.item())
     out = (cen[:v], gidx[:v], midx[:v].long())
     return out + (inv.long(),) if return_inverse else out

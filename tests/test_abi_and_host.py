@@ -34,6 +34,57 @@ def test_library_exports_every_declared_symbol():
     assert _lib.lib().hnr_version().startswith(b"hnr-hip")
 
 
+def _header_prototypes():
+    """[(return type, name, [parameter text])] of every prototype in include/hnr.h, comments stripped, whitespace collapsed."""
+    src = open(os.path.join(ROOT, "include", "hnr.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = re.sub(r"//[^\n]*", "", src)
+    out = []
+    for ret, name, params in re.findall(r"(?m)^\s*((?:const\s+)?\w+\s*\**)\s*\b(hnr_\w+)\s*\(([^()]*)\)\s*;", src):
+        params = [" ".join(p.split()) for p in params.split(",")]
+        out.append((" ".join(ret.split()), name, [] if params == ["void"] else params))
+    return out
+
+
+def test_signature_table_matches_the_header():
+    """_lib.SIGNATURES against the prototypes of include/hnr.h: arity, return type, every scalar parameter's exact type, a pointer type for every
+    pointer parameter, and the header's element type or struct behind every typed POINTER(...)."""
+    from hybridneuralrendering_amd import _lib
+    scalars = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double,
+               "int8_t": ctypes.c_int8, "uint8_t": ctypes.c_uint8, "uint32_t": ctypes.c_uint32, "uint64_t": ctypes.c_uint64}
+    structs = {"hnr_grid_params": _lib.GridParams, "hnr_grid_stats": _lib.GridStats, "hnr_query_params": _lib.QueryParams,
+               "hnr_render_params": _lib.RenderParams, "hnr_render_cloud": _lib.RenderCloud, "hnr_render_weights": _lib.RenderWeights,
+               "hnr_render_camera": _lib.RenderCamera, "hnr_render_views": _lib.RenderViews, "hnr_render_outputs": _lib.RenderOutputs,
+               "hnr_train_params": _lib.TrainParams, "hnr_train_cloud": _lib.TrainCloud, "hnr_train_cloud_grads": _lib.TrainCloudGrads,
+               "hnr_train_weights": _lib.TrainWeights, "hnr_train_views": _lib.TrainViews, "hnr_frame_bank": _lib.FrameBankC,
+               "hnr_frame_batch_params": _lib.FrameBatchParams, "hnr_frame_batch_out": _lib.FrameBatchOut, "hnr_depth_bank": _lib.DepthBankC,
+               "hnr_adam_tensor": _lib.AdamTensor, "hnr_blur_learn_params": _lib.BlurLearnParams, "hnr_blur_learn_weights": _lib.BlurLearnWeights}
+    returns = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "const char *": ctypes.c_char_p}
+    protos = _header_prototypes()
+    assert sorted(n for _, n, _ in protos) == sorted(_lib.SIGNATURES), "the prototype pattern no longer finds every declared function"
+    for ret, name, params in protos:
+        res, args = _lib.SIGNATURES[name]
+        assert ret in returns and res is returns[ret], "%s: returns %r in the header, %r in the table" % (name, ret, res)
+        assert len(args) == len(params), "%s: %d parameters in the header, %d in the table" % (name, len(params), len(args))
+        for i, (text, t) in enumerate(zip(params, args)):
+            where = "%s, parameter %d (%s)" % (name, i, text)
+            m = re.match(r"^(?:const )?(\w+) ?(\*[\w *]*?)? ?\b\w+(\[\d*\])?$", text)
+            assert m, "%s: not understood" % where
+            elem, stars = m.group(1), (m.group(2) or "").count("*") + (1 if m.group(3) else 0)
+            if stars == 0:
+                assert elem in scalars and t is scalars[elem], "%s: a scalar of another type in the table: %r" % (where, t)
+                continue
+            assert t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer), "%s: no pointer type in the table: %r" % (where, t)
+            if issubclass(t, ctypes._Pointer):
+                inner = t._type_
+                if stars > 1:
+                    assert inner is ctypes.c_void_p or issubclass(inner, ctypes._Pointer), "%s: POINTER(%r) for a pointer to pointers" % (where, inner)
+                elif issubclass(inner, ctypes.Structure):
+                    assert structs.get(elem) is inner, "%s: POINTER(%s) in the table" % (where, inner.__name__)
+                else:
+                    assert elem in scalars and inner is scalars[elem], "%s: POINTER(%r) in the table" % (where, inner)
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     from hybridneuralrendering_amd import _lib
     monkeypatch.setattr(_lib, "_lib", None)
