@@ -260,7 +260,8 @@ __global__ __launch_bounds__(256, RT >= 4 ? 1 : 2) void chain_kernel(ChainArgs a
         // ---- layer 1 (block1.2) -> operand of block3.0 = [H2 | extras]
         {
             zero_acc();
-            h2_mfma_layer<RT, 2, CH_S1, 0, CH_WSTEP, ch_slot(RT)>(wsrd, CH_W1, woff, lds, lane, acc, []() {});
+            // k steps 8..15, 0..7: the order the weight-stationary kernel adds them in (csrc/chain_ws.hip, cw_korder), so that the two kernels give the same bits
+            h2_mfma_layer<RT, 2, CH_S1, 0, CH_WSTEP, ch_slot(RT), -1, 0, 0, 0, 8>(wsrd, CH_W1, woff, lds, lane, acc, []() {});
             CH_STAMP(4);
             float amax[RT];
             activate(1, amax, std::false_type{});

@@ -56,8 +56,10 @@ __device__ __forceinline__ f32x2 f32x2_fma(f32x2 a, f32x2 b, f32x2 c) { return f
 // group's epilogue (6.2 instead of 5.0 cycles per VALU instruction there, 34.0 instead of 32.0 cycles per MFMA here).
 // after(): called once, right after the layer's LAST weight-fragment loads have been issued: loads placed there (gathered addends ...) are
 // not waited for by any later weight wait of the layer (vmcnt counts in order), yet run under the remaining k steps' MFMAs.
+// KROT: iteration i of the loop runs k step (i + KROT) % S.  The fp32 accumulators add the k steps in that order, so a kernel that must give another
+// kernel's bits runs the order that kernel runs (csrc/chain_ws.hip runs block1.2 as 8..15, 0..7: cw_korder).
 struct H2NoHook { __device__ __forceinline__ void operator()() const {} };
-template <int RT, int CT, int S, int PRELOAD_ALL, int WSTEP, int SLOT, int BAR = -1, int WSAME = 0, int PACE = 0, int PDO = 0, class Mid, class After = H2NoHook>
+template <int RT, int CT, int S, int PRELOAD_ALL, int WSTEP, int SLOT, int BAR = -1, int WSAME = 0, int PACE = 0, int PDO = 0, int KROT = 0, class Mid, class After = H2NoHook>
 __device__ __forceinline__ void h2_mfma_layer(__amdgpu_buffer_rsrc_t wsrd, int wbase, unsigned woff, const char *lds, int lane, f32x16 (&acc)[RT][CT], Mid mid, After after = After())
 {
     constexpr int PD = PDO > 0 ? PDO : (RT * CT >= 8 ? 2 : 3);          // k steps of weight fragments in flight
@@ -66,6 +68,7 @@ __device__ __forceinline__ void h2_mfma_layer(__amdgpu_buffer_rsrc_t wsrd, int w
     asm volatile("" : "+s"(wbase));                                       // per-tile opaque: the k-step offsets are s_add'ed here, not hoisted out of the tile loop (SGPR spills)
     const char *bp = lds + lane * 16;                                     // fragment (s, rt, plane p) at s * SLOT + (rt * 2 + p) * 1024
     constexpr int NW = PRELOAD_ALL ? S : PD + 1;
+    auto ks = [](int i) { return KROT ? (i + KROT) % S : i; };          // k step of iteration i
     u32x4 wf[NW][CT][2], bf[2][RT][2];
     auto load_w = [&](int slot, int s) {
 #pragma unroll
@@ -81,20 +84,20 @@ __device__ __forceinline__ void h2_mfma_layer(__amdgpu_buffer_rsrc_t wsrd, int w
     };
     if (PRELOAD_ALL) {
 #pragma unroll
-        for (int s = 0; s < S; ++s) load_w(s, s);
+        for (int s = 0; s < S; ++s) load_w(s, ks(s));
     } else {
 #pragma unroll
-        for (int s = 0; s < PD && s < S; ++s) load_w(s, s);
+        for (int s = 0; s < PD && s < S; ++s) load_w(s, ks(s));
     }
     __builtin_amdgcn_sched_barrier(0);
     mid();                                                                // loads the caller wants queued BEHIND the first weight fragments
     __builtin_amdgcn_sched_barrier(0);
-    load_b(0, 0);
+    load_b(0, ks(0));
 #pragma unroll
     for (int s = 0; s < S; ++s) {
         if (PACE == 0) {
-            if (!PRELOAD_ALL && s + PD < S) load_w((s + PD) % (PD + 1), s + PD);
-            if (s + 1 < S) load_b((s + 1) & 1, s + 1);
+            if (!PRELOAD_ALL && s + PD < S) load_w((s + PD) % (PD + 1), ks(s + PD));
+            if (s + 1 < S) load_b((s + 1) & 1, ks(s + 1));
         }
         if (s == (PRELOAD_ALL || S <= PD ? 0 : S - 1 - PD)) { __builtin_amdgcn_sched_barrier(0); after(); __builtin_amdgcn_sched_barrier(0); }
         const int ws = PRELOAD_ALL ? s : s % (PD + 1), bs = s & 1;
@@ -111,11 +114,11 @@ __device__ __forceinline__ void h2_mfma_layer(__amdgpu_buffer_rsrc_t wsrd, int w
                 bool load = false;
                 if (has_b && m < 2 * RT) {
                     const int r2 = m >> 1, p2 = m & 1;
-                    bf[(s + 1) & 1][r2][p2] = *reinterpret_cast<const u32x4 *>(bp + (s + 1) * SLOT + (r2 * 2 + p2) * 1024);
+                    bf[(s + 1) & 1][r2][p2] = *reinterpret_cast<const u32x4 *>(bp + ks(s + 1) * SLOT + (r2 * 2 + p2) * 1024);
                     load = true;
                 } else if (has_w && m >= 2 * RT && m < 2 * RT + 2 * CT) {
                     const int i2 = m - 2 * RT, c2 = i2 >> 1, p2 = i2 & 1;
-                    wf[(s + PD) % (PD + 1)][c2][p2] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(wsrd, woff + (c2 * 2 + p2) * 1024, wbase + (WSAME ? 0 : s + PD) * WSTEP, 0));
+                    wf[(s + PD) % (PD + 1)][c2][p2] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(wsrd, woff + (c2 * 2 + p2) * 1024, wbase + (WSAME ? 0 : ks(s + PD)) * WSTEP, 0));
                     load = true;
                 }
                 if (load) asm volatile("s_nop %0" :: "n"(PACE > 1 ? PACE - 2 : 0)); else asm volatile("s_nop %0" :: "n"(PACE > 0 ? PACE - 1 : 0));
